@@ -10,19 +10,25 @@ bench.py -- env-steps/s of the batched docking3d step() on N MI355X (BASELINE.js
 A "step" is one launch of the fused HIP step kernel over this rank's envs (weak scaling: the per-GPU env count is
 fixed; at N = 1 the K launches of a region are queued by one dockauv_step_sequence call), followed -- for N > 1 --
 by one gather of [obs | reward | done] over xGMI so that a single learner sees all observations.  Inputs (actions)
-are resident in HBM before the timed region.  A timed region is EXACTLY K steps between barrier + synchronize on both
-sides (max over ranks); regions are repeated until --min-seconds have been measured and the MEDIAN region is
-reported (`reps`, `ms_per_step_first_region` and `ms_per_step_min` beside it), so that a short --steps is meaningful.
-Rank 0 prints ONE JSON line.
+are resident in HBM before the timed region.  After W warm-up steps, ONE timed region of EXACTLY K steps runs between
+barrier + synchronize on both sides (max over ranks): `ms_per_step` = region time / K.  Rank 0 prints ONE JSON line.
+
+A plain run measures the headline alone (its line carries the roofline of the timed region's own HIP events at N = 1).
+--full adds everything else the line has carried: the CPU baselines, the other BASELINE configs, the ray-dense points,
+the batch-size sweep, the closed-loop and resident-sequence rates, per-dispatch kernel timing and the N > 1
+sub-measurements; those sub-measurements repeat their regions until --min-seconds have been measured.
+--dump-outputs DIR writes what the last timed step returned to its caller (obs, reward, done of every env; a fixed,
+seeded sample of the envs where that exceeds 60 MiB) as DIR/<name>.npy, float32: with the same arguments the inputs are
+the same from run to run, so two builds can be compared output for output.
 
 Workloads (--config):
   2  BlueROV2, SimpleDocking3d, 4 096 envs/GPU, no obstacles (pure 6-DOF RKF45 + reward)
   3  BlueROV2, 16-beam fan vs 8 spheres, 65 536 envs/GPU          [default at N = 1: the largest single-GPU config]
   4  LAUV, ObstaclesDocking3d (5 capsules, 63 rays), t_step_size 0.02, 32 768 envs/GPU      [default at N > 1]
   5  BlueROV2/LAUV 50/50, ObstaclesCurrentDocking3d, current speed U(0,1), t_step_size 0.02, 65 536 envs/GPU
-`roofline.kernel_us` = HIP events recorded on the launch stream around each timed region / K (the average launch duration,
+`roofline.kernel_us` = HIP events recorded on the launch stream around the timed region / K (the average launch duration,
 launch boundary included; `--isolated-kernel-timing` adds the older per-dispatch events on launches issued one by one).
-At N = 1 the line also carries `configs`: the same measurement (open-loop rate, kernel duration by HIP events,
+With --full, at N = 1 the line also carries `configs`: the same measurement (open-loop rate, kernel duration by HIP events,
 roofline, closed-loop rate) of config 2 at 4 096 envs and of the per-GPU shards of configs 4 and 5.
 """
 import argparse
@@ -249,13 +255,17 @@ def roofline_of(config_id: int, envs: int, kernel_us: float, n_timed: int, ksha:
     return r
 
 
-def timed_regions(run, steps, warmup_steps, warm_i0, min_seconds, max_reps, sync, barrier, reduce_max, event_ms=None, torch=None):
+def timed_regions(run, steps, warmup_steps, warm_i0, min_seconds, max_reps, sync, barrier, reduce_max, event_ms=None, torch=None,
+                  prepare=None):
     """Warm up, then time regions of EXACTLY `steps` steps (barrier + synchronize on both sides, max over ranks) until
-    `min_seconds` have been measured.  Returns the list of region durations (host clock).  event_ms (a list): each
-    region is also bracketed by two HIP events recorded on the launch stream (torch's current stream: the one the steps are
-    queued on); their elapsed times in ms are appended to it."""
+    `min_seconds` have been measured or `max_reps` regions have run.  Returns the list of region durations (host clock).
+    event_ms (a list): each region is also bracketed by two HIP events recorded on the launch stream (torch's current
+    stream: the one the steps are queued on); their elapsed times in ms are appended to it.  prepare(steps, i0): called
+    after the warm-up, before the clock starts (host-side set-up of the region, e.g. its step sequence)."""
     if warmup_steps > 0:
         run(warmup_steps, warm_i0)
+    if prepare is not None:
+        prepare(steps, warm_i0 + warmup_steps)
     times = []
     while True:
         sync(); barrier(); sync()
@@ -541,6 +551,36 @@ def measure_single(config_id, envs, args, torch, dev, local_rank, rank, ksha, ke
     return res
 
 
+# --dump-outputs: at most this many bytes of arrays (beyond it, a fixed sample of the envs)
+DUMP_LIMIT_BYTES = 60 * 2**20
+
+
+def step_outputs(rows, n_obs: int, pack_mode):
+    """What a caller of the timed path receives from one step, as host float32 arrays: obs [N, n_obs], reward [N], done [N]
+    (1.0 / 0.0), from packed [obs | reward | done] rows (bf16 rows: observation columns widened from bfloat16)."""
+    from gym_dockauv_amd.parallel import ShardedStepper
+    obs, rew, done = (ShardedStepper.split_bf16 if pack_mode == "bf16" else ShardedStepper.split)(rows, n_obs)
+    return {"obs": obs.float().cpu().numpy(), "reward": rew.float().cpu().numpy(), "done": done.float().cpu().numpy()}
+
+
+def write_outputs(directory: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES, seed: int = 0) -> dict:
+    """Write each array (first axis: env) as <directory>/<name>.npy (float64 stays float64, anything else float32).  If they
+    hold more than `limit` bytes, the same seeded sample of the envs is taken from every array and the sampled env indices
+    are written beside them as sample_rows.npy (float64).  Returns {name: shape}."""
+    arrays = {k: np.asarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        per_env = total / n + 8
+        rows = np.sort(np.random.default_rng(seed).choice(n, int(limit // per_env), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def split_json_line(out: str):
     """(the LAST line of `out` that is a JSON object, every other line) -- (None, []) if there is none."""
     lines = out.splitlines()
@@ -611,7 +651,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--config", type=int, default=0, help="0 = config 3 at N = 1, config 4 (32 768 envs per GPU) at N > 1")
     ap.add_argument("--envs", type=int, default=0, help="envs per GPU (0 = the config's size)")
-    ap.add_argument("--min-seconds", type=float, default=0.2, help="timed regions are repeated until this much has been measured")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: CPU baselines, the other BASELINE configs, ray-dense points, "
+                         "the batch-size sweep, closed-loop and resident-sequence rates, per-dispatch kernel timing, the N > 1 "
+                         "sub-measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write obs / reward / done of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--min-seconds", type=float, default=0.2,
+                    help="--full: the sub-measurements repeat their timed regions until this much has been measured")
     ap.add_argument("--max-reps", type=int, default=4000)
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu", action="store_true")
@@ -640,6 +687,8 @@ def main():
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--sweep", type=int, nargs="*", default=[262144, 1048576])
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.cpu_worker:      # oracle loop only: no torch, no GPU
         print(cpu_baseline(workload(args.config or 3, 2), args.cpu_seconds)["value"])
         return
@@ -770,21 +819,30 @@ def main():
     # Python per step.  With RCCL in the loop the steps are issued one by one (the gather sits between them).
     seq_cache = {}
 
-    def run(n, i0=0):
+    def sequence(n, i0=0):
+        """The prepared sequence of n steps from step i0 (built on first use), or None where steps are issued one by one."""
         if not use_dist:
             key = (n, i0 % RING)
             if key not in seq_cache:
                 out_ptr = stepper.local_slice(stepper.bufs[0]).data_ptr()
                 seq_cache[key] = env.make_step_sequence([actions[i % RING].data_ptr() for i in range(i0, i0 + n)],
                                                         [out_ptr] * n, packed=True)
-            env.run_step_sequence(seq_cache[key], stream=stream)
-            return
+            return seq_cache[key]
         if transport == "p2p" and not args.no_overlap:
-            # one host call: n step kernels, the gather of step t riding in the grid of step kernel t + 1
             key = (n, i0 % RING, stepper.gather.t & 1)
             if key not in seq_cache:
                 seq_cache[key] = stepper.make_sequence(env, [actions[i % RING].data_ptr() for i in range(i0, i0 + n)])
-            stepper.run_sequence(env, seq_cache[key])
+            return seq_cache[key]
+        return None
+
+    def run(n, i0=0):
+        seq = sequence(n, i0)
+        if not use_dist:
+            env.run_step_sequence(seq, stream=stream)
+            return
+        if seq is not None:
+            # one host call: n step kernels, the gather of step t riding in the grid of step kernel t + 1
+            stepper.run_sequence(env, seq)
             return
         for i in range(i0, i0 + n):
             stepper.step(actions[i % RING])
@@ -801,9 +859,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
+    # the headline: ONE region of exactly --steps steps after the warm-up (its step sequence prepared before the clock starts)
     region_ev_ms = []
-    times = timed_regions(run, args.steps, max(0, args.warmup - n_verify), n_verify, args.min_seconds, args.max_reps,
-                          torch.cuda.synchronize, barrier, reduce_max, event_ms=None if use_dist else region_ev_ms, torch=torch)
+    times = timed_regions(run, args.steps, max(0, args.warmup - n_verify), n_verify, 0.0, 1,
+                          torch.cuda.synchronize, barrier, reduce_max, event_ms=None if use_dist else region_ev_ms, torch=torch,
+                          prepare=sequence)
     if transport == "p2p":
         # a stamp that did not arrive within the spin bound voids the regions on every rank: measure again over RCCL
         late = torch.tensor([stepper.gather.timed_out()], device=dev, dtype=torch.int64)
@@ -815,14 +875,24 @@ def main():
             stepper.close()
             stepper, transport = rccl_stepper, "rccl"
             seq_cache.clear()
-            times = timed_regions(run, args.steps, args.warmup, 0, args.min_seconds, args.max_reps,
-                                  torch.cuda.synchronize, barrier, reduce_max)
+            times = timed_regions(run, args.steps, args.warmup, 0, 0.0, 1,
+                                  torch.cuda.synchronize, barrier, reduce_max, prepare=sequence)
     dt = statistics.median(times)
+
+    # what the caller of the timed path received from its last step: the rows every rank holds after the gather (rank 0's copy)
+    if transport == "p2p":
+        last_rows = stepper.bufs[(stepper.gather.t - 1) % stepper.gather.nb]
+    else:
+        last_rows = stepper.bufs[(stepper.i - 1) % len(stepper.bufs)] if use_dist else stepper.bufs[0]
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        torch.cuda.synchronize()
+        dumped = write_outputs(args.dump_outputs, step_outputs(last_rows, n_obs, pack_mode))
 
     # for comparison: the same steps with the RCCL all-gather as the transport, issued step by step from Python (the
     # p2p regions are queued by one host call: the two paces differ by host pacing as well as by transport)
     rccl_ms = None
-    if transport == "p2p" and os.environ.get("DOCKAUV_DIST_BACKEND", "nccl") != "gloo":   # (gloo rehearsal: far too slow)
+    if args.full and transport == "p2p" and os.environ.get("DOCKAUV_DIST_BACKEND", "nccl") != "gloo":   # (gloo rehearsal: far too slow)
         k2 = min(args.steps, 2000)
         torch.cuda.synchronize()
         dist.barrier()
@@ -840,7 +910,7 @@ def main():
     # single-GPU line is measured): the per-GPU rate this workload reaches alone.  The weak-scaling efficiency of the
     # line is value / (n_gpus * this) -- the default single-GPU line is a different workload (config 3, the headline).
     alone = None
-    if use_dist:
+    if use_dist and args.full:
         alone_cache = {}
 
         def run_alone(n, i0=0):
@@ -859,7 +929,7 @@ def main():
 
     # the same regions with half-precision rows over the links (RCCL transport): observation columns bfloat16
     bf16_gather = None
-    if use_dist and transport == "rccl" and pack_mode is True and os.environ.get("DOCKAUV_DIST_BACKEND", "nccl") != "gloo":
+    if args.full and use_dist and transport == "rccl" and pack_mode is True and os.environ.get("DOCKAUV_DIST_BACKEND", "nccl") != "gloo":
         def step_fn16(a, out_local):
             env.step_device(a.data_ptr(), out_local.data_ptr(), stream=stream, packed="bf16")
         st16 = ShardedStepper(N, env.packed_row_words("bf16"), step_fn16, dev, world=world, rank=rank, overlap=not args.no_overlap,
@@ -886,14 +956,14 @@ def main():
     n_timed = min(max(args.steps, 256), 1024)
     kernel_us_iso = None
     short_regions = args.steps < 100   # (a region of a few launches is dominated by its first launch after an idle gap)
-    if use_dist or args.isolated_kernel_timing or short_regions:
+    if args.isolated_kernel_timing or (args.full and (use_dist or short_regions)):
         kernel_us_iso = 0.0
         for i in range(n_timed):
             kernel_us_iso += env.time_steps_device(actions[i % RING].data_ptr(), out_l.data_ptr(), steps=1, stream=stream, packed=pack_mode)
         kernel_us_iso /= n_timed
         torch.cuda.synchronize()
-    if use_dist or short_regions:
-        kernel_us = kernel_us_iso
+    if use_dist or (args.full and short_regions):
+        kernel_us = kernel_us_iso   # (N > 1 without --full or --isolated-kernel-timing: None, the line has no roofline)
         n_timed = (f"hipExtLaunchKernel start/stop events on {n_timed} single dispatches of the step kernel ("
                    + ("the regions of an N > 1 run contain the gather" if use_dist else f"--steps {args.steps}: regions too short to average over") + ")")
     else:
@@ -907,12 +977,13 @@ def main():
     else:
         finite = bool(torch.isfinite(last).all().item())
         n_done = int((out_l[:, n_obs + 1] > 0.5).sum().item())
-    closed = closed_loop_rate(env, torch, dev, N, n_obs, n_u, 400) if world == 1 and not use_dist and not args.no_closed_loop else None
+    single = args.full and world == 1 and not use_dist   # the --full sub-measurements of the single-GPU line
+    closed = closed_loop_rate(env, torch, dev, N, n_obs, n_u, 400) if single and not args.no_closed_loop else None
     resident = (resident_sequence_rate(env, run, args, torch, config_id, N, kernel_us)
-                if world == 1 and not use_dist and not args.no_resident and args.steps >= 2 else None)
+                if single and not args.no_resident and args.steps >= 2 else None)
 
     sweep = []
-    if world == 1 and not args.no_sweep and not args.envs:
+    if args.full and world == 1 and not args.no_sweep and not args.envs:
         # the same kernel at batch sizes where the state no longer fits the caches (HBM-relevant roofline points)
         for n_big in args.sweep:
             sweep.append(sweep_point(wl, config_id, n_big, N, args, torch, dev, local_rank, stream, gen))
@@ -962,8 +1033,8 @@ def main():
             "data": "synthetic",
             "config": {"workload": wl["name"], "envs_per_gpu": N, "total_envs": world * N, "n_obs": n_obs, "n_u": n_u,
                        "auto_reset": "in-kernel scenario generation (Philox4x32-10)",
-                       "timing": f"median of {len(times)} regions of {args.steps} steps (>= {args.min_seconds} s measured in all), "
-                                 "each between barrier + synchronize, max over ranks; open loop: actions from a ring resident in HBM",
+                       "timing": f"one region of {args.steps} steps after {args.warmup} warm-up steps, between barrier + synchronize, "
+                                 "max over ranks; open loop: actions from a ring resident in HBM",
                        "collective": collective,
                        "gather_dtype": ("bf16" if pack_mode == "bf16" else "f32") if use_dist else None,
                        "gather_bytes_per_rank_per_step": (stepper.bytes_per_rank_per_step if hasattr(stepper, "bytes_per_rank_per_step")
@@ -973,8 +1044,11 @@ def main():
                        **({"rccl_all_gather_ms_per_step_python_issued": rccl_ms} if rccl_ms is not None else {}),
                        "obs_finite": finite, "done_last_step_rank0": n_done,
                        "kernel_source_sha": ksha},
-            "roofline": roofline_of(config_id, N, kernel_us, n_timed, ksha),
         }
+        if kernel_us is not None:
+            out["roofline"] = roofline_of(config_id, N, kernel_us, n_timed, ksha)
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if kernel_us_iso is not None and not use_dist:
             out["kernel_us_isolated_launches"] = kernel_us_iso
         if closed:
@@ -999,7 +1073,7 @@ def main():
                    if bf16_gather else {})}
         if sweep:
             out["sweep"] = sweep
-        if world == 1 and not use_dist and not args.no_configs and not args.envs:
+        if single and not args.no_configs and not args.envs:
             subs = []
             for cid in (2, 3, 4, 5):
                 if cid == config_id:
@@ -1020,7 +1094,7 @@ def main():
                     if cid != config_id and "ray-dense" not in sub["workload"] and sub.get("layout") != "vehicle_sorted":
                         sub["cpu_baseline"] = cpu_baseline(workload(cid, 2), max(2.0, args.cpu_seconds / 4))
             out["configs"] = subs
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(wl, args.cpu_seconds)
             allv, procs = cpu_baseline_all_cores(config_id, args.cpu_seconds)
             out["cpu_baseline"]["all_cores_value"] = allv        # one oracle process per CPU of this host

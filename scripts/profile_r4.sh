@@ -62,7 +62,7 @@ prof config5_524k --config 5 --envs 524288 --steps 200 --warmup 20
 # 64 steps) next to the bench line's own per-step figure
 for c in 2 3 4 5; do
   OUT=$ROOT/resident_config$c; mkdir -p $OUT
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --config $c --no-cpu --no-sweep --no-configs --no-closed-loop --steps 1024 --warmup 128 --min-seconds 0.05 > $OUT/bench_line.json 2> $OUT/bench_trace.err || tail -5 $OUT/bench_trace.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --config $c --full --no-cpu --no-sweep --no-configs --no-closed-loop --steps 1024 --warmup 128 --min-seconds 0.05 > $OUT/bench_line.json 2> $OUT/bench_trace.err || tail -5 $OUT/bench_trace.err
   find $OUT/trace -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/kernel_stats.csv
   rm -rf $OUT/trace
   python3 - $OUT <<'PY'

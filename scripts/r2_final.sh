@@ -13,7 +13,7 @@ for c in "2 4096" "3 65536" "4 32768"; do set -- $c
   DOCKAUV_LIB=$GRAFT_REPO_ROOT/gym_dockauv_amd/lib/libdockauv_stamps.so timeout -k 10 120 python scripts/stamps.py --config $1 --envs $2 2>&1 | grep -v "amdgpu.ids\|RuntimeWarning\|nanmedian" >> $O/stamps.txt
 done
 timeout -k 10 300 python scripts/active_fraction.py 2>&1 | grep -v amdgpu.ids > $O/active_fraction.txt
-timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "== bench rc=$?"; tail -2 $O/bench_default.err
+timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "== bench rc=$?"; tail -2 $O/bench_default.err
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r2_final/bench_default.json").read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # the default bench line (no sweep unless SWEEP=1) + a table of its sub-results -> gpurun_out/r3/bench_line.json
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/r3
-EXTRA="--no-sweep"; [ "$SWEEP" = "1" ] && EXTRA=""
+EXTRA="--full --no-sweep"; [ "$SWEEP" = "1" ] && EXTRA="--full"
 timeout -k 10 900 python bench.py $EXTRA --cpu-seconds ${CPU_SECONDS:-4} "$@" > gpurun_out/r3/bench_line.json 2> gpurun_out/r3/bench_err.txt || { tail -20 gpurun_out/r3/bench_err.txt; exit 1; }
 python - <<'PY'
 import json

@@ -7,7 +7,7 @@ TAG=${TAG:-ab}
 REPS=${REPS:-2}
 for rep in $(seq $REPS); do
 for lib in libdockauv.so "$@"; do
-  DOCKAUV_LIB=$GRAFT_REPO_ROOT/gym_dockauv_amd/lib/$lib timeout -k 10 300 python bench.py --no-sweep --no-cpu --no-closed-loop --steps 1000 --warmup 500 --min-seconds 0.1 $BENCH_ARGS 2>/dev/null | python -c "
+  DOCKAUV_LIB=$PWD/gym_dockauv_amd/lib/$lib timeout -k 10 300 python bench.py --full --no-sweep --no-cpu --no-closed-loop --steps 1000 --warmup 500 --min-seconds 0.1 $BENCH_ARGS 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 def nm(s): return s['workload'][:7] + ('-dense' if 'ray-dense' in s['workload'] else ('-sorted' if s.get('layout') == 'vehicle_sorted' else ''))

@@ -1,6 +1,7 @@
 """bench.py's contract with the driver: the workloads are BASELINE.json's configs, the algorithmic bytes per env-step are
 SURVEY.md section 8d's formula, and (on a GPU) the default invocation prints ONE JSON line with the fields the round
-prompt names."""
+prompt names; a plain run measures the headline alone, --full adds the rest; --dump-outputs writes the last step's
+outputs."""
 import json
 import os
 import subprocess
@@ -108,6 +109,41 @@ def test_launcher_relays_exactly_the_json_line():
     assert json.loads(line) == {"b": 2} and others == ['{"a": 1}', "noise"]
 
 
+def test_help_lists_full_and_dump_outputs():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
+def test_write_outputs_small_arrays_whole(tmp_path):
+    rng = np.random.default_rng(3)
+    arrays = {"obs": rng.random((100, 20)), "reward": rng.random(100).astype(np.float32), "done": np.zeros(100, dtype=bool)}
+    shapes = bench.write_outputs(str(tmp_path), arrays)
+    assert shapes == {"obs": [100, 20], "reward": [100], "done": [100]}
+    obs, rew, done = (np.load(tmp_path / f"{k}.npy") for k in ("obs", "reward", "done"))
+    assert obs.dtype == np.float64 and rew.dtype == np.float32 and done.dtype == np.float32
+    assert np.array_equal(obs, arrays["obs"]) and np.array_equal(rew, arrays["reward"]) and not done.any()
+    assert not (tmp_path / "sample_rows.npy").exists()
+
+
+def test_write_outputs_samples_large_arrays_the_same_way_every_time(tmp_path):
+    n = 5000
+    obs = np.arange(n * 22, dtype=np.float32).reshape(n, 22)
+    rew = np.arange(n, dtype=np.float32)
+    limit = 40000
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), {"obs": obs, "reward": rew}, limit=limit)
+    total = 0
+    for k in ("obs", "reward", "sample_rows"):
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= limit
+    rows = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert rows.dtype == np.float64 and len(rows) > 0 and np.all(np.diff(rows) > 0)
+    idx = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "obs.npy"), obs[idx]) and np.array_equal(np.load(tmp_path / "a" / "reward.npy"), rew[idx])
+
+
 def test_world_size_must_match_gpus():
     env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0", HIP_VISIBLE_DEVICES="")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4"], capture_output=True, text=True,
@@ -118,7 +154,7 @@ def test_world_size_must_match_gpus():
 @pytest.mark.gpu
 def test_default_line_has_the_contract_fields():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "200", "--warmup", "50", "--min-seconds", "0.05",
-                          "--no-sweep", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--no-sweep", "--cpu-seconds", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -153,3 +189,34 @@ def test_default_line_has_the_contract_fields():
     for s in subs.values():
         assert s["kernel_us"] > 0 and 0 < s["roofline"]["frac"] < 1 and "traffic" in s["roofline"]
     assert subs["config2"]["envs"] == 4096 and subs["config4"]["envs"] == 32768 and subs["config5"]["envs"] == 65536
+
+
+def _plain_run(out_dir, *extra):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "10",
+                          "--dump-outputs", str(out_dir), *extra], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_line_times_exactly_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run: one region of exactly --steps steps, the headline fields, none of --full's sub-measurements; the last
+    step's obs / reward / done written as float32 arrays, the same ones in a second run with the same arguments."""
+    d = _plain_run(tmp_path / "a", "--config", "2")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 30 and d["warmup"] == 10 and d["reps"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert np.isclose(d["value"], 4096 / (d["ms_per_step"] * 1e-3), rtol=1e-9)
+    for k in ("configs", "cpu_baseline", "sweep", "closed_loop", "sequence_resident"):
+        assert k not in d, k
+    n_obs = d["config"]["n_obs"]
+    obs, rew, done = (np.load(tmp_path / "a" / f"{k}.npy") for k in ("obs", "reward", "done"))
+    assert obs.shape == (4096, n_obs) and rew.shape == (4096,) and done.shape == (4096,)
+    assert obs.dtype == rew.dtype == done.dtype == np.float32 and np.isfinite(obs).all() and np.isfinite(rew).all()
+    assert set(np.unique(done)) <= {0.0, 1.0} and int(done.sum()) == d["config"]["done_last_step_rank0"]
+    assert d["dumped_outputs"] == {"obs": [4096, n_obs], "reward": [4096], "done": [4096]}
+    _plain_run(tmp_path / "b", "--config", "2")
+    for k in ("obs", "reward", "done"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")), k

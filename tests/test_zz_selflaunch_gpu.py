@@ -4,7 +4,7 @@ The driver starts the scaling runs as `python bench.py --gpus N`; the launcher h
 (tests/test_bench_contract.py).  Here both self-launched rank processes get as far as the JSON line: they share the box's
 one GPU (DOCKAUV_RANKS_SHARE_GPU=1) and use gloo for the all-gather, because RCCL refuses two ranks on one device -- everything
 else (sharding, packed rows written into the rank's slice of the gather buffer, the overlapped gather, max over ranks, the
-sub-measurements of the N > 1 line) is the code the N-GPU run executes."""
+sub-measurements that --full adds to the N > 1 line) is the code the N-GPU run executes."""
 import json
 import os
 import subprocess
@@ -20,7 +20,7 @@ def test_two_self_launched_ranks_print_one_line():
     env = dict(os.environ, DOCKAUV_RANKS_SHARE_GPU="1", DOCKAUV_DIST_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = out.stdout.strip().splitlines()
