@@ -93,6 +93,22 @@ class P2PPlan(C.Structure):
     ]
 
 
+ACT_NONE, ACT_TANH, ACT_RELU = 0, 1, 2
+POLICY_MAX_WIDTH = 128
+
+
+class PolicyDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("precision", C.c_int32),
+        ("n_in", C.c_int32), ("n_hidden", C.c_int32 * 2), ("n_out", C.c_int32),
+        ("hidden_act", C.c_int32), ("out_act", C.c_int32),
+        ("pointers_on_device", C.c_int32), ("reserved", C.c_int32),
+        ("W1", C.c_void_p), ("b1", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p), ("W3", C.c_void_p), ("b3", C.c_void_p),
+        ("log_std", C.c_void_p),
+        ("seed", C.c_uint64), ("env_id_offset", C.c_uint64),
+    ]
+
+
 # every symbol include/dockauv.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("dockauv_abi_version", C.c_int, []),
@@ -128,6 +144,12 @@ SYMBOLS = [
     ("dockauv_p2p_gather", C.c_int, [C.POINTER(P2PPlan), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     ("dockauv_step_gather_sequence", C.c_int, [C.c_void_p, C.POINTER(StepIO), C.c_int, C.POINTER(P2PPlan), C.c_int,
                                                C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
+    ("dockauv_policy_create", C.c_int, [C.c_void_p, C.POINTER(PolicyDesc), C.POINTER(C.c_void_p)]),
+    ("dockauv_policy_load", C.c_int, [C.c_void_p, C.POINTER(PolicyDesc), C.c_void_p]),
+    ("dockauv_policy_destroy", C.c_int, [C.c_void_p]),
+    ("dockauv_policy_forward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]),
+    ("dockauv_rollout", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                  C.c_uint64, C.c_int, C.c_void_p]),
 ]
 
 _lib: Optional[C.CDLL] = None

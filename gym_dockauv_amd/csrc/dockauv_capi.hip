@@ -1167,6 +1167,186 @@ int dockauv_time_steps(dockauv_handle h, const dockauv_step_io* io, void* hip_st
     return check_status(h);
 }
 
+// ------------------------------------------------------------------------------------------ policy + closed-loop rollout
+}  // extern "C"
+
+struct dockauv_policy_s {
+    dockauv_handle h = nullptr;
+    PolicyShape S{};
+    float* packed = nullptr;      // the weights as the kernel reads them (dockauv_device.h: PolicyShape)
+    float* raw = nullptr;         // device staging of host arrays: W1 b1 W2 b2 W3 b3 log_std back to back
+    bool has_log_std = false;
+    uint64_t seed = 0, env_id_offset = 0;
+};
+
+namespace {
+
+// the descriptor's own fields; `like` != nullptr: a reload, shapes and activations must be those of the policy
+int validate_policy_desc(dockauv_handle h, const dockauv_policy_desc* d, const PolicyShape* like) {
+    if (d->struct_size != sizeof(dockauv_policy_desc))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.struct_size: got %u, library has %zu", d->struct_size, sizeof(dockauv_policy_desc));
+    if (d->precision != DOCKAUV_F32) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.precision: %d, only DOCKAUV_F32 is implemented", d->precision);
+    if (d->n_in < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_in: %d must be >= 1", d->n_in);
+    if (d->n_hidden[0] < 1 || d->n_hidden[0] > DOCKAUV_POLICY_MAX_WIDTH)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_hidden[0]: %d outside 1..%d", d->n_hidden[0], DOCKAUV_POLICY_MAX_WIDTH);
+    if (d->n_hidden[1] < 0 || d->n_hidden[1] > DOCKAUV_POLICY_MAX_WIDTH)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_hidden[1]: %d outside 0..%d (0 = one hidden layer)", d->n_hidden[1], DOCKAUV_POLICY_MAX_WIDTH);
+    if (d->n_out < 1 || d->n_out > DOCKAUV_MAX_U) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_out: %d outside 1..%d", d->n_out, DOCKAUV_MAX_U);
+    if (d->hidden_act != DOCKAUV_ACT_TANH && d->hidden_act != DOCKAUV_ACT_RELU)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.hidden_act: %d is neither DOCKAUV_ACT_TANH nor DOCKAUV_ACT_RELU", d->hidden_act);
+    if (d->out_act != DOCKAUV_ACT_NONE && d->out_act != DOCKAUV_ACT_TANH)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.out_act: %d is neither DOCKAUV_ACT_NONE nor DOCKAUV_ACT_TANH", d->out_act);
+    if (d->pointers_on_device != 0 && d->pointers_on_device != 1)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.pointers_on_device: %d must be 0 or 1", d->pointers_on_device);
+    if (!d->W1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.W1 is NULL");
+    if (!d->b1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.b1 is NULL");
+    if (d->n_hidden[1] > 0 && !d->W2) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.W2 is NULL (n_hidden[1] > 0)");
+    if (d->n_hidden[1] > 0 && !d->b2) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.b2 is NULL (n_hidden[1] > 0)");
+    if (!d->W3) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.W3 is NULL");
+    if (!d->b3) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.b3 is NULL");
+    if (like && (d->n_in != like->n_in || d->n_hidden[0] != like->n_h1 || d->n_hidden[1] != like->n_h2 || d->n_out != like->n_out ||
+                 d->hidden_act != like->hidden_act || d->out_act != like->out_act))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_load: n_in / n_hidden / n_out / activations differ from the policy's (%d-%d-%d-%d)",
+                    like->n_in, like->n_h1, like->n_h2, like->n_out);
+    return 0;
+}
+
+// weights of `d` -> p->packed, ordered on `stream`; host arrays go through p->raw and the call waits for the copies
+int upload_policy(dockauv_policy p, const dockauv_policy_desc* d, hipStream_t stream) {
+    dockauv_handle h = p->h;
+    const PolicyShape& S = p->S;
+    const int n_last = S.n_h2 ? S.n_h2 : S.n_h1;
+    const float* src[7] = {d->W1, d->b1, d->W2, d->b2, d->W3, d->b3, d->log_std};
+    const size_t cnt[7] = {(size_t)S.n_h1 * S.n_in, (size_t)S.n_h1, (size_t)S.n_h2 * S.n_h1, (size_t)S.n_h2,
+                           (size_t)S.n_out * n_last, (size_t)S.n_out, (size_t)S.n_out};
+    const float* dev[7];
+    if (d->pointers_on_device) {
+        for (int i = 0; i < 7; ++i) dev[i] = src[i];
+    } else {
+        size_t off = 0;
+        for (int i = 0; i < 7; ++i) {
+            dev[i] = (src[i] && cnt[i]) ? p->raw + off : nullptr;
+            if (dev[i]) HIP_TRY(h, hipMemcpyAsync(p->raw + off, src[i], cnt[i] * sizeof(float), hipMemcpyHostToDevice, stream));
+            off += cnt[i];
+        }
+        HIP_TRY(h, hipStreamSynchronize(stream));   // the caller's host arrays are free on return
+    }
+    if (!S.n_h2) dev[2] = dev[3] = nullptr;
+    const PolicyRaw raw{dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6]};
+    const int rc = launch_policy_pack(S, raw, p->packed, stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "policy weight packing launch failed: %s", hipGetErrorString((hipError_t)rc));
+    p->has_log_std = d->log_std != nullptr;
+    p->seed = d->seed;
+    p->env_id_offset = d->env_id_offset;
+    return 0;
+}
+
+int policy_forward(dockauv_handle h, dockauv_policy p, const float* rows, float* actions, uint64_t t, int stochastic, hipStream_t stream) {
+    const int rc = launch_policy_forward(p->S, p->packed, rows, actions, h->cfg.n_envs, h->n_obs + 2, h->n_u_max, t,
+                                         (stochastic && p->has_log_std) ? 1 : 0, p->seed, p->env_id_offset, stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "policy kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = stream;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dockauv_policy_create(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out) {
+    if (!d || !out) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_create: null argument");
+    *out = nullptr;
+    int rc = validate_policy_desc(h, d, nullptr);
+    if (rc) return rc;
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_create: null handle");
+    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_create: the policy kernel is float32; the handle's precision is DOCKAUV_F64");
+    if (d->n_in != h->n_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_in: %d, the handle's n_obs is %d", d->n_in, h->n_obs);
+    if (d->n_out != h->n_u_max) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_out: %d, the handle's n_u is %d", d->n_out, h->n_u_max);
+    PolicyShape S{};
+    S.n_in = d->n_in;
+    S.n_h1 = d->n_hidden[0];
+    S.n_h2 = d->n_hidden[1];
+    S.n_out = d->n_out;
+    S.hidden_act = d->hidden_act;
+    S.out_act = d->out_act;
+    policy_layout(S);
+    if (policy_lds_bytes(S) > kPolMaxLds)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc: the padded weights (%zu B for n_in %d, n_hidden %d / %d) exceed "
+                    "the 160 KiB of LDS the policy kernel keeps them in: narrower layers", policy_lds_bytes(S), S.n_in, S.n_h1, S.n_h2);
+    HIP_TRY(h, hipSetDevice(h->device));
+    dockauv_policy p = new dockauv_policy_s();
+    p->h = h;
+    p->S = S;
+    const int n_last = S.n_h2 ? S.n_h2 : S.n_h1;
+    const size_t raw_floats = (size_t)S.n_h1 * S.n_in + S.n_h1 + (size_t)S.n_h2 * S.n_h1 + S.n_h2 + (size_t)S.n_out * n_last + 2 * (size_t)S.n_out;
+    hipError_t e = hipMalloc((void**)&p->packed, (size_t)S.total * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->raw, raw_floats * sizeof(float));
+    if (e != hipSuccess) {
+        dockauv_policy_destroy(p);
+        return fail(h, DOCKAUV_E_HIP, "policy buffers: %s", hipGetErrorString(e));
+    }
+    if ((rc = upload_policy(p, d, nullptr)) != 0) {
+        dockauv_policy_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return 0;
+}
+
+int dockauv_policy_load(dockauv_policy p, const dockauv_policy_desc* d, void* hip_stream) {
+    if (!p) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_load: null policy");
+    if (!d) return fail(p->h, DOCKAUV_E_INVALID, "dockauv_policy_load: null descriptor");
+    int rc = validate_policy_desc(p->h, d, &p->S);
+    if (rc) return rc;
+    HIP_TRY(p->h, hipSetDevice(p->h->device));
+    return upload_policy(p, d, (hipStream_t)hip_stream);
+}
+
+int dockauv_policy_destroy(dockauv_policy p) {
+    if (!p) return 0;
+    if (p->h) (void)hipSetDevice(p->h->device);
+    (void)hipDeviceSynchronize();
+    if (p->packed) (void)hipFree(p->packed);
+    if (p->raw) (void)hipFree(p->raw);
+    delete p;
+    return 0;
+}
+
+int dockauv_policy_forward(dockauv_handle h, dockauv_policy p, const float* rows, float* actions, uint64_t t, int stochastic,
+                           void* hip_stream) {
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_forward: null handle");
+    if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward: null policy");
+    if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward: the policy was created for another handle");
+    if (!rows || !actions) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward: rows/actions must not be NULL");
+    HIP_TRY(h, hipSetDevice(h->device));
+    return policy_forward(h, p, rows, actions, t, stochastic, (hipStream_t)hip_stream);
+}
+
+int dockauv_rollout(dockauv_handle h, dockauv_policy p, const float* rows_in, float* rows_out, float* actions_out,
+                    float* terminal_obs, int n_steps, uint64_t t0, int stochastic, void* hip_stream) {
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_rollout: null handle");
+    if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: null policy");
+    if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: the policy was created for another handle");
+    if (n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: n_steps %d must be >= 1", n_steps);
+    if (!rows_in || !rows_out || !actions_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: rows_in/rows_out/actions_out must not be NULL");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const size_t N = (size_t)h->cfg.n_envs, row = (size_t)h->n_obs + 2;
+    for (int k = 0; k < n_steps; ++k) {
+        const float* rows = k == 0 ? rows_in : rows_out + (size_t)(k - 1) * N * row;
+        float* act = actions_out + (size_t)k * N * h->n_u_max;
+        int rc = policy_forward(h, p, rows, act, t0 + (uint64_t)k, stochastic, stream);
+        if (rc) return rc;
+        dockauv_step_io io{};
+        io.actions = act;
+        io.obs = rows_out + (size_t)k * N * row;
+        io.terminal_obs = terminal_obs ? terminal_obs + (size_t)k * N * h->n_obs : nullptr;
+        io.pack_reward_done = 1;
+        if ((rc = launch(h, &io, stream)) != 0) return rc;
+    }
+    return check_status(h);   // (what dockauv_poll_status looks at: no synchronisation)
+}
+
 #ifdef DOCKAUV_STAMPS
 // diagnostic build only (scripts/stamps.py): 64 groups x 32 s_memtime stamps of the last f32 step
 int dockauv_debug_read_stamps(unsigned long long* out) {

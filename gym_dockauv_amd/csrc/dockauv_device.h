@@ -236,6 +236,74 @@ int launch_step_f64(const KernelArgs<double, 2>& a, int vk, bool sym, bool has_r
 // one by one.  a.io: everything but actions / obs, which come from `seq`.
 int launch_sequence_f32(const KernelArgs<float, 2>& a, int vk, bool sym, bool has_rays, int threads, const SeqArgs& seq, void* stream);
 
+#ifdef __HIPCC__
+// Philox4x32-10 (Salmon et al., SC'11): counter-based, integer only -> bit-exact against the NumPy restatement in
+// oracle/philox_ref.py.  Counter slot 3 names the stream: 0 = episode generator, 1 = current noise (dockauv_step.hip.inc),
+// 2 = policy exploration noise (dockauv_policy.hip).
+__device__ __forceinline__ void philox4x32_10_(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];   // one v_mad_u64_u32 each
+        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
+        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
+        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+#endif
+
+// ------------------------------------------------------------------------------------------ MLP policy (dockauv_policy.hip)
+// a = out_act(W3 act(W2 act(W1 obs + b1) + b2) + b3) on the packed rows of the step kernel, one or two hidden layers.
+// The kernel works on 32-unit x 32-env tiles of v_mfma_f32_32x32x2_f32 with the units on the M side: the weights are kept
+// in device memory in the order the A operand wants them ("packed", written by policy_pack_kernel from the caller's
+// row-major arrays), zero-padded to whole tiles.  Offsets in floats into that buffer:
+//   W1: [ks1][mt1][64]       lane l of k step s, tile m: W1[32 m + (l & 31)][2 s + (l >> 5)]
+//   W2: [16 mt1][mt2][64]    lane l of k step (m1, r), tile m2: W2[32 m2 + (l & 31)][k], k = 32 m1 + (r & 3) + 8 (r >> 2) +
+//                            4 (l >> 5): the unit that accumulator register r of tile m1 holds in that lane half, so that the
+//                            activations of one layer are the B operand of the next as they stand
+//   W3: [16 mtl][1][64]      the same over the last hidden layer (mtl tiles), units = actions
+//   b1 / b2 / b3: [tiles][16][2]  the bias of the unit of (register r, lane half)
+//   std: [8]                 exp(log_std[j]) (0 without log_std)
+constexpr int kPolMaxWidth = 128;
+constexpr int kPolThreads = 256;          // four waves, each one tile of 32 envs
+constexpr size_t kPolMaxLds = 160 * 1024;
+struct PolicyShape {
+    int n_in, n_h1, n_h2, n_out;          // n_h2 == 0: one hidden layer
+    int hidden_act, out_act;              // DOCKAUV_ACT_*
+    int mt1, mt2, ks1;
+    int off_w1, off_w2, off_w3, off_b1, off_b2, off_b3, off_std, total;   // total: multiple of 4
+};
+inline void policy_layout(PolicyShape& s) {
+    s.mt1 = (s.n_h1 + 31) / 32;
+    s.mt2 = (s.n_h2 + 31) / 32;
+    s.ks1 = (s.n_in + 1) / 2;
+    const int mtl = s.mt2 ? s.mt2 : s.mt1;
+    int o = 0;
+    s.off_w1 = o; o += s.ks1 * s.mt1 * 64;
+    s.off_w2 = o; o += 16 * s.mt1 * s.mt2 * 64;
+    s.off_w3 = o; o += 16 * mtl * 64;
+    s.off_b1 = o; o += s.mt1 * 32;
+    s.off_b2 = o; o += s.mt2 * 32;
+    s.off_b3 = o; o += 32;
+    s.off_std = o; o += 8;
+    s.total = o;
+}
+// LDS of one group: the packed weights (what the launch requests and what create checks against kPolMaxLds)
+inline size_t policy_lds_bytes(const PolicyShape& s) { return (size_t)s.total * sizeof(float); }
+struct PolicyRaw {   // the caller's arrays, device pointers (row-major [out][in] = torch.nn.Linear.weight)
+    const float *W1, *b1, *W2, *b2, *W3, *b3, *log_std;
+};
+// packed[0 .. s.total) from raw, on stream.  Returns a hipError_t as int.
+int launch_policy_pack(const PolicyShape& s, const PolicyRaw& raw, float* packed, void* stream);
+// actions[i][0 .. n_out) of env rows i < n (rows: [n][row_stride], only the first n_in columns are read; actions:
+// [n][act_stride]); stochastic != 0 adds std[j] * N(0, 1) of Philox counter (env_id_offset + i, t, j, 2), key = seed,
+// before the output activation.  Returns a hipError_t as int.
+int launch_policy_forward(const PolicyShape& s, const float* packed, const float* rows, float* actions, int n, int row_stride,
+                          int act_stride, unsigned long long t, int stochastic, unsigned long long seed,
+                          unsigned long long env_id_offset, void* stream);
+
 #ifdef DOCKAUV_STAMPS
 int read_stamps(unsigned long long* out);   // diagnostic build only
 int read_span(unsigned long long* out, int groups);

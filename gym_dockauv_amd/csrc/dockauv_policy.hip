@@ -1,0 +1,266 @@
+// dockauv_policy.hip -- the library's own MLP actor for gfx950 (MI355X): the policy of a closed loop evaluated on the packed
+// rows the step kernel writes (include/dockauv.h: dockauv_policy_*, dockauv_rollout; the reference's counterpart is SB3's
+// MlpPolicy, train.py:64, queried per step in train.py:64-71, 86-119).
+//
+// One launch = a[i] = out_act(W3 act(W2 act(W1 obs[i] + b1) + b2) + b3) for every env row i, exact float32.
+//
+// Work decomposition: the TRANSPOSED product on v_mfma_f32_32x32x2_f32 -- units on the M side, envs on the N side.  A wave
+// owns 32 consecutive envs (column = lane & 31) and walks them through all layers; a workgroup is four such waves and stages
+// the packed weights (dockauv_device.h: PolicyShape) into LDS once.
+//   * layer 1: the B operand of k step s is obs[env][2 s + (lane >> 5)], read straight from the row (only columns < n_in
+//     are ever touched: the reward / done columns never enter a product, and rows >= n are never read); the A operand is
+//     one LDS word per lane;
+//   * the C/D layout of the instruction holds unit 32 m + (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of the wave's env column in
+//     register r of tile m: after the activation that register IS the B operand of one k step of the next layer, whose
+//     weight columns were permuted to match when they were packed -- no transpose, no LDS traffic for activations;
+//   * every pre-activation is one accumulator chain that starts from the bias and takes its k steps in an order fixed by
+//     the shape alone: an env's action depends on its row and the weights, not on n, its position or the grid;
+//   * the actions (<= 8) of an env sit in registers 0..3 of the two lane halves; exploration noise, output activation and
+//     the store happen there.
+// Instantiated per (tiles of hidden layer 1, tiles of hidden layer 2) so that every accumulator index is a constant.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/dockauv.h"
+#include "dockauv_device.h"
+
+namespace dockauv {
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct PolicyArgs {
+    PolicyShape S;
+    const float* packed;
+    const float* rows;
+    float* actions;
+    int n, row_stride, act_stride, stochastic;
+    unsigned int t_lo;                 // t mod 2^32
+    unsigned int env_off_lo;           // env_id_offset mod 2^32 (the counter word is 32 bits wide)
+    unsigned long long seed;
+};
+
+// tanh(x) = 1 - 2 / (exp(2 x) + 1): v_exp_f32 and v_rcp_f32 are good to 1 ulp, the form has no cancellation beyond the final
+// subtraction, so the absolute error stays below ~3e-7 everywhere (+-1 at the ends, exactly 0 at 0: padded units stay 0).
+__device__ __forceinline__ float tanh_(float x) {
+    const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);   // exp(2 x)
+    return fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
+}
+
+__device__ __forceinline__ float act_(float x, int kind) {
+    if (kind == DOCKAUV_ACT_TANH) return tanh_(x);
+    if (kind == DOCKAUV_ACT_RELU) return fmaxf(x, 0.0f);
+    return x;
+}
+
+// standard normal of Philox counter (env, t, j, 2): Box-Muller cos branch on the first two words, u1 / u2 as the current
+// noise of the step kernel draws them (oracle/philox_ref.py: philox_normal).  u1 is formed in float32: the + 0.5 is held while
+// c[0] >> 8 < 2^23 and rounded to even above, so u1 lies in (0, 1] -- the log is finite, and the top value gives z = 0.
+__device__ __forceinline__ float policy_normal_(unsigned long long seed, uint32_t env, uint32_t t, uint32_t j) {
+    uint32_t c[4] = {env, t, j, 2u};
+    philox4x32_10_(c, (uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32));
+    const float u1 = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float u2 = (float)(c[1] >> 8) * (1.0f / 16777216.0f);
+    return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);                   // cos(2 pi u2), argument reduction exact
+}
+
+template <int MT>
+__device__ __forceinline__ void load_bias_(f32x16 (&acc)[MT], const float* lds_b, int half) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[m][r] = lds_b[(m * 16 + r) * 2 + half];
+}
+
+template <int MT>
+__device__ __forceinline__ void activate_(f32x16 (&acc)[MT], int kind) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[m][r] = act_(acc[m][r], kind);
+}
+
+// out[mo] += W[.. , k] h[k] over the units the accumulators `in` hold: k step (mi, r) takes register r of tile mi as it stands
+template <int MI, int MO>
+__device__ __forceinline__ void dense_(f32x16 (&out)[MO], const f32x16 (&in)[MI], const float* lds_w, int lane) {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+#pragma unroll
+            for (int mo = 0; mo < MO; ++mo)
+                out[mo] = __builtin_amdgcn_mfma_f32_32x32x2f32(lds_w[((mi * 16 + r) * MO + mo) * 64 + lane], in[mi][r], out[mo], 0, 0, 0);
+}
+
+constexpr int kChunk = 16;   // layer-1 k steps whose row words are requested together
+
+template <int MT1, int MT2>
+__global__ __launch_bounds__(kPolThreads) void policy_mlp_kernel(const PolicyArgs a) {
+    extern __shared__ float lds[];
+    const PolicyShape& S = a.S;
+    {
+        const float4* src = reinterpret_cast<const float4*>(a.packed);
+        float4* dst = reinterpret_cast<float4*>(lds);
+        for (int i = threadIdx.x; i < S.total / 4; i += kPolThreads) dst[i] = src[i];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, half = lane >> 5;
+    const long tile = (long)blockIdx.x * (kPolThreads / 64) + (threadIdx.x >> 6);
+    if (tile * 32 >= a.n) return;                       // (no barrier below)
+    const long env = tile * 32 + (lane & 31);
+    const bool live = env < a.n;                        // tail: rows >= n are neither read nor written
+    const float* row = a.rows + (live ? env : 0) * (long)a.row_stride;
+
+    // ---- layer 1
+    f32x16 h1[MT1];
+    load_bias_<MT1>(h1, lds + S.off_b1, half);
+    for (int s0 = 0; s0 < S.ks1; s0 += kChunk) {
+        float x[kChunk];
+#pragma unroll
+        for (int j = 0; j < kChunk; ++j) {
+            const int k = 2 * (s0 + j) + half;
+            x[j] = (live && k < S.n_in) ? row[k] : 0.0f;
+        }
+#pragma unroll
+        for (int j = 0; j < kChunk; ++j) {
+            if (s0 + j < S.ks1) {
+#pragma unroll
+                for (int m = 0; m < MT1; ++m)
+                    h1[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(lds[S.off_w1 + ((s0 + j) * MT1 + m) * 64 + lane], x[j], h1[m], 0, 0, 0);
+            }
+        }
+    }
+    activate_<MT1>(h1, S.hidden_act);
+
+    // ---- hidden layer 2 (if any) and the output layer
+    f32x16 out[1];
+    load_bias_<1>(out, lds + S.off_b3, half);
+    if constexpr (MT2 > 0) {
+        f32x16 h2[MT2];
+        load_bias_<MT2>(h2, lds + S.off_b2, half);
+        dense_<MT1, MT2>(h2, h1, lds + S.off_w2, lane);
+        activate_<MT2>(h2, S.hidden_act);
+        dense_<MT2, 1>(out, h2, lds + S.off_w3, lane);
+    } else {
+        dense_<MT1, 1>(out, h1, lds + S.off_w3, lane);
+    }
+
+    // ---- actions: unit j = 4 half + r sits in register r < 4
+    float* dst = a.actions + (live ? env : 0) * (long)a.act_stride;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int j = 4 * half + r;
+        if (j < S.n_out) {
+            float v = out[0][r];
+            if (a.stochastic) v = fmaf(lds[S.off_std + j], policy_normal_(a.seed, a.env_off_lo + (uint32_t)env, a.t_lo, (uint32_t)j), v);
+            v = act_(v, S.out_act);
+            if (live) dst[j] = v;
+        }
+    }
+}
+
+struct PackArgs {
+    PolicyShape S;
+    PolicyRaw raw;
+    float* packed;
+};
+
+// unit of accumulator register r in lane half `half` of a tile (C/D layout of v_mfma_f32_32x32x2_f32)
+__device__ __forceinline__ int unit_of_(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
+__global__ void policy_pack_kernel(const PackArgs a) {
+    const PolicyShape& S = a.S;
+    const int n_last = S.n_h2 ? S.n_h2 : S.n_h1;
+    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < S.total; idx += gridDim.x * blockDim.x) {
+        float v = 0.0f;
+        if (idx < S.off_w2) {
+            const int loc = idx - S.off_w1, l = loc & 63, t = loc >> 6;
+            const int m = t % S.mt1, s = t / S.mt1;
+            const int unit = 32 * m + (l & 31), k = 2 * s + (l >> 5);
+            if (unit < S.n_h1 && k < S.n_in) v = a.raw.W1[(long)unit * S.n_in + k];
+        } else if (idx < S.off_w3) {
+            const int loc = idx - S.off_w2, l = loc & 63, t = loc >> 6;
+            const int m = t % S.mt2, sr = t / S.mt2;
+            const int unit = 32 * m + (l & 31), k = 32 * (sr >> 4) + unit_of_(sr & 15, l >> 5);
+            if (unit < S.n_h2 && k < S.n_h1) v = a.raw.W2[(long)unit * S.n_h1 + k];
+        } else if (idx < S.off_b1) {
+            const int loc = idx - S.off_w3, l = loc & 63, sr = loc >> 6;
+            const int unit = l & 31, k = 32 * (sr >> 4) + unit_of_(sr & 15, l >> 5);
+            if (unit < S.n_out && k < n_last) v = a.raw.W3[(long)unit * n_last + k];
+        } else if (idx < S.off_std) {
+            const float* b = idx < S.off_b2 ? a.raw.b1 : (idx < S.off_b3 ? a.raw.b2 : a.raw.b3);
+            const int n_units = idx < S.off_b2 ? S.n_h1 : (idx < S.off_b3 ? S.n_h2 : S.n_out);
+            const int loc = idx - (idx < S.off_b2 ? S.off_b1 : (idx < S.off_b3 ? S.off_b2 : S.off_b3));
+            const int unit = 32 * (loc >> 5) + unit_of_((loc >> 1) & 15, loc & 1);
+            if (unit < n_units) v = b[unit];
+        } else {
+            const int j = idx - S.off_std;
+            if (a.raw.log_std && j < S.n_out) v = expf(a.raw.log_std[j]);
+        }
+        a.packed[idx] = v;
+    }
+}
+
+template <int MT1, int MT2>
+int launch_forward_(const PolicyArgs& a, size_t lds, hipStream_t stream) {
+    if (lds > 64 * 1024) {
+        // more than 64 KiB of LDS per group must be requested explicitly; the attribute belongs to the (device, function)
+        // pair: set on the launch path, as the step kernels do
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&policy_mlp_kernel<MT1, MT2>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    const long tiles = ((long)a.n + 31) / 32;
+    const long groups = (tiles + kPolThreads / 64 - 1) / (kPolThreads / 64);
+    hipLaunchKernelGGL((policy_mlp_kernel<MT1, MT2>), dim3((unsigned)groups), dim3(kPolThreads), lds, stream, a);
+    return (int)hipGetLastError();
+}
+
+template <int MT1>
+int launch_forward_mt1_(const PolicyArgs& a, size_t lds, hipStream_t stream) {
+    switch (a.S.mt2) {
+        case 0: return launch_forward_<MT1, 0>(a, lds, stream);
+        case 1: return launch_forward_<MT1, 1>(a, lds, stream);
+        case 2: return launch_forward_<MT1, 2>(a, lds, stream);
+        case 3: return launch_forward_<MT1, 3>(a, lds, stream);
+        case 4: return launch_forward_<MT1, 4>(a, lds, stream);
+    }
+    return (int)hipErrorInvalidValue;
+}
+
+}  // namespace
+
+int launch_policy_pack(const PolicyShape& s, const PolicyRaw& raw, float* packed, void* stream) {
+    PackArgs a{s, raw, packed};
+    hipLaunchKernelGGL(policy_pack_kernel, dim3((unsigned)((s.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+int launch_policy_forward(const PolicyShape& s, const float* packed, const float* rows, float* actions, int n, int row_stride,
+                          int act_stride, unsigned long long t, int stochastic, unsigned long long seed,
+                          unsigned long long env_id_offset, void* stream) {
+    PolicyArgs a;
+    a.S = s;
+    a.packed = packed;
+    a.rows = rows;
+    a.actions = actions;
+    a.n = n;
+    a.row_stride = row_stride;
+    a.act_stride = act_stride;
+    a.stochastic = stochastic ? 1 : 0;
+    a.t_lo = (unsigned int)(t & 0xffffffffull);
+    a.env_off_lo = (unsigned int)(env_id_offset & 0xffffffffull);
+    a.seed = seed;
+    const size_t lds = policy_lds_bytes(s);
+    if (n <= 0 || lds > kPolMaxLds) return (int)hipErrorInvalidValue;
+    switch (s.mt1) {
+        case 1: return launch_forward_mt1_<1>(a, lds, (hipStream_t)stream);
+        case 2: return launch_forward_mt1_<2>(a, lds, (hipStream_t)stream);
+        case 3: return launch_forward_mt1_<3>(a, lds, (hipStream_t)stream);
+        case 4: return launch_forward_mt1_<4>(a, lds, (hipStream_t)stream);
+    }
+    return (int)hipErrorInvalidValue;
+}
+
+}  // namespace dockauv

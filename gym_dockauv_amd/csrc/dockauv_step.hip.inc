@@ -758,20 +758,8 @@ __device__ __forceinline__ bool sphere_may_be_hit_(T ocx, T d2, T dist, T rad, T
 }
 
 // ------------------------------------------------------------------------------------------ device-side reset
-// Philox4x32-10 (Salmon et al., SC'11): counter-based, integer only -> bit-exact against the NumPy restatement in
-// oracle/philox_ref.py.  Counter = (env, episode, block, 0), key = config.seed.
-__device__ __forceinline__ void philox4x32_10_(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];   // one v_mad_u64_u32 each
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
+// Philox4x32-10: philox4x32_10_ of dockauv_device.h (shared with the policy kernel).  Counter = (env, episode, block, 0),
+// key = config.seed.
 
 // Scenario generators of the reference (envs/docking3d.py:687-703, 795-988) fed with 12 uniforms U[k] = (x >> 8) 2^-24
 // in the reference's draw order (same mapping as gym_dockauv_amd/scenarios.py: episodes_from_uniforms).

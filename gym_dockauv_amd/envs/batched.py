@@ -616,6 +616,59 @@ class BatchedDocking3d:
         rc = self._lib.dockauv_set_option(self._handle, _capi.OPT_SEQUENCE_RESIDENT, 1 if on else 0)
         _capi.check(self._lib, self._handle, rc, "dockauv_set_option")
 
+    # ------------------------------------------------------------------------------------------ closed loop
+    def make_policy(self, mlp, seed: int = 0, env_id_offset: int = 0):
+        """Put an ``MLPPolicy`` (gym_dockauv_amd/policy.py) on this handle's device: dockauv_policy_create.  ``seed`` keys the
+        exploration noise, ``env_id_offset`` is added to the env index in its counter (shards of one batch)."""
+        from ..policy import DevicePolicy
+        d = mlp.host_desc(seed, env_id_offset)
+        ptr = C.c_void_p()
+        rc = self._lib.dockauv_policy_create(self._handle, C.byref(d), C.byref(ptr))
+        _capi.check(self._lib, self._handle, rc, "dockauv_policy_create")
+        pol = DevicePolicy(ptr, mlp, seed, env_id_offset)
+        self._policies = getattr(self, "_policies", []) + [pol]
+        return pol
+
+    def load_policy(self, policy, mlp=None, device_ptrs=None, log_std_ptr: int = 0, stream: int = 0) -> None:
+        """New weights of the same shapes: dockauv_policy_load.  Either ``mlp`` (host arrays; the call waits for the copies)
+        or ``device_ptrs`` = (W1, b1, W2, b2, W3, b3) device addresses of contiguous float32 arrays (W2 / b2 0 with one
+        hidden layer) plus ``log_std_ptr``: no host round trip, ordered on ``stream``."""
+        if (mlp is None) == (device_ptrs is None):
+            raise ValueError("give either mlp or device_ptrs")
+        if mlp is not None:
+            d = mlp.host_desc(policy.seed, policy.env_id_offset)
+        else:
+            d = _capi.PolicyDesc.from_buffer_copy(policy.shape)
+            d.pointers_on_device = 1
+            d.W1, d.b1, d.W2, d.b2, d.W3, d.b3 = [int(x) or None for x in device_ptrs]
+            d.log_std = int(log_std_ptr) or None
+            d.seed, d.env_id_offset = policy.seed, policy.env_id_offset
+        rc = self._lib.dockauv_policy_load(policy.ptr, C.byref(d), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_policy_load")
+        policy.has_log_std = bool(d.log_std)
+
+    def policy_forward_device(self, policy, rows_ptr: int, actions_ptr: int, t: int = 0, stochastic: bool = False,
+                              stream: int = 0) -> None:
+        """Asynchronous actor forward on device pointers: rows float32 [N][n_obs + 2] (packed rows; only the observation
+        columns are read), actions float32 [N][n_u]."""
+        rc = self._lib.dockauv_policy_forward(self._handle, policy.ptr, C.c_void_p(rows_ptr or None), C.c_void_p(actions_ptr or None),
+                                              int(t), 1 if stochastic else 0, C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_policy_forward")
+
+    def rollout_device(self, policy, rows_in_ptr: int, rows_out_ptr: int, actions_out_ptr: int, n_steps: int, t0: int = 0,
+                       stochastic: bool = False, stream: int = 0, terminal_obs_ptr: int = 0) -> None:
+        """n_steps x (policy, step) queued by one host call (dockauv_rollout): rows_out [n_steps][N][n_obs + 2], actions_out
+        [n_steps][N][n_u], terminal_obs [n_steps][N][n_obs] or 0.  Asynchronous; raises like poll_status()."""
+        rc = self._lib.dockauv_rollout(self._handle, policy.ptr, C.c_void_p(rows_in_ptr or None), C.c_void_p(rows_out_ptr or None),
+                                       C.c_void_p(actions_out_ptr or None), C.c_void_p(terminal_obs_ptr or None), int(n_steps),
+                                       int(t0), 1 if stochastic else 0, C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_rollout")
+
+    def destroy_policy(self, policy) -> None:
+        if policy.ptr is not None and policy.ptr.value:
+            self._lib.dockauv_policy_destroy(policy.ptr)
+            policy.ptr = C.c_void_p()
+
     def time_steps_device(self, actions_ptr: int, obs_ptr: int, reward_ptr: int = 0, done_ptr: int = 0, steps: int = 1,
                           stream: int = 0, packed: bool = False, terminal_obs_ptr: int = 0) -> float:
         """Average KERNEL duration in microseconds from per-dispatch HIP events on `stream` (bench.py)."""
@@ -641,6 +694,9 @@ class BatchedDocking3d:
     # ------------------------------------------------------------------------------------------ VecEnv odds and ends
     def close(self) -> None:
         if getattr(self, "_handle", None) is not None and self._handle.value:
+            for pol in getattr(self, "_policies", []):   # (a policy goes before its handle)
+                self.destroy_policy(pol)
+            self._policies = []
             self._lib.dockauv_destroy(self._handle)
             self._handle = C.c_void_p()
 

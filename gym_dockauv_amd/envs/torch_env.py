@@ -43,6 +43,12 @@ class TorchDocking3d:
                         for _ in range(n_buf)]
         self._terminal = None
         self._i = 0
+        # closed loop (rollout): step counter of the trajectory (the exploration noise's counter), the rows the next policy
+        # forward reads when they are not in self._packed, buffers per rollout length
+        self._t = 0
+        self._last_rows = None
+        self._rollout_bufs = {}
+        self.rollout_terminal_observation = None
         # mixed batches built with sort_vehicles=True: row j of every tensor handed in / out belongs to the caller's env
         # perm[j] (kind-sorted on the device, the caller's order within a kind); identity otherwise
         self.perm = torch.as_tensor(self.batch.perm, device=self.device)
@@ -51,6 +57,7 @@ class TorchDocking3d:
     def reset(self, seed: Optional[int] = None):
         """All envs: new episodes; returns the reference's reset observation (zeros, docking3d.py:269,322)."""
         self.batch.reset(seed=seed)
+        self._last_rows = None
         self._packed[self._i % len(self._packed)].zero_()
         return self._packed[self._i % len(self._packed)][:, : self.n_obs]
 
@@ -63,6 +70,8 @@ class TorchDocking3d:
                 or tuple(actions.shape) != (self.num_envs, self.n_u):
             raise ValueError(f"actions must be a contiguous float32 [{self.num_envs}, {self.n_u}] tensor on {self.device}")
         self._i += 1
+        self._t += 1
+        self._last_rows = None          # (the rows of this step are the trajectory's last)
         out = self._packed[self._i % len(self._packed)]
         term_ptr = 0
         if want_terminal_obs:
@@ -75,6 +84,70 @@ class TorchDocking3d:
         # memory: looked at every step without a synchronisation; what it shows belongs to steps that have already run
         self.batch.poll_status()
         return out[:, : self.n_obs], out[:, self.n_obs], out[:, self.n_obs + 1] > 0.5
+
+    # ------------------------------------------------------------------------------------------ closed loop
+    def make_policy(self, mlp, seed: int = 0):
+        """The on-device policy of an ``MLPPolicy`` (gym_dockauv_amd/policy.py) for ``rollout``."""
+        return self.batch.make_policy(mlp, seed=seed)
+
+    def load_policy(self, policy, module_or_tensors, log_std=None) -> None:
+        """New weights from DEVICE tensors, without a host copy and ordered on the current stream: an ``nn.Sequential`` whose
+        Linear layers live on this device, or a sequence (W1, b1[, W2, b2], W3, b3) of contiguous float32 tensors;
+        ``log_std``: device tensor [n_u] or None.  The tensors are read when the copy runs on the stream."""
+        torch = self.torch
+        if isinstance(module_or_tensors, torch.nn.Module):
+            # a Linear without a bias loads zeros, as MLPPolicy.from_torch does (the allocator keeps the temporary's memory
+            # ordered on the current stream, which is the stream the copy runs on)
+            ts = [t for m in module_or_tensors if isinstance(m, torch.nn.Linear)
+                  for t in (m.weight, m.bias if m.bias is not None else torch.zeros_like(m.weight[:, 0]).contiguous())]
+        else:
+            ts = list(module_or_tensors)
+        ts = [t.detach() for t in ts]
+        if len(ts) == 4:
+            ts[2:2] = [None, None]
+        if len(ts) != 6:
+            raise ValueError("expected the weights and biases of two or three Linear layers")
+        for t in ts + [log_std]:
+            if t is not None and (t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError(f"policy tensors must be contiguous float32 on {self.device}")
+        widths = [policy.n_in] + policy.n_hidden + [policy.n_out]
+        got = [t for t in ts if t is not None]
+        for i in range(len(widths) - 1):
+            if tuple(got[2 * i].shape) != (widths[i + 1], widths[i]) or tuple(got[2 * i + 1].shape) != (widths[i + 1],):
+                raise ValueError(f"layer {i}: expected weight [{widths[i + 1]}, {widths[i]}] and bias [{widths[i + 1]}]")
+        if log_std is not None and tuple(log_std.shape) != (policy.n_out,):
+            raise ValueError(f"log_std must be [{policy.n_out}]")
+        self.batch.load_policy(policy, device_ptrs=[0 if t is None else t.data_ptr() for t in ts],
+                               log_std_ptr=0 if log_std is None else log_std.detach().data_ptr(),
+                               stream=torch.cuda.current_stream().cuda_stream)
+
+    def rollout(self, policy, n_steps: int, stochastic: bool = False, want_terminal_obs: bool = False):
+        """``n_steps`` x (policy, step) queued by ONE host call (dockauv_rollout) on the current stream, starting from the rows
+        the env last wrote (``reset``, ``step`` or an earlier ``rollout``: one trajectory).  Returns
+        (obs [K, N, n_obs], actions [K, N, n_u], reward [K, N], done [K, N] bool): obs[k] / reward[k] / done[k] are what step k
+        returned for actions[k].  Views of buffers the env owns, reused by the next ``rollout`` of the same K; with
+        ``want_terminal_obs`` ``self.rollout_terminal_observation`` [K, N, n_obs] holds the last observation where done."""
+        torch = self.torch
+        K = int(n_steps)
+        if K < 1:
+            raise ValueError("n_steps must be >= 1")
+        bufs = self._rollout_bufs.get(K)
+        if bufs is None:
+            bufs = self._rollout_bufs[K] = [torch.zeros((K, self.num_envs, self.n_obs + 2), device=self.device, dtype=torch.float32),
+                                            torch.zeros((K, self.num_envs, self.n_u), device=self.device, dtype=torch.float32), None]
+        if want_terminal_obs and bufs[2] is None:
+            bufs[2] = torch.zeros((K, self.num_envs, self.n_obs), device=self.device, dtype=torch.float32)
+        rows, acts, term = bufs
+        # the trajectory's last rows: of the last step(), or the last slice of an earlier rollout (also when that is a slice of
+        # `rows` itself: the first policy forward has read it before the step kernel that overwrites it starts)
+        cur = self._last_rows if self._last_rows is not None else self._packed[self._i % len(self._packed)]
+        self.batch.rollout_device(policy, cur.data_ptr(), rows.data_ptr(), acts.data_ptr(), K, t0=self._t, stochastic=stochastic,
+                                  stream=torch.cuda.current_stream().cuda_stream,
+                                  terminal_obs_ptr=term.data_ptr() if (want_terminal_obs and term is not None) else 0)
+        self._t += K
+        self._last_rows = rows[K - 1]
+        self.rollout_terminal_observation = term if want_terminal_obs else None
+        return rows[:, :, : self.n_obs], acts, rows[:, :, self.n_obs], rows[:, :, self.n_obs + 1] > 0.5
 
     @property
     def terminal_observation(self):

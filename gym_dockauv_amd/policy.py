@@ -1,0 +1,182 @@
+"""
+The library's own actor for the closed loop: a small MLP (one or two hidden layers of up to 128 units) evaluated on the
+device by libdockauv's policy kernel (include/dockauv.h: dockauv_policy_*, dockauv_rollout).  The reference's counterpart
+is SB3's ``MlpPolicy``, which train.py:64 instantiates and train.py:64-71 / 86-119 query once per step.
+
+``MLPPolicy`` is a plain host object that holds the arrays; ``BatchedDocking3d.make_policy`` / ``TorchDocking3d.make_policy``
+put it on the device.  ``forward_reference`` and ``normals_reference`` are float64 NumPy statements of what the kernel
+computes (for tests and for callers who want to check a port); they are never used as a compute path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import _capi
+
+_ACTS = {"none": _capi.ACT_NONE, "tanh": _capi.ACT_TANH, "relu": _capi.ACT_RELU}
+
+# Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11; Random123 constants)
+_M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_W0, _W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+_MASK = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+
+
+def _philox4x32_10(counter: np.ndarray, key: Sequence[int]) -> np.ndarray:
+    """counter [..., 4] (values < 2^32), key (k0, k1) -> [..., 4] uint64 words < 2^32"""
+    c = [np.array(counter[..., i], dtype=np.uint64) for i in range(4)]
+    k0, k1 = np.uint64(key[0]), np.uint64(key[1])
+    for _ in range(10):
+        p0, p1 = _M0 * c[0], _M1 * c[2]
+        c = [(p1 >> _S32) ^ c[1] ^ k0, p1 & _MASK, (p0 >> _S32) ^ c[3] ^ k1, p0 & _MASK]
+        k0, k1 = (k0 + _W0) & _MASK, (k1 + _W1) & _MASK
+    return np.stack(c, axis=-1)
+
+
+def _act(x: np.ndarray, kind: str) -> np.ndarray:
+    if kind == "tanh":
+        return np.tanh(x)
+    if kind == "relu":
+        return np.maximum(x, 0.0)
+    return x
+
+
+class MLPPolicy:
+    """a = out_act(W3 act(W2 act(W1 obs + b1) + b2) + b3); ``layers``: [(W [out, in], b [out]), ...] of two or three
+    Linear layers (torch.nn.Linear layout); ``log_std`` [n_out] or None."""
+
+    def __init__(self, layers, hidden_act: str = "tanh", out_act: str = "none", log_std=None):
+        if len(layers) not in (2, 3):
+            raise ValueError("MLPPolicy takes one or two hidden layers plus the output layer")
+        if hidden_act not in ("tanh", "relu"):
+            raise ValueError("hidden_act must be 'tanh' or 'relu'")
+        if out_act not in ("none", "tanh"):
+            raise ValueError("out_act must be 'none' or 'tanh'")
+        self.layers = [(np.ascontiguousarray(W, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)) for W, b in layers]
+        n = self.layers[0][0].shape[1]
+        for W, b in self.layers:
+            if W.ndim != 2 or b.shape != (W.shape[0],) or W.shape[1] != n:
+                raise ValueError("layer shapes do not chain: W [out, in], b [out]")
+            n = W.shape[0]
+        self.hidden_act, self.out_act = hidden_act, out_act
+        self.log_std = None if log_std is None else np.ascontiguousarray(log_std, dtype=np.float32).reshape(-1)
+        if self.log_std is not None and self.log_std.shape != (self.n_out,):
+            raise ValueError("log_std must have n_out entries")
+
+    n_in = property(lambda self: int(self.layers[0][0].shape[1]))
+    n_out = property(lambda self: int(self.layers[-1][0].shape[0]))
+    n_hidden = property(lambda self: [int(W.shape[0]) for W, _ in self.layers[:-1]])
+
+    # ------------------------------------------------------------------------------------------ construction
+    @classmethod
+    def from_torch(cls, module_or_state_dict, hidden_act: Optional[str] = None, out_act: Optional[str] = None, log_std=None):
+        """An ``nn.Sequential`` of Linear / Tanh / ReLU layers (activations are read off the modules), or an SB3-style
+        state dict with ``mlp_extractor.policy_net.{0,2}.*``, ``action_net.*`` and (optionally) ``log_std`` -- there the
+        hidden activation is ``hidden_act`` (SB3's default: tanh) and the output is raw unless ``out_act`` says otherwise.
+        Needs no stable-baselines3 import."""
+        def arr(t):
+            return (t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)).astype(np.float32)
+
+        if isinstance(module_or_state_dict, dict) or hasattr(module_or_state_dict, "keys"):
+            sd = module_or_state_dict
+            layers = []
+            for i in (0, 2):
+                k = f"mlp_extractor.policy_net.{i}.weight"
+                if k in sd:
+                    layers.append((arr(sd[k]), arr(sd[f"mlp_extractor.policy_net.{i}.bias"])))
+            if not layers or "action_net.weight" not in sd:
+                raise ValueError("state dict needs mlp_extractor.policy_net.0.* and action_net.*")
+            layers.append((arr(sd["action_net.weight"]), arr(sd["action_net.bias"])))
+            if log_std is None and "log_std" in sd:
+                log_std = arr(sd["log_std"])
+            return cls(layers, hidden_act or "tanh", out_act or "none", log_std)
+        layers, acts = [], []
+        for m in module_or_state_dict:
+            name = type(m).__name__
+            if name == "Linear":
+                layers.append((arr(m.weight), arr(m.bias) if m.bias is not None else np.zeros(m.weight.shape[0], np.float32)))
+                acts.append("none")
+            elif name in ("Tanh", "ReLU") and layers:
+                if acts[-1] != "none":
+                    raise ValueError("two activations in a row")
+                acts[-1] = name.lower()
+            else:
+                raise ValueError(f"unsupported layer {name}: Linear, Tanh and ReLU are")
+        if len(layers) not in (2, 3) or len(set(acts[:-1])) != 1 or acts[0] == "none":
+            raise ValueError("expected Linear-act-[Linear-act-]Linear[-Tanh] with one kind of hidden activation")
+        if (hidden_act and hidden_act != acts[0]) or (out_act and out_act != acts[-1]):
+            raise ValueError("the activations asked for are not the module's")
+        return cls(layers, acts[0], acts[-1], log_std)
+
+    # ------------------------------------------------------------------------------------------ float64 statements
+    def forward_reference(self, obs: np.ndarray, z: Optional[np.ndarray] = None) -> np.ndarray:
+        """float64 forward of float32 weights: obs [..., n_in] -> [..., n_out]; ``z`` [..., n_out]: exploration normals,
+        added as exp(log_std) * z before the output activation."""
+        x = np.asarray(obs, dtype=np.float64)
+        for W, b in self.layers[:-1]:
+            x = _act(x @ W.astype(np.float64).T + b.astype(np.float64), self.hidden_act)
+        W, b = self.layers[-1]
+        x = x @ W.astype(np.float64).T + b.astype(np.float64)
+        if z is not None:
+            if self.log_std is None:
+                raise ValueError("z given but the policy has no log_std")
+            x = x + np.exp(self.log_std.astype(np.float64)) * np.asarray(z, dtype=np.float64)
+        return _act(x, self.out_act)
+
+    @staticmethod
+    def normals_reference(seed: int, env_ids, t: int, n_out: int) -> np.ndarray:
+        """The standard normals the kernel draws for step counter ``t``: Philox4x32-10 counter (env id mod 2^32, t mod 2^32,
+        j, 2), key = seed; Box-Muller cos branch on the first two words with u1 = ((x0 >> 8) + 0.5) 2^-24, u2 = (x1 >> 8) 2^-24.
+        ``env_ids`` already include the policy's env_id_offset.  Returns float64 [len(env_ids), n_out].
+
+        This is the exact statement.  The kernel forms u1 in float32 (as the step kernel's current noise does), which holds
+        the + 0.5 only while x0 >> 8 < 2^23: above that the sum is rounded to even, so u1 is off by up to 2^-25 there and the
+        top value x0 >> 8 = 2^24 - 1 gives u1 = 1 and z = 0.  That rounding, amplified by 1 / (u1 sqrt(-2 log u1)) near
+        u1 = 1, and the float32 log / sqrt / cos are the whole device-to-reference deviation (a few 1e-5 at most)."""
+        env = np.asarray(env_ids, dtype=np.uint64).reshape(-1) & _MASK
+        ctr = np.empty((env.size, n_out, 4), dtype=np.uint64)
+        ctr[..., 0] = env[:, None]
+        ctr[..., 1] = np.uint64(int(t) & 0xFFFFFFFF)
+        ctr[..., 2] = np.arange(n_out, dtype=np.uint64)[None, :]
+        ctr[..., 3] = np.uint64(2)
+        x = _philox4x32_10(ctr, (int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF))
+        u1 = ((x[..., 0] >> np.uint64(8)).astype(np.float64) + 0.5) / 16777216.0
+        u2 = (x[..., 1] >> np.uint64(8)).astype(np.float64) / 16777216.0
+        return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+
+    # ------------------------------------------------------------------------------------------ C ABI
+    def shape_desc(self) -> _capi.PolicyDesc:
+        """dockauv_policy_desc with the shapes and activations filled in and no arrays"""
+        d = _capi.PolicyDesc()
+        d.struct_size = C.sizeof(_capi.PolicyDesc)
+        d.precision = _capi.F32
+        d.n_in, d.n_out = self.n_in, self.n_out
+        d.n_hidden[0] = self.n_hidden[0]
+        d.n_hidden[1] = self.n_hidden[1] if len(self.n_hidden) == 2 else 0
+        d.hidden_act, d.out_act = _ACTS[self.hidden_act], _ACTS[self.out_act]
+        return d
+
+    def host_desc(self, seed: int = 0, env_id_offset: int = 0) -> _capi.PolicyDesc:
+        """dockauv_policy_desc over this object's host arrays (which must outlive the call that reads it)"""
+        d = self.shape_desc()
+        d.pointers_on_device = 0
+        ptrs = [a.ctypes.data for Wb in self.layers for a in Wb]
+        if len(self.layers) == 2:
+            ptrs[2:2] = [None, None]
+        d.W1, d.b1, d.W2, d.b2, d.W3, d.b3 = ptrs
+        d.log_std = None if self.log_std is None else self.log_std.ctypes.data
+        d.seed, d.env_id_offset = int(seed), int(env_id_offset)
+        return d
+
+
+class DevicePolicy:
+    """A dockauv_policy of one BatchedDocking3d handle (made by ``make_policy``): the handle plus what a reload needs."""
+
+    def __init__(self, ptr: C.c_void_p, mlp: MLPPolicy, seed: int, env_id_offset: int):
+        self.ptr, self.seed, self.env_id_offset = ptr, int(seed), int(env_id_offset)
+        self.shape = mlp.shape_desc()
+        self.n_in, self.n_hidden, self.n_out = mlp.n_in, mlp.n_hidden, mlp.n_out
+        self.has_log_std = mlp.log_std is not None

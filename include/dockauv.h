@@ -332,6 +332,63 @@ int dockauv_p2p_gather(const dockauv_p2p_plan* plan, const void* src, uint32_t s
 int dockauv_step_gather_sequence(dockauv_handle h, const dockauv_step_io* ios, int n, const dockauv_p2p_plan* plans,
                                  int n_plans, uint64_t t0, int lag, void* compute_stream, void* gather_stream);
 
+/*
+ * Closed loop: the library's own policy and a rollout queued by one host call.  Replaces the learner's rollout loop
+ * (train.py:64-71: SB3's collect_rollouts, policy forward then env.step, per step) and the prediction loop (train.py:86-119:
+ * model.predict then env.step) for a policy that is a small MLP actor -- SB3's MlpPolicy, which train.py:64 instantiates
+ * (two hidden layers of 64 tanh units by default, an action_net, a state-independent log_std).  The actor is evaluated by a
+ * gfx950 matrix kernel directly on the packed [obs | reward | done] rows the step kernel writes, so that neither Python nor
+ * torch nor a graph capture sits between two steps.  Arithmetic is float32 throughout: every pre-activation is one fused
+ * multiply-add chain from the bias in a k order fixed by the shapes alone; env i's action depends on row i and the weights
+ * only.  A value head, log-probabilities and GAE stay with the learner.
+ */
+#define DOCKAUV_ACT_NONE 0       /* output: raw (PPO; the step kernel clips, objects/auvsim.py:74) */
+#define DOCKAUV_ACT_TANH 1       /* hidden: SB3's default; output: SAC-style squashing */
+#define DOCKAUV_ACT_RELU 2       /* hidden only */
+#define DOCKAUV_POLICY_MAX_WIDTH 128
+/* The MLP actor (SB3 MlpPolicy: mlp_extractor.policy_net + action_net + log_std; train.py:64).  Arrays are read during the
+ * call that gets the descriptor (create / load) and not kept. */
+typedef struct dockauv_policy_desc {
+    uint32_t struct_size;          /* sizeof(dockauv_policy_desc): ABI check */
+    int32_t precision;             /* DOCKAUV_F32 only for now; the field is there for a later bf16 mode */
+    int32_t n_in, n_hidden[2], n_out;  /* n_in = dockauv_n_obs, widths 1..DOCKAUV_POLICY_MAX_WIDTH, n_hidden[1] == 0: one
+                                      hidden layer; n_out = dockauv_n_u */
+    int32_t hidden_act, out_act;   /* DOCKAUV_ACT_TANH / _RELU; DOCKAUV_ACT_NONE / _TANH */
+    int32_t pointers_on_device;    /* 0: host arrays; 1: device arrays, copied stream-ordered */
+    int32_t reserved;
+    const float *W1, *b1, *W2, *b2, *W3, *b3;  /* row-major [out][in] = torch.nn.Linear.weight; W2/b2 NULL with one layer */
+    const float *log_std;          /* nullable [n_out]: exploration noise exp(log_std[j]) * N(0, 1) when asked for */
+    uint64_t seed, env_id_offset;  /* exploration: Philox4x32-10 key; added to the env index in the counter (shards) */
+} dockauv_policy_desc;
+typedef struct dockauv_policy_s* dockauv_policy;
+
+/* MlpPolicy(...) of train.py:64 for the actor part: validates the descriptor (every failure DOCKAUV_E_INVALID, the message
+ * names the field; the descriptor's own fields first, then what must match the handle: float32 handle, n_in == dockauv_n_obs,
+ * n_out == dockauv_n_u) before any device call, then uploads the weights.  A policy belongs to its handle's device and is
+ * destroyed before the handle.  Errors of the policy calls are reported through dockauv_last_error(h). */
+int dockauv_policy_create(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out);
+/* policy.load_state_dict: new weights of the same shapes and activations (what a learner on the same GPU calls once per
+ * iteration, train.py:64-71, with pointers_on_device = 1: no host round trip, ordered on the stream; seed / env_id_offset
+ * are taken over as well). */
+int dockauv_policy_load(dockauv_policy p, const dockauv_policy_desc* d, void* hip_stream);
+int dockauv_policy_destroy(dockauv_policy p);
+/* policy.predict / the actor's forward (train.py:86-119) for all envs of the handle; device pointers, asynchronous on stream.
+ * rows: float32 [n_envs][n_obs + 2] packed rows (only the first n_obs columns are read); actions: float32 [n_envs][n_u].
+ * stochastic != 0 with a loaded log_std: a = mean + exp(log_std[j]) * z before the output activation, z the standard normal
+ * of Philox4x32-10 counter (env_id_offset + i, t mod 2^32, j, 2), key = seed, Box-Muller cos branch on the first two words
+ * (slots 0 and 1 of the last counter word belong to the episode generator and the current noise). */
+int dockauv_policy_forward(dockauv_handle h, dockauv_policy p, const float* rows, float* actions,
+                           uint64_t t, int stochastic, void* hip_stream);
+/* The rollout loop of train.py:64-71 (learner) / 86-119 (predict): n_steps x (policy, step) queued back to back on the stream
+ * by this one call, asynchronous.  rows_out: float32 [n_steps][n_envs][n_obs + 2]; actions_out: float32
+ * [n_steps][n_envs][n_u]; terminal_obs: nullable float32 [n_steps][n_envs][n_obs].  Step k: the policy reads rows_in (k = 0)
+ * or rows_out[k - 1] and writes actions_out[k] with counter t = t0 + k; dockauv_step reads actions_out[k] and writes
+ * rows_out[k] (pack_reward_done = 1, the handle's reset mode, terminal_obs[k] when given).  Exactly the launches of
+ * 2 n_steps calls of dockauv_policy_forward / dockauv_step; the resident sequence path is not used.  Returns what
+ * dockauv_poll_status returns, looked at once after queueing. */
+int dockauv_rollout(dockauv_handle h, dockauv_policy p, const float* rows_in, float* rows_out, float* actions_out,
+                    float* terminal_obs, int n_steps, uint64_t t0, int stochastic, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
