@@ -571,6 +571,19 @@ def gen_trajectories():
     gen_mixed_partner()
     gen_near_obstacles()
     gen_lauv_collision()
+    gen_sensor_free_short()
+
+
+def gen_sensor_free_short():
+    """Sensor-free episodes that END: traj_SimpleDocking3d_lauv_random never meets a terminal step, and the sensor-free
+    BlueROV2 fixtures run at h = 0.1.  LAUV and BlueROV2 in SimpleDocking3d at h = 0.02 with max_timesteps 60 (time-limit
+    terminations every 61 steps): the LAUV and the mixed sensor-free product kernels with the terminal copy
+    (tests/test_gpu_reset.py)."""
+    short = {"t_step_size": 0.02, "max_timesteps": 60}
+    run_traj("traj_SimpleDocking3d_lauv_short", "SimpleDocking3d", "LAUV", 91, 200, lambda rs: ctrl_random(rs),
+             cfg_over=short, act_seed=21)
+    run_traj("traj_SimpleDocking3d_bluerov2_h002_short", "SimpleDocking3d", "BlueROV2", 92, 200, lambda rs: ctrl_random(rs),
+             cfg_over=short, act_seed=22)
 
 
 def gen_mixed_partner():

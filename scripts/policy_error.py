@@ -5,7 +5,8 @@ helpers of tests/test_gpu_policy.py (the same weights, rows, shapes and batch si
   python scripts/policy_error.py [--out profiles/policy/forward_error.txt]
 
 forward_*: max |a - a_f64| per shape and batch size (MLPPolicy.forward_reference); exploration_max_dev: max |z_dev - z_ref|
-against MLPPolicy.normals_reference.  tests/test_gpu_policy.py reads exploration_max_dev as the base of its bound (4 x the
+against MLPPolicy.normals_reference; scaled_*: the saturated case's device and float32-NumPy errors; closed_loop_*: dockauv_rollout
+against the oracle driven by the float64 forward.  tests/test_gpu_policy.py reads exploration_max_dev as the base of its bound (4 x the
 value, capped at 1e-4), so the file is to be rewritten only with a kernel whose figures have been looked at.
 """
 import argparse
@@ -38,6 +39,19 @@ def main():
     lines += ["# exploration: max |z_dev - z_ref| over 65 536 x 6 draws, t in {0, 1, 2^32 - 1}, env_id_offset in {0, 1 000 000};",
               f"# z_dev = a_stochastic - a_deterministic with log_std = 0; the test asserts 4 x this value, capped at {T.EXPLORATION_CAP:g}",
               f"exploration_max_dev {dev:.4e}"]
+    lines += ["# saturated tanh units: SCALED = 36-128-128-3 tanh actor, every weight and bias x w, observations x x, 1 000 rows; device and",
+              "# float32-NumPy error against float64 (max |a - a_f64|) and the largest |a_f64|; the test asserts device <= 8 x NumPy"]
+    for w, x in ((4, 10), (16, 100)):
+        dev_err, np_err, amax = T.scaled_errors(w, x)
+        lines += [f"scaled_x{w}_obs_x{x}_device_err {dev_err:.4e}", f"scaled_x{w}_obs_x{x}_numpy_f32_err {np_err:.4e}",
+                  f"scaled_x{w}_obs_x{x}_max_abs_a {amax:.3f}"]
+        print("\n".join(lines[-3:]), flush=True)
+    obs_dev, rew_dev, done_equal, n_done = T.closed_loop_vs_oracle()
+    lines += ["# closed loop: dockauv_rollout of a 36-64-64-6 tanh actor, 48 envs of SimpleCurrentDocking3d x 14 steps, against OracleEnv driven",
+              "# by the float64 forward; max |obs - obs_oracle| (bound helpers.TOL f32 obs = 1e-5), max reward deviation relative to max(1, |r|)",
+              f"closed_loop_max_obs_dev {obs_dev:.4e}", f"closed_loop_max_reward_dev {rew_dev:.4e}",
+              f"closed_loop_done_equal {int(done_equal)}", f"closed_loop_oracle_episodes_ended {n_done}"]
+    print("\n".join(lines[-4:]), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")

@@ -124,6 +124,27 @@ def teacher_forced_inputs(g, steps, max_caps, max_sph):
     return dict(state=state[steps], u=u[steps], tsteps=tsteps[steps], noise=w[steps], episodes=ep, actions=act, gold=gold)
 
 
+def interleaved_teacher_forced_inputs(gs, n_envs, max_caps, max_sph):
+    """teacher_forced_inputs of a batch made of len(gs) golden trajectories: env j starts at golden step (j // K) % T of
+    trajectory j % K (K = len(gs)), the layout of a mixed batch with interleaved vehicle kinds."""
+    K = len(gs)
+    parts = []
+    for k, g in enumerate(gs):
+        envs_k = np.arange(k, n_envs, K)
+        parts.append((envs_k, teacher_forced_inputs(g, (envs_k // K) % int(g["meta_T"]), max_caps, max_sph)))
+
+    def merge(get):
+        first = get(parts[0][1])
+        out = np.zeros((n_envs,) + first.shape[1:], dtype=first.dtype)
+        for envs_k, inp in parts:
+            out[envs_k] = get(inp)
+        return out
+    inp = {k: merge(lambda p, k=k: p[k]) for k in ("state", "u", "tsteps", "noise", "actions")}
+    inp["episodes"] = {k: merge(lambda p, k=k: p["episodes"][k]) for k in parts[0][1]["episodes"]}
+    inp["gold"] = {k: merge(lambda p, k=k: p["gold"][k]) for k in parts[0][1]["gold"]}
+    return inp
+
+
 def load_teacher_forced(env, inp):
     from gym_dockauv_amd import _capi
     n = inp["state"].shape[0]

@@ -108,6 +108,11 @@ def test_config3_write_back_twin_beyond_262144_envs():
     run_tiled(["traj_SphereDocking3d_bluerov2_fan16_random"], 262144 + 64, threads=256)   # (0 = auto: one wave per group there)
 
 
+def test_config4_write_back_twin_beyond_262144_envs():
+    """The LAUV's twin of the same kind (63 rays, capsules): config 4 at 256 threads per group, 4 097 groups, the ray-rich fixture."""
+    run_tiled(["traj_ObstaclesDocking3d_lauv_near"], 262144 + 64, threads=256)
+
+
 @pytest.mark.parametrize("which,precision", [("sphere", "f32"), ("sphere", "f64"), ("lauv_near", "f32"), ("lauv_ram", "f32"),
                                              ("mixed_near", "f32"), ("mixed_near", "f64")])
 def test_one_wave_ray_groups_vs_reference(which, precision):

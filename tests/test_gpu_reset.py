@@ -121,13 +121,114 @@ def test_tail_group_and_large_batch():
         big.close()
 
 
+# sensor-free workloads no BASELINE config has: LAUV alone, and the mixed batch (both at the LAUV's step size)
+LAUV_SIMPLE = dict(scenario="SimpleDocking3d", vehicle="LAUV", h=0.02, mixed=False)
+MIXED_SIMPLE = dict(scenario="SimpleCurrentDocking3d", vehicle="BlueROV2", h=0.02, mixed=True)
 SEQ_CASES = {
-    # name: (bench config id or scenario kwargs, envs, threads)
+    # name: (bench config id or one of the dicts above, envs, threads[, "many_rounds"])
     "config2_256": (2, 777, 0), "config2_128": (2, 1000, 128), "config2_64": (2, 1000, 64),
     "config3_256": (3, 777, 0), "config3_64": (3, 1000, 64),
     "config4_512": (4, 777, 512), "config4_256": (4, 777, 256), "config4_64": (4, 1000, 64),
     "config5_256": (5, 778, 0), "config5_64": (5, 778, 64),
+    # the sensor-free resident kernels of the LAUV and of mixed batches, and the 512-thread ray kernels of BlueROV2 and mixed
+    "lauv_simple_64": (LAUV_SIMPLE, 777, 64), "lauv_simple_128": (LAUV_SIMPLE, 777, 128), "lauv_simple_256": (LAUV_SIMPLE, 777, 256),
+    "mixed_simple_64": (MIXED_SIMPLE, 778, 64), "mixed_simple_128": (MIXED_SIMPLE, 778, 128), "mixed_simple_256": (MIXED_SIMPLE, 778, 256),
+    "config3_512": (3, 777, 512), "config5_512": (5, 778, 512),
+    # batches that run in several rounds of groups, at the smallest size that selects the kernel: beyond 262 144 envs launch_seq_vk
+    # (dockauv_step.hip.inc) gives the 256-thread ray kernel of one vehicle kind its write-back twin and keeps the mixed one
+    # written through; from 196 608 envs up dockauv_create gives config 4 one wave per group with the records in registers
+    "config3_many_rounds": (3, 262144 + 64, 256, "many_rounds"), "config4_many_rounds": (4, 262144 + 64, 256, "many_rounds"),
+    "config5_many_rounds": (5, 262144 + 128, 256, "many_rounds"), "config4_one_wave_many_rounds": (4, 196608 + 64, 0, "many_rounds"),
 }
+
+
+def _seq_workload(what, n_envs):
+    import copy
+    import sys
+    import os
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    if not isinstance(what, dict):
+        wl = bench.workload(what, n_envs)
+        return copy.deepcopy(wl["cfg"]), wl["scenario"], wl["vehicles"]
+    from gym_dockauv_amd.config.env_config import BASE_CONFIG
+    cfg = copy.deepcopy(BASE_CONFIG)
+    cfg["vehicle"], cfg["t_step_size"] = what["vehicle"], what["h"]
+    return cfg, what["scenario"], (["BlueROV2" if i % 2 == 0 else "LAUV" for i in range(n_envs)] if what["mixed"] else None)
+
+
+def _first_difference(torch, ref, got, k):
+    """where step k's rows first differ, for the failure message: env (its lane and its group of 64 envs) and column"""
+    bad = (ref.view(torch.int32) != got.view(torch.int32)).nonzero()
+    if bad.numel() == 0:
+        return ""
+    env, col = int(bad[0, 0]), int(bad[0, 1])
+    n_env = int(bad[:, 0].unique().numel())
+    return (f"step {k}: {bad.shape[0]} words of {n_env} envs differ; first: env {env} (lane {env % 64}, group {env // 64}), column {col}: "
+            f"single {float(ref[env, col])!r} sequence {float(got[env, col])!r}")
+
+
+def _many_rounds_sequence(case):
+    """The many-rounds cases of SEQ_CASES: K = 66 steps (one resident launch of 64 and one of 2), the modes single / resident /
+    resident_one_buffer, rows compared on the device.  Two copies of 66 steps of rows stay below 4 GB for the 22-word rows of
+    config 3 and for config 4 at 196 672 envs: the other cases keep the rows of the steps 0, 1, 63, 64 and 65 (around the launch
+    boundary) apart, send the other steps' rows to one scratch buffer, and leave the rest to the one-buffer mode and to the
+    final state, which every step feeds."""
+    import time
+    import torch
+    from gym_dockauv_amd.envs.batched import BatchedDocking3d
+    what, N, threads, _ = SEQ_CASES[case]
+    K = 66
+    dev = torch.device("cuda", 0)
+    cfg, scenario, vehicles = _seq_workload(what, N)
+    cfg["max_timesteps"] = 23
+    ref = spheres = None
+    seconds = 0.0
+    for mode in ("single", "resident", "resident_one_buffer"):
+        env = BatchedDocking3d(cfg, num_envs=N, scenario=scenario, precision="f32", reset_mode="device", device_seed=99,
+                               rng="batched", vehicles=vehicles, threads_per_group=threads)
+        try:
+            assert not threads or env.threads_in_use == threads
+            env._gen = np.random.default_rng(3)
+            if spheres is not None:      # (config 3's sphere shells come from one host generator per env: drawn once for the three modes)
+                env._static_spheres = spheres
+            env.reset()
+            spheres = getattr(env, "_static_spheres", None)
+            t0 = time.perf_counter()
+            g = torch.Generator(device=dev)
+            g.manual_seed(5)
+            acts = torch.rand((K, N, env.n_u), device=dev, generator=g) * 2 - 1
+            words = env.packed_row_words(True)
+            keep = list(range(K)) if 2 * K * N * words * 4 <= 4e9 else [0, 1, 63, 64, 65]
+            one = mode == "resident_one_buffer"
+            rows = {k: torch.zeros((N, words), device=dev) for k in ([K - 1] if one else keep)}
+            scratch = rows[K - 1] if one else torch.zeros((N, words), device=dev)
+            bufs = [rows.get(k, scratch) for k in range(K)]
+            stream = torch.cuda.current_stream().cuda_stream
+            if mode == "single":
+                for k in range(K):
+                    env.step_device(acts[k].data_ptr(), bufs[k].data_ptr(), stream=stream, packed=True)
+            else:
+                env.set_sequence_resident(True)
+                ios = env.make_step_sequence([acts[k].data_ptr() for k in range(K)], [b.data_ptr() for b in bufs], packed=True)
+                env.run_step_sequence(ios, stream=stream)
+            torch.cuda.synchronize()
+            env.synchronize()
+            host = (env.state.copy(), env.get_field(9).copy(), env.t_steps.copy())
+            if mode == "single":
+                ref = (rows, host)
+                assert int(host[1].max()) >= 2, "episodes must end inside the sequence"
+            else:
+                for k in sorted(rows):
+                    assert torch.equal(rows[k].view(torch.int32), ref[0][k].view(torch.int32)), \
+                        f"{case}: {mode} differs from single launches: " + _first_difference(torch, ref[0][k], rows[k], k)
+                for a, b, name in zip(ref[1], host, ("state", "episode counters", "t_steps")):
+                    assert np.array_equal(a, b), f"{case}: {mode}: {name} differ from single launches"
+            del acts, rows, scratch, bufs
+            seconds += time.perf_counter() - t0
+        finally:
+            env.close()
+    print(f"{case}: {N} envs x {K} steps x 3 modes, {seconds:.1f} s beyond env construction")
 
 
 @pytest.mark.gpu
@@ -137,24 +238,23 @@ def test_step_sequence_equals_single_steps(case):
     (option off) AND as the resident fast path (default: every group walks its envs through up to 64 steps per launch, no
     launch boundary in between; include/dockauv.h).  70 steps = two resident launches; episodes are short, so in-kernel
     resets happen inside the sequences; every BASELINE workload's kernel, every group shape; packed float32 and bfloat16
-    rows; distinct output rows per step and one buffer for all steps (then the last step's rows must be what is left)."""
-    import copy
-    import sys
-    import os
+    rows; distinct output rows per step and one buffer for all steps (then the last step's rows must be what is left).
+    Every step_seq_kernel launch_seq_vk can select has a case (SEQ_CASES); that the resident modes do run it, and not the
+    silent fall-back to single launches, is on record in profiles/coverage/kernels.txt (a kernel trace of this file)."""
     import torch
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    import bench
     from gym_dockauv_amd.envs.batched import BatchedDocking3d
-    cid, N, threads = SEQ_CASES[case]
+    if len(SEQ_CASES[case]) == 4:
+        return _many_rounds_sequence(case)
+    what, N, threads = SEQ_CASES[case]
     K = 70
     dev = torch.device("cuda", 0)
-    wl = bench.workload(cid, N)
-    cfg = copy.deepcopy(wl["cfg"])
+    cfg, scenario, vehicles = _seq_workload(what, N)
     cfg["max_timesteps"] = 23
     outs = {}
     for mode in ("single", "launches", "resident", "resident_one_buffer", "resident_bf16", "single_bf16"):
-        env = BatchedDocking3d(cfg, num_envs=N, scenario=wl["scenario"], precision="f32", reset_mode="device", device_seed=99,
-                               rng="batched", vehicles=wl["vehicles"], threads_per_group=threads)
+        env = BatchedDocking3d(cfg, num_envs=N, scenario=scenario, precision="f32", reset_mode="device", device_seed=99,
+                               rng="batched", vehicles=vehicles, threads_per_group=threads)
+        assert not threads or env.threads_in_use == threads
         env._gen = np.random.default_rng(3)
         env.reset()
         g = torch.Generator(device=dev)
@@ -335,10 +435,25 @@ def test_device_noise_matches_philox_reference(precision):
         env.close()
 
 
+# (golden trajectories, threads_per_group): one trajectory, or a BlueROV2 / LAUV pair for an interleaved mixed batch.  Which
+# step_kernel<..., TERM> each case launches is recorded in profiles/coverage/kernels.txt: BlueROV2 sensor-free and with rays at
+# 256 threads, LAUV at 512 (dockauv_create's choice for a small config-4 batch) and at 256 (its choice from 65 536 envs up: what
+# TorchDocking3d.step(want_terminal_obs=True) runs there), LAUV sensor-free, and the mixed kernels sensor-free and with rays at
+# 256 and 512 threads.
+_NEAR_PAIR = ("traj_ObstaclesCurrentDocking3d_bluerov2_h002_near", "traj_ObstaclesCurrentDocking3d_lauv_near")
+_SHORT_PAIR = ("traj_SimpleDocking3d_bluerov2_h002_short", "traj_SimpleDocking3d_lauv_short")
+TERM_CASES = [pytest.param((n,), 0, id=n) for n in
+              ("traj_ObstaclesCurrentDocking3d_bluerov2_random", "traj_SphereDocking3d_bluerov2_fan16_random",
+               "traj_ObstaclesDocking3d_lauv_near", "traj_SimpleDocking3d_bluerov2_roll")] + [
+    pytest.param(("traj_ObstaclesDocking3d_lauv_near",), 256, id="traj_ObstaclesDocking3d_lauv_near-256"),
+    pytest.param(("traj_SimpleDocking3d_lauv_short",), 0, id="traj_SimpleDocking3d_lauv_short"),
+    pytest.param(_NEAR_PAIR, 256, id="mixed_near-256"), pytest.param(_NEAR_PAIR, 512, id="mixed_near-512"),
+    pytest.param(_SHORT_PAIR, 0, id="mixed_short")]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["traj_ObstaclesCurrentDocking3d_bluerov2_random", "traj_SphereDocking3d_bluerov2_fan16_random",
-                                  "traj_ObstaclesDocking3d_lauv_near", "traj_SimpleDocking3d_bluerov2_roll"])
-def test_product_kernel_terminal_observation_vs_reference(name):
+@pytest.mark.parametrize("names,threads_per_group", TERM_CASES)
+def test_product_kernel_terminal_observation_vs_reference(names, threads_per_group):
     """The product kernel with the terminal copy (TERM: packed rows + terminal_obs on device pointers, in-kernel auto-reset)
     against the reference: every env starts where a golden step started; where the reference's episode ends in that step
     the packed row must be the reset observation (zeros, Q8) and terminal_obs the reference's last observation of the
@@ -346,11 +461,33 @@ def test_product_kernel_terminal_observation_vs_reference(name):
     packed row is the reference's observation and terminal_obs is left untouched."""
     import torch
     from tests import helpers as H
-    g = H.load(name)
-    T = int(g["meta_T"])
-    env, max_caps, max_sph = H.make_batched(g, T, "f32", reset_mode="device", device_seed=3, rng="batched")
-    try:
+    gs = [H.load(n) for n in names]
+    if len(gs) == 1:
+        g = gs[0]
+        T = int(g["meta_T"])
+        env, max_caps, max_sph = H.make_batched(g, T, "f32", reset_mode="device", device_seed=3, rng="batched",
+                                                threads_per_group=threads_per_group)
         inp = H.teacher_forced_inputs(g, np.arange(T), max_caps, max_sph)
+    else:
+        # a mixed batch the way tests/test_gpu_fullsize.py: run_tiled builds one: even envs BlueROV2, odd envs LAUV, one copy of
+        # every golden step of both trajectories
+        from gym_dockauv_amd.envs.batched import BatchedDocking3d
+        cfg = H.config_from_meta(gs[0])
+        c2 = H.config_from_meta(gs[1])
+        assert c2["t_step_size"] == cfg["t_step_size"] and c2["max_timesteps"] == cfg["max_timesteps"]
+        assert c2["radar"] == cfg["radar"] and H.scenario_of(gs[1]) == H.scenario_of(gs[0])
+        T = 2 * max(int(g["meta_T"]) for g in gs)
+        max_caps = max(int(g["ep_n_capsules"].max()) if g["ep_n_capsules"].size else 0 for g in gs)
+        max_sph = max(int(g["ep_sph_radii"].shape[1]) for g in gs)
+        vehicles = [str(gs[j % 2]["meta_vehicle"]) for j in range(T)]
+        assert vehicles[:2] == ["BlueROV2", "LAUV"]
+        env = BatchedDocking3d(cfg, num_envs=T, scenario=H.scenario_of(gs[0]), precision="f32", reset_mode="device", device_seed=3,
+                               rng="batched", max_capsules=max_caps, max_spheres=max_sph, current_mu=float(gs[0]["ep_current"][0, 0]),
+                               vehicles=vehicles, threads_per_group=threads_per_group)
+        inp = H.interleaved_teacher_forced_inputs(gs, T, max_caps, max_sph)
+    try:
+        if threads_per_group:
+            assert env.threads_in_use == threads_per_group
         H.load_teacher_forced(env, inp)
         dev = torch.device("cuda", env.device)
         n = env.n_observations
