@@ -109,6 +109,15 @@ class PolicyDesc(C.Structure):
     ]
 
 
+class CollectIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_steps", C.c_int32),
+        ("rows_in", C.c_void_p), ("rows_out", C.c_void_p), ("actions_out", C.c_void_p), ("terminal_obs", C.c_void_p),
+        ("log_prob", C.c_void_p), ("values", C.c_void_p), ("advantages", C.c_void_p), ("returns", C.c_void_p),
+        ("t0", C.c_uint64), ("stochastic", C.c_int32), ("gamma", C.c_float), ("gae_lambda", C.c_float), ("reserved", C.c_int32),
+    ]
+
+
 # every symbol include/dockauv.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("dockauv_abi_version", C.c_int, []),
@@ -150,6 +159,13 @@ SYMBOLS = [
     ("dockauv_policy_forward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]),
     ("dockauv_rollout", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                   C.c_uint64, C.c_int, C.c_void_p]),
+    ("dockauv_value_create", C.c_int, [C.c_void_p, C.POINTER(PolicyDesc), C.POINTER(C.c_void_p)]),
+    ("dockauv_value_forward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    ("dockauv_policy_forward_logp", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
+                                              C.c_void_p]),
+    ("dockauv_gae", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                              C.c_void_p]),
+    ("dockauv_collect", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CollectIO), C.c_void_p]),
 ]
 
 _lib: Optional[C.CDLL] = None

@@ -1175,7 +1175,9 @@ struct dockauv_policy_s {
     PolicyShape S{};
     float* packed = nullptr;      // the weights as the kernel reads them (dockauv_device.h: PolicyShape)
     float* raw = nullptr;         // device staging of host arrays: W1 b1 W2 b2 W3 b3 log_std back to back
+    float* log_std = nullptr;     // the raw log_std [DOCKAUV_MAX_U] (the packed image keeps exp(log_std)): read by the log-prob epilogue
     bool has_log_std = false;
+    bool value_role = false;      // a critic (dockauv_value_create): n_out == 1, raw output
     uint64_t seed = 0, env_id_offset = 0;
 };
 
@@ -1225,43 +1227,106 @@ int upload_policy(dockauv_policy p, const dockauv_policy_desc* d, hipStream_t st
     } else {
         size_t off = 0;
         for (int i = 0; i < 7; ++i) {
-            dev[i] = (src[i] && cnt[i]) ? p->raw + off : nullptr;
+            dev[i] = (src[i] && cnt[i] && !(i == 6 && p->value_role)) ? p->raw + off : nullptr;
             if (dev[i]) HIP_TRY(h, hipMemcpyAsync(p->raw + off, src[i], cnt[i] * sizeof(float), hipMemcpyHostToDevice, stream));
             off += cnt[i];
         }
         HIP_TRY(h, hipStreamSynchronize(stream));   // the caller's host arrays are free on return
     }
     if (!S.n_h2) dev[2] = dev[3] = nullptr;
+    if (p->value_role) dev[6] = nullptr;   // (a critic has no exploration noise)
+    if (dev[6]) HIP_TRY(h, hipMemcpyAsync(p->log_std, dev[6], cnt[6] * sizeof(float), hipMemcpyDeviceToDevice, stream));
     const PolicyRaw raw{dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6]};
     const int rc = launch_policy_pack(S, raw, p->packed, stream);
     if (rc != 0) return fail(h, DOCKAUV_E_HIP, "policy weight packing launch failed: %s", hipGetErrorString((hipError_t)rc));
-    p->has_log_std = d->log_std != nullptr;
+    p->has_log_std = dev[6] != nullptr;
     p->seed = d->seed;
     p->env_id_offset = d->env_id_offset;
     return 0;
 }
 
-int policy_forward(dockauv_handle h, dockauv_policy p, const float* rows, float* actions, uint64_t t, int stochastic, hipStream_t stream) {
+int policy_forward(dockauv_handle h, dockauv_policy p, const float* rows, float* actions, uint64_t t, int stochastic, hipStream_t stream,
+                   float* log_prob = nullptr) {
     const int rc = launch_policy_forward(p->S, p->packed, rows, actions, h->cfg.n_envs, h->n_obs + 2, h->n_u_max, t,
-                                         (stochastic && p->has_log_std) ? 1 : 0, p->seed, p->env_id_offset, stream);
+                                         (stochastic && p->has_log_std) ? 1 : 0, p->seed, p->env_id_offset, stream, log_prob,
+                                         log_prob ? p->log_std : nullptr);
     if (rc != 0) return fail(h, DOCKAUV_E_HIP, "policy kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     h->last_stream = stream;
     return 0;
 }
 
-}  // namespace
+// V(rows[r]) for n_rows packed rows -> values[r]: the critic's kernel with one output unit and an action stride of 1
+int value_forward(dockauv_handle h, dockauv_policy c, const float* rows, long long n_rows, float* values, hipStream_t stream) {
+    const int rc = launch_policy_forward(c->S, c->packed, rows, values, (long)n_rows, h->n_obs + 2, 1, 0, 0, 0, 0, stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "value kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = stream;
+    return 0;
+}
 
-extern "C" {
+// what the actor argument of `fn` must be: of this handle, not a critic; with want_logp also a log_std and a raw output
+int check_actor(dockauv_handle h, dockauv_policy p, const char* fn, bool want_logp) {
+    if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "%s: the policy was created for another handle", fn);
+    if (p->value_role) return fail(h, DOCKAUV_E_INVALID, "%s: the policy is a critic (dockauv_value_create), an actor is needed", fn);
+    if (want_logp && !p->has_log_std) return fail(h, DOCKAUV_E_INVALID, "%s: log_prob needs a policy with a log_std", fn);
+    if (want_logp && p->S.out_act == DOCKAUV_ACT_TANH)
+        return fail(h, DOCKAUV_E_INVALID, "%s: log_prob of a policy with out_act DOCKAUV_ACT_TANH needs the squashing correction, "
+                    "which stays with the learner", fn);
+    return 0;
+}
 
-int dockauv_policy_create(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out) {
-    if (!d || !out) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_create: null argument");
+int check_critic(dockauv_handle h, dockauv_policy c, const char* fn) {
+    if (c->h != h) return fail(h, DOCKAUV_E_INVALID, "%s: the critic was created for another handle", fn);
+    if (!c->value_role) return fail(h, DOCKAUV_E_INVALID, "%s: the critic argument is an actor (dockauv_policy_create), not a critic", fn);
+    return 0;
+}
+
+int check_gae_factors(dockauv_handle h, const char* fn, float gamma, float gae_lambda) {
+    if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail(h, DOCKAUV_E_INVALID, "%s: gamma %g outside [0, 1]", fn, (double)gamma);
+    if (!(gae_lambda >= 0.0f && gae_lambda <= 1.0f)) return fail(h, DOCKAUV_E_INVALID, "%s: gae_lambda %g outside [0, 1]", fn, (double)gae_lambda);
+    return 0;
+}
+
+// the launches of dockauv_rollout; log_prob (nullable, [n_steps][n_envs]): the actor in its log-prob form
+int queue_rollout(dockauv_handle h, dockauv_policy p, const float* rows_in, float* rows_out, float* actions_out, float* terminal_obs,
+                  float* log_prob, int n_steps, uint64_t t0, int stochastic, hipStream_t stream) {
+    const size_t N = (size_t)h->cfg.n_envs, row = (size_t)h->n_obs + 2;
+    for (int k = 0; k < n_steps; ++k) {
+        const float* rows = k == 0 ? rows_in : rows_out + (size_t)(k - 1) * N * row;
+        float* act = actions_out + (size_t)k * N * h->n_u_max;
+        int rc = policy_forward(h, p, rows, act, t0 + (uint64_t)k, stochastic, stream, log_prob ? log_prob + (size_t)k * N : nullptr);
+        if (rc) return rc;
+        dockauv_step_io io{};
+        io.actions = act;
+        io.obs = rows_out + (size_t)k * N * row;
+        io.terminal_obs = terminal_obs ? terminal_obs + (size_t)k * N * h->n_obs : nullptr;
+        io.pack_reward_done = 1;
+        if ((rc = launch(h, &io, stream)) != 0) return rc;
+    }
+    return 0;
+}
+
+int gae(dockauv_handle h, const float* rows_out, const float* values, int n_steps, float gamma, float gae_lambda, float* advantages,
+        float* returns, hipStream_t stream) {
+    const int rc = launch_gae(rows_out, values, advantages, returns, n_steps, h->cfg.n_envs, h->n_obs, gamma, gae_lambda, stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "GAE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = stream;
+    return 0;
+}
+
+// actor (dockauv_policy_create) or critic (dockauv_value_create): `fn` names the entry point in the messages
+int create_policy(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out, bool value_role, const char* fn) {
+    if (!d || !out) return fail(h, DOCKAUV_E_INVALID, "%s: null argument", fn);
     *out = nullptr;
     int rc = validate_policy_desc(h, d, nullptr);
     if (rc) return rc;
-    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_create: null handle");
-    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_create: the policy kernel is float32; the handle's precision is DOCKAUV_F64");
+    if (value_role && d->n_out != 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_out: %d, a critic has one output", d->n_out);
+    if (value_role && d->out_act != DOCKAUV_ACT_NONE)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.out_act: %d, a critic's output is raw (DOCKAUV_ACT_NONE)", d->out_act);
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
+    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "%s: the policy kernel is float32; the handle's precision is DOCKAUV_F64", fn);
     if (d->n_in != h->n_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_in: %d, the handle's n_obs is %d", d->n_in, h->n_obs);
-    if (d->n_out != h->n_u_max) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_out: %d, the handle's n_u is %d", d->n_out, h->n_u_max);
+    if (!value_role && d->n_out != h->n_u_max)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_out: %d, the handle's n_u is %d", d->n_out, h->n_u_max);
     PolicyShape S{};
     S.n_in = d->n_in;
     S.n_h1 = d->n_hidden[0];
@@ -1277,10 +1342,13 @@ int dockauv_policy_create(dockauv_handle h, const dockauv_policy_desc* d, dockau
     dockauv_policy p = new dockauv_policy_s();
     p->h = h;
     p->S = S;
+    p->value_role = value_role;
     const int n_last = S.n_h2 ? S.n_h2 : S.n_h1;
     const size_t raw_floats = (size_t)S.n_h1 * S.n_in + S.n_h1 + (size_t)S.n_h2 * S.n_h1 + S.n_h2 + (size_t)S.n_out * n_last + 2 * (size_t)S.n_out;
     hipError_t e = hipMalloc((void**)&p->packed, (size_t)S.total * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void**)&p->raw, raw_floats * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->log_std, DOCKAUV_MAX_U * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(p->log_std, 0, DOCKAUV_MAX_U * sizeof(float));
     if (e != hipSuccess) {
         dockauv_policy_destroy(p);
         return fail(h, DOCKAUV_E_HIP, "policy buffers: %s", hipGetErrorString(e));
@@ -1291,6 +1359,18 @@ int dockauv_policy_create(dockauv_handle h, const dockauv_policy_desc* d, dockau
     }
     *out = p;
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dockauv_policy_create(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out) {
+    return create_policy(h, d, out, false, "dockauv_policy_create");
+}
+
+int dockauv_value_create(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out) {
+    return create_policy(h, d, out, true, "dockauv_value_create");
 }
 
 int dockauv_policy_load(dockauv_policy p, const dockauv_policy_desc* d, void* hip_stream) {
@@ -1308,6 +1388,7 @@ int dockauv_policy_destroy(dockauv_policy p) {
     (void)hipDeviceSynchronize();
     if (p->packed) (void)hipFree(p->packed);
     if (p->raw) (void)hipFree(p->raw);
+    if (p->log_std) (void)hipFree(p->log_std);
     delete p;
     return 0;
 }
@@ -1316,34 +1397,87 @@ int dockauv_policy_forward(dockauv_handle h, dockauv_policy p, const float* rows
                            void* hip_stream) {
     if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_forward: null handle");
     if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward: null policy");
-    if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward: the policy was created for another handle");
+    if (int rc = check_actor(h, p, "dockauv_policy_forward", false)) return rc;
     if (!rows || !actions) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward: rows/actions must not be NULL");
     HIP_TRY(h, hipSetDevice(h->device));
     return policy_forward(h, p, rows, actions, t, stochastic, (hipStream_t)hip_stream);
+}
+
+int dockauv_policy_forward_logp(dockauv_handle h, dockauv_policy p, const float* rows, float* actions, float* log_prob, uint64_t t,
+                                int stochastic, void* hip_stream) {
+    if (!rows || !actions || !log_prob) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_logp: rows/actions/log_prob must not be NULL");
+    if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_logp: null policy");
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_forward_logp: null handle");
+    if (int rc = check_actor(h, p, "dockauv_policy_forward_logp", true)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return policy_forward(h, p, rows, actions, t, stochastic, (hipStream_t)hip_stream, log_prob);
+}
+
+int dockauv_value_forward(dockauv_handle h, dockauv_policy critic, const float* rows, long long n_rows, float* values, void* hip_stream) {
+    if (!rows || !values) return fail(h, DOCKAUV_E_INVALID, "dockauv_value_forward: rows/values must not be NULL");
+    if (n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_value_forward: n_rows %lld must be >= 1", n_rows);
+    if (!critic) return fail(h, DOCKAUV_E_INVALID, "dockauv_value_forward: null critic");
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_value_forward: null handle");
+    if (int rc = check_critic(h, critic, "dockauv_value_forward")) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return value_forward(h, critic, rows, n_rows, values, (hipStream_t)hip_stream);
+}
+
+int dockauv_gae(dockauv_handle h, const float* rows_out, const float* values, int n_steps, float gamma, float gae_lambda,
+                float* advantages, float* returns, void* hip_stream) {
+    if (!rows_out || !values || !advantages || !returns)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_gae: rows_out/values/advantages/returns must not be NULL");
+    if (n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_gae: n_steps %d must be >= 1", n_steps);
+    if (int rc = check_gae_factors(h, "dockauv_gae", gamma, gae_lambda)) return rc;
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_gae: null handle");
+    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "dockauv_gae: the packed rows are float32; the handle's precision is DOCKAUV_F64");
+    HIP_TRY(h, hipSetDevice(h->device));
+    return gae(h, rows_out, values, n_steps, gamma, gae_lambda, advantages, returns, (hipStream_t)hip_stream);
+}
+
+int dockauv_collect(dockauv_handle h, dockauv_policy actor, dockauv_policy critic, const dockauv_collect_io* io, void* hip_stream) {
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect: io is NULL");
+    if (io->struct_size != sizeof(dockauv_collect_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_collect_io));
+    if (io->n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.n_steps: %d must be >= 1", io->n_steps);
+    if (!io->rows_in || !io->rows_out || !io->actions_out)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: rows_in/rows_out/actions_out must not be NULL");
+    if (critic && (!io->values || !io->advantages || !io->returns))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: values/advantages/returns must not be NULL with a critic");
+    if (!critic && (io->values || io->advantages || io->returns))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: values/advantages/returns must be NULL without a critic");
+    if (critic)
+        if (int rc = check_gae_factors(h, "dockauv_collect_io", io->gamma, io->gae_lambda)) return rc;
+    if (!actor) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect: null actor");
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_collect: null handle");
+    if (int rc = check_actor(h, actor, "dockauv_collect", io->log_prob != nullptr)) return rc;
+    if (critic)
+        if (int rc = check_critic(h, critic, "dockauv_collect")) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int K = io->n_steps;
+    int rc = queue_rollout(h, actor, io->rows_in, io->rows_out, io->actions_out, io->terminal_obs, io->log_prob, K, io->t0,
+                           io->stochastic, stream);
+    if (rc) return rc;
+    if (critic) {
+        const size_t N = (size_t)h->cfg.n_envs;
+        if ((rc = value_forward(h, critic, io->rows_in, (long long)N, io->values, stream)) != 0) return rc;
+        if ((rc = value_forward(h, critic, io->rows_out, (long long)K * (long long)N, io->values + N, stream)) != 0) return rc;
+        if ((rc = gae(h, io->rows_out, io->values, K, io->gamma, io->gae_lambda, io->advantages, io->returns, stream)) != 0) return rc;
+    }
+    return check_status(h);   // (what dockauv_poll_status looks at: no synchronisation)
 }
 
 int dockauv_rollout(dockauv_handle h, dockauv_policy p, const float* rows_in, float* rows_out, float* actions_out,
                     float* terminal_obs, int n_steps, uint64_t t0, int stochastic, void* hip_stream) {
     if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_rollout: null handle");
     if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: null policy");
-    if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: the policy was created for another handle");
+    if (int rc = check_actor(h, p, "dockauv_rollout", false)) return rc;
     if (n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: n_steps %d must be >= 1", n_steps);
     if (!rows_in || !rows_out || !actions_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: rows_in/rows_out/actions_out must not be NULL");
     HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const size_t N = (size_t)h->cfg.n_envs, row = (size_t)h->n_obs + 2;
-    for (int k = 0; k < n_steps; ++k) {
-        const float* rows = k == 0 ? rows_in : rows_out + (size_t)(k - 1) * N * row;
-        float* act = actions_out + (size_t)k * N * h->n_u_max;
-        int rc = policy_forward(h, p, rows, act, t0 + (uint64_t)k, stochastic, stream);
-        if (rc) return rc;
-        dockauv_step_io io{};
-        io.actions = act;
-        io.obs = rows_out + (size_t)k * N * row;
-        io.terminal_obs = terminal_obs ? terminal_obs + (size_t)k * N * h->n_obs : nullptr;
-        io.pack_reward_done = 1;
-        if ((rc = launch(h, &io, stream)) != 0) return rc;
-    }
+    if (int rc = queue_rollout(h, p, rows_in, rows_out, actions_out, terminal_obs, nullptr, n_steps, t0, stochastic, (hipStream_t)hip_stream))
+        return rc;
     return check_status(h);   // (what dockauv_poll_status looks at: no synchronisation)
 }
 

@@ -299,10 +299,21 @@ struct PolicyRaw {   // the caller's arrays, device pointers (row-major [out][in
 int launch_policy_pack(const PolicyShape& s, const PolicyRaw& raw, float* packed, void* stream);
 // actions[i][0 .. n_out) of env rows i < n (rows: [n][row_stride], only the first n_in columns are read; actions:
 // [n][act_stride]); stochastic != 0 adds std[j] * N(0, 1) of Philox counter (env_id_offset + i, t, j, 2), key = seed,
-// before the output activation.  Returns a hipError_t as int.
-int launch_policy_forward(const PolicyShape& s, const float* packed, const float* rows, float* actions, int n, int row_stride,
+// before the output activation.  log_prob (nullable, [n]) with log_std ([n_out], the raw values, device memory): the
+// log-probability of the actions before the output activation, log_prob[i] = sum_j fmaf(-0.5f * z_ij, z_ij, -(log_std[j] +
+// log(2 pi) / 2)) summed over j = 0..3 and j = 4..7 separately, then (first sum) + (second sum); z = 0 when not stochastic.
+// Returns a hipError_t as int.
+int launch_policy_forward(const PolicyShape& s, const float* packed, const float* rows, float* actions, long n, int row_stride,
                           int act_stride, unsigned long long t, int stochastic, unsigned long long seed,
-                          unsigned long long env_id_offset, void* stream);
+                          unsigned long long env_id_offset, void* stream, float* log_prob = nullptr,
+                          const float* log_std = nullptr);
+
+// ------------------------------------------------------------------------------------------ GAE (dockauv_collect.hip)
+// SB3's compute_returns_and_advantage over packed rows: rows [K][N][row_stride] with the reward in column n_obs and done in
+// column n_obs + 1 (the observation columns are never read), values [K + 1][N], advantages / returns [K][N]; one lane per
+// env walks k = K - 1 .. 0.  The float32 expression order is stated in include/dockauv.h (dockauv_gae).  Returns a hipError_t.
+int launch_gae(const float* rows, const float* values, float* advantages, float* returns, int n_steps, int n_envs, int n_obs,
+               float gamma, float gae_lambda, void* stream);
 
 #ifdef DOCKAUV_STAMPS
 int read_stamps(unsigned long long* out);   // diagnostic build only

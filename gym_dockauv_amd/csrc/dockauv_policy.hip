@@ -16,7 +16,12 @@
 //   * every pre-activation is one accumulator chain that starts from the bias and takes its k steps in an order fixed by
 //     the shape alone: an env's action depends on its row and the weights, not on n, its position or the grid;
 //   * the actions (<= 8) of an env sit in registers 0..3 of the two lane halves; exploration noise, output activation and
-//     the store happen there.
+//     the store happen there; so does the log-probability of the drawn actions (launch_policy_forward: log_prob), summed per
+//     lane half and exchanged once between the halves.
+// policy_mlp_kernel and policy_logp_kernel (the same with the log-probability epilogue) share the tile body.  The value launch
+// (dockauv_value_forward, any number of rows) is policy_mlp_kernel with one output unit.  A resident grid whose waves loop over
+// the tiles -- the weights staged once per resident group, not once per 128 rows -- was built and measured for it: not reliably
+// faster (profiles/collect/tile_loop_experiment.txt), so it is not here.
 // Instantiated per (tiles of hidden layer 1, tiles of hidden layer 2) so that every accumulator index is a constant.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -35,7 +40,10 @@ struct PolicyArgs {
     const float* packed;
     const float* rows;
     float* actions;
-    int n, row_stride, act_stride, stochastic;
+    float* log_prob;                   // nullable [n]: sum_j (-z_ij^2 / 2 - log_std[j] - log(2 pi) / 2)
+    const float* log_std;              // [n_out] raw log_std (read with log_prob only; the LDS image keeps exp(log_std))
+    long n;
+    int row_stride, act_stride, stochastic;
     unsigned int t_lo;                 // t mod 2^32
     unsigned int env_off_lo;           // env_id_offset mod 2^32 (the counter word is 32 bits wide)
     unsigned long long seed;
@@ -93,21 +101,22 @@ __device__ __forceinline__ void dense_(f32x16 (&out)[MO], const f32x16 (&in)[MI]
                 out[mo] = __builtin_amdgcn_mfma_f32_32x32x2f32(lds_w[((mi * 16 + r) * MO + mo) * 64 + lane], in[mi][r], out[mo], 0, 0, 0);
 }
 
+constexpr float kHalfLog2Pi = 0.91893853320467274f;   // log(2 pi) / 2
 constexpr int kChunk = 16;   // layer-1 k steps whose row words are requested together
 
-template <int MT1, int MT2>
-__global__ __launch_bounds__(kPolThreads) void policy_mlp_kernel(const PolicyArgs a) {
-    extern __shared__ float lds[];
-    const PolicyShape& S = a.S;
-    {
-        const float4* src = reinterpret_cast<const float4*>(a.packed);
-        float4* dst = reinterpret_cast<float4*>(lds);
-        for (int i = threadIdx.x; i < S.total / 4; i += kPolThreads) dst[i] = src[i];
-    }
+// the packed weights -> LDS, all threads of the group; the barrier behind it is the kernel's only one
+__device__ __forceinline__ void stage_weights_(const PolicyArgs& a, float* lds) {
+    const float4* src = reinterpret_cast<const float4*>(a.packed);
+    float4* dst = reinterpret_cast<float4*>(lds);
+    for (int i = threadIdx.x; i < a.S.total / 4; i += kPolThreads) dst[i] = src[i];
     __syncthreads();
+}
+
+// one tile of 32 envs through all layers, by one wave (tile * 32 < a.n); LOGP: also a.log_prob
+template <int MT1, int MT2, bool LOGP>
+__device__ __forceinline__ void policy_tile_(const PolicyArgs& a, const float* lds, long tile) {
+    const PolicyShape& S = a.S;
     const int lane = threadIdx.x & 63, half = lane >> 5;
-    const long tile = (long)blockIdx.x * (kPolThreads / 64) + (threadIdx.x >> 6);
-    if (tile * 32 >= a.n) return;                       // (no barrier below)
     const long env = tile * 32 + (lane & 31);
     const bool live = env < a.n;                        // tail: rows >= n are neither read nor written
     const float* row = a.rows + (live ? env : 0) * (long)a.row_stride;
@@ -148,16 +157,50 @@ __global__ __launch_bounds__(kPolThreads) void policy_mlp_kernel(const PolicyArg
 
     // ---- actions: unit j = 4 half + r sits in register r < 4
     float* dst = a.actions + (live ? env : 0) * (long)a.act_stride;
+    [[maybe_unused]] float lp = 0.0f;                   // this lane half's part of the log-probability, in the order of r
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int j = 4 * half + r;
         if (j < S.n_out) {
             float v = out[0][r];
-            if (a.stochastic) v = fmaf(lds[S.off_std + j], policy_normal_(a.seed, a.env_off_lo + (uint32_t)env, a.t_lo, (uint32_t)j), v);
+            float z = 0.0f;
+            if (a.stochastic) {
+                z = policy_normal_(a.seed, a.env_off_lo + (uint32_t)env, a.t_lo, (uint32_t)j);
+                v = fmaf(lds[S.off_std + j], z, v);
+            }
             v = act_(v, S.out_act);
             if (live) dst[j] = v;
+            if constexpr (LOGP) lp += fmaf(-0.5f * z, z, -(a.log_std[j] + kHalfLog2Pi));
         }
     }
+    if constexpr (LOGP) {
+        // lanes l and l ^ 32 hold the two halves of one env: v_permlane32_swap hands lanes 0..31 (second result) what lanes
+        // 32..63 hold; the lower lane adds (actions 0..3) + (actions 4..7) and stores
+        const unsigned int bits = __float_as_uint(lp);
+        const auto sw = __builtin_amdgcn_permlane32_swap(bits, bits, false, false);
+        const float total = lp + __uint_as_float(sw[1]);
+        if (live && half == 0) a.log_prob[env] = total;
+    }
+}
+
+template <int MT1, int MT2>
+__global__ __launch_bounds__(kPolThreads) void policy_mlp_kernel(const PolicyArgs a) {
+    extern __shared__ float lds[];
+    stage_weights_(a, lds);
+    const long tile = (long)blockIdx.x * (kPolThreads / 64) + (threadIdx.x >> 6);
+    if (tile * 32 >= a.n) return;                       // (no barrier below)
+    policy_tile_<MT1, MT2, false>(a, lds, tile);
+}
+
+// the same with the log-probability epilogue (dockauv_policy_forward_logp): a kernel of its own, so that the plain actor
+// keeps its registers (the epilogue costs <3, 3> its fourth wave per SIMD)
+template <int MT1, int MT2>
+__global__ __launch_bounds__(kPolThreads) void policy_logp_kernel(const PolicyArgs a) {
+    extern __shared__ float lds[];
+    stage_weights_(a, lds);
+    const long tile = (long)blockIdx.x * (kPolThreads / 64) + (threadIdx.x >> 6);
+    if (tile * 32 >= a.n) return;                       // (no barrier below)
+    policy_tile_<MT1, MT2, true>(a, lds, tile);
 }
 
 struct PackArgs {
@@ -204,16 +247,17 @@ __global__ void policy_pack_kernel(const PackArgs a) {
 
 template <int MT1, int MT2>
 int launch_forward_(const PolicyArgs& a, size_t lds, hipStream_t stream) {
+    const long tiles = ((long)a.n + 31) / 32;
+    const long groups = (tiles + kPolThreads / 64 - 1) / (kPolThreads / 64);
+    void (*kernel)(const PolicyArgs) = a.log_prob ? policy_logp_kernel<MT1, MT2> : policy_mlp_kernel<MT1, MT2>;
+    if (groups > 0x7fffffffL) return (int)hipErrorInvalidValue;
     if (lds > 64 * 1024) {
         // more than 64 KiB of LDS per group must be requested explicitly; the attribute belongs to the (device, function)
         // pair: set on the launch path, as the step kernels do
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&policy_mlp_kernel<MT1, MT2>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
     }
-    const long tiles = ((long)a.n + 31) / 32;
-    const long groups = (tiles + kPolThreads / 64 - 1) / (kPolThreads / 64);
-    hipLaunchKernelGGL((policy_mlp_kernel<MT1, MT2>), dim3((unsigned)groups), dim3(kPolThreads), lds, stream, a);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(kPolThreads), lds, stream, a);
     return (int)hipGetLastError();
 }
 
@@ -237,14 +281,16 @@ int launch_policy_pack(const PolicyShape& s, const PolicyRaw& raw, float* packed
     return (int)hipGetLastError();
 }
 
-int launch_policy_forward(const PolicyShape& s, const float* packed, const float* rows, float* actions, int n, int row_stride,
+int launch_policy_forward(const PolicyShape& s, const float* packed, const float* rows, float* actions, long n, int row_stride,
                           int act_stride, unsigned long long t, int stochastic, unsigned long long seed,
-                          unsigned long long env_id_offset, void* stream) {
+                          unsigned long long env_id_offset, void* stream, float* log_prob, const float* log_std) {
     PolicyArgs a;
     a.S = s;
     a.packed = packed;
     a.rows = rows;
     a.actions = actions;
+    a.log_prob = log_prob;
+    a.log_std = log_std;
     a.n = n;
     a.row_stride = row_stride;
     a.act_stride = act_stride;
@@ -253,7 +299,7 @@ int launch_policy_forward(const PolicyShape& s, const float* packed, const float
     a.env_off_lo = (unsigned int)(env_id_offset & 0xffffffffull);
     a.seed = seed;
     const size_t lds = policy_lds_bytes(s);
-    if (n <= 0 || lds > kPolMaxLds) return (int)hipErrorInvalidValue;
+    if (n <= 0 || lds > kPolMaxLds || (log_prob && !log_std)) return (int)hipErrorInvalidValue;
     switch (s.mt1) {
         case 1: return launch_forward_mt1_<1>(a, lds, (hipStream_t)stream);
         case 2: return launch_forward_mt1_<2>(a, lds, (hipStream_t)stream);

@@ -629,8 +629,20 @@ class BatchedDocking3d:
         self._policies = getattr(self, "_policies", []) + [pol]
         return pol
 
+    def make_value(self, mlp):
+        """Put a critic -- an ``MLPPolicy`` with one raw output (``MLPPolicy.value_from_torch``) -- on this handle's device:
+        dockauv_value_create.  ``load_policy`` and ``destroy_policy`` work on what it returns."""
+        from ..policy import DevicePolicy
+        d = mlp.host_desc()
+        ptr = C.c_void_p()
+        rc = self._lib.dockauv_value_create(self._handle, C.byref(d), C.byref(ptr))
+        _capi.check(self._lib, self._handle, rc, "dockauv_value_create")
+        val = DevicePolicy(ptr, mlp, 0, 0, value_role=True)
+        self._policies = getattr(self, "_policies", []) + [val]
+        return val
+
     def load_policy(self, policy, mlp=None, device_ptrs=None, log_std_ptr: int = 0, stream: int = 0) -> None:
-        """New weights of the same shapes: dockauv_policy_load.  Either ``mlp`` (host arrays; the call waits for the copies)
+        """New weights of the same shapes (an actor's or a critic's): dockauv_policy_load.  Either ``mlp`` (host arrays; the call waits for the copies)
         or ``device_ptrs`` = (W1, b1, W2, b2, W3, b3) device addresses of contiguous float32 arrays (W2 / b2 0 with one
         hidden layer) plus ``log_std_ptr``: no host round trip, ordered on ``stream``."""
         if (mlp is None) == (device_ptrs is None):
@@ -645,7 +657,7 @@ class BatchedDocking3d:
             d.seed, d.env_id_offset = policy.seed, policy.env_id_offset
         rc = self._lib.dockauv_policy_load(policy.ptr, C.byref(d), C.c_void_p(stream or None))
         _capi.check(self._lib, self._handle, rc, "dockauv_policy_load")
-        policy.has_log_std = bool(d.log_std)
+        policy.has_log_std = bool(d.log_std) and not getattr(policy, "value_role", False)
 
     def policy_forward_device(self, policy, rows_ptr: int, actions_ptr: int, t: int = 0, stochastic: bool = False,
                               stream: int = 0) -> None:
@@ -663,6 +675,50 @@ class BatchedDocking3d:
                                        C.c_void_p(actions_out_ptr or None), C.c_void_p(terminal_obs_ptr or None), int(n_steps),
                                        int(t0), 1 if stochastic else 0, C.c_void_p(stream or None))
         _capi.check(self._lib, self._handle, rc, "dockauv_rollout")
+
+    def policy_forward_logp_device(self, policy, rows_ptr: int, actions_ptr: int, log_prob_ptr: int, t: int = 0,
+                                   stochastic: bool = False, stream: int = 0) -> None:
+        """policy_forward_device that also writes log_prob float32 [N]: the log-probability of the drawn actions
+        (dockauv_policy_forward_logp; needs a log_std and a raw output)."""
+        rc = self._lib.dockauv_policy_forward_logp(self._handle, policy.ptr, C.c_void_p(rows_ptr or None), C.c_void_p(actions_ptr or None),
+                                                   C.c_void_p(log_prob_ptr or None), int(t), 1 if stochastic else 0,
+                                                   C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_policy_forward_logp")
+
+    def value_forward_device(self, value, rows_ptr: int, n_rows: int, values_ptr: int, stream: int = 0) -> None:
+        """Asynchronous critic forward on device pointers: values float32 [n_rows] of n_rows packed rows [n_obs + 2], any
+        number of them (dockauv_value_forward)."""
+        rc = self._lib.dockauv_value_forward(self._handle, value.ptr, C.c_void_p(rows_ptr or None), int(n_rows),
+                                             C.c_void_p(values_ptr or None), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_value_forward")
+
+    def gae_device(self, rows_out_ptr: int, values_ptr: int, n_steps: int, gamma: float, gae_lambda: float, advantages_ptr: int,
+                   returns_ptr: int, stream: int = 0) -> None:
+        """GAE over the rows of a rollout (dockauv_gae): rows_out [K][N][n_obs + 2], values [K + 1][N] -> advantages, returns
+        [K][N]; asynchronous."""
+        rc = self._lib.dockauv_gae(self._handle, C.c_void_p(rows_out_ptr or None), C.c_void_p(values_ptr or None), int(n_steps),
+                                   float(gamma), float(gae_lambda), C.c_void_p(advantages_ptr or None), C.c_void_p(returns_ptr or None),
+                                   C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_gae")
+
+    def collect_device(self, policy, value, rows_in_ptr: int, rows_out_ptr: int, actions_out_ptr: int, n_steps: int,
+                       gamma: float = 0.99, gae_lambda: float = 0.95, t0: int = 0, stochastic: bool = True, stream: int = 0,
+                       terminal_obs_ptr: int = 0, log_prob_ptr: int = 0, values_ptr: int = 0, advantages_ptr: int = 0,
+                       returns_ptr: int = 0) -> None:
+        """One PPO iteration's collection queued by one host call (dockauv_collect): the rollout (log_prob [K][N] when asked
+        for), V of the K + 1 observation sets -> values [K + 1][N], GAE -> advantages, returns [K][N].  ``value`` None: rollout
+        and log-probabilities only.  Asynchronous; raises like poll_status()."""
+        io = _capi.CollectIO()
+        io.struct_size = C.sizeof(_capi.CollectIO)
+        io.n_steps = int(n_steps)
+        io.rows_in, io.rows_out, io.actions_out = rows_in_ptr or None, rows_out_ptr or None, actions_out_ptr or None
+        io.terminal_obs, io.log_prob = terminal_obs_ptr or None, log_prob_ptr or None
+        io.values, io.advantages, io.returns = values_ptr or None, advantages_ptr or None, returns_ptr or None
+        io.t0, io.stochastic = int(t0), 1 if stochastic else 0
+        io.gamma, io.gae_lambda = float(gamma), float(gae_lambda)
+        rc = self._lib.dockauv_collect(self._handle, policy.ptr, value.ptr if value is not None else None, C.byref(io),
+                                       C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_collect")
 
     def destroy_policy(self, policy) -> None:
         if policy.ptr is not None and policy.ptr.value:

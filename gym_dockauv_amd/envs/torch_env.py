@@ -15,10 +15,16 @@ Here the same loop is::
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Optional
 
+from .. import _capi
 from ..config.env_config import BASE_CONFIG
 from .batched import BatchedDocking3d
+
+
+# what TorchDocking3d.collect returns: views of buffers the env owns
+Collected = namedtuple("Collected", ["obs", "actions", "reward", "done", "log_prob", "values", "advantages", "returns"])
 
 
 class TorchDocking3d:
@@ -48,6 +54,7 @@ class TorchDocking3d:
         self._t = 0
         self._last_rows = None
         self._rollout_bufs = {}
+        self._collect_bufs = {}
         self.rollout_terminal_observation = None
         # mixed batches built with sort_vehicles=True: row j of every tensor handed in / out belongs to the caller's env
         # perm[j] (kind-sorted on the device, the caller's order within a kind); identity otherwise
@@ -90,8 +97,12 @@ class TorchDocking3d:
         """The on-device policy of an ``MLPPolicy`` (gym_dockauv_amd/policy.py) for ``rollout``."""
         return self.batch.make_policy(mlp, seed=seed)
 
+    def make_value(self, mlp):
+        """The on-device critic of an ``MLPPolicy`` with one raw output (``MLPPolicy.value_from_torch``) for ``collect``."""
+        return self.batch.make_value(mlp)
+
     def load_policy(self, policy, module_or_tensors, log_std=None) -> None:
-        """New weights from DEVICE tensors, without a host copy and ordered on the current stream: an ``nn.Sequential`` whose
+        """New weights (an actor's or a critic's) from DEVICE tensors, without a host copy and ordered on the current stream: an ``nn.Sequential`` whose
         Linear layers live on this device, or a sequence (W1, b1[, W2, b2], W3, b3) of contiguous float32 tensors;
         ``log_std``: device tensor [n_u] or None.  The tensors are read when the copy runs on the stream."""
         torch = self.torch
@@ -148,6 +159,46 @@ class TorchDocking3d:
         self._last_rows = rows[K - 1]
         self.rollout_terminal_observation = term if want_terminal_obs else None
         return rows[:, :, : self.n_obs], acts, rows[:, :, self.n_obs], rows[:, :, self.n_obs + 1] > 0.5
+
+    def collect(self, policy, value, n_steps: int, gamma: float, gae_lambda: float, stochastic: bool = True,
+                want_terminal_obs: bool = False):
+        """One PPO iteration's collection queued by ONE host call (dockauv_collect) on the current stream: ``rollout`` plus
+        log pi(a|s), V(s) of the K + 1 observation sets and GAE.  Continues the trajectory exactly as ``rollout`` does.  Returns
+        a ``Collected`` named tuple of views of buffers the env owns (reused by the next ``collect`` of the same K):
+        obs [K + 1, N, n_obs] (obs[k], k < K: what the actor saw at step k; obs[K]: the last observation), actions [K, N, n_u],
+        reward [K, N], done [K, N] bool (of step k), log_prob [K, N] (None for a policy without log_std or with a tanh output,
+        whose log-probability the library does not compute), values [K + 1, N], advantages [K, N], returns [K, N] (None with
+        ``value`` None: rollout and log-probabilities only)."""
+        torch = self.torch
+        K = int(n_steps)
+        if K < 1:
+            raise ValueError("n_steps must be >= 1")
+        N = self.num_envs
+        bufs = self._collect_bufs.get(K)
+        if bufs is None:
+            z = lambda *shape: torch.zeros(shape, device=self.device, dtype=torch.float32)
+            bufs = self._collect_bufs[K] = dict(rows=z(K + 1, N, self.n_obs + 2), acts=z(K, N, self.n_u), logp=z(K, N),
+                                                values=z(K + 1, N), adv=z(K, N), ret=z(K, N), term=None)
+        if want_terminal_obs and bufs["term"] is None:
+            bufs["term"] = torch.zeros((K, N, self.n_obs), device=self.device, dtype=torch.float32)
+        rows, term = bufs["rows"], bufs["term"] if want_terminal_obs else None
+        # rows[0]: a copy of the trajectory's last rows (what the actor reads at step 0), so that obs[0 .. K] is one view
+        cur = self._last_rows if self._last_rows is not None else self._packed[self._i % len(self._packed)]
+        rows[0].copy_(cur)
+        has_v = value is not None
+        values, adv, ret = (bufs["values"], bufs["adv"], bufs["ret"]) if has_v else (None, None, None)
+        logp = bufs["logp"] if (policy.has_log_std and policy.shape.out_act == _capi.ACT_NONE) else None
+        self.batch.collect_device(policy, value, rows[0].data_ptr(), rows[1].data_ptr(), bufs["acts"].data_ptr(), K, gamma=gamma,
+                                  gae_lambda=gae_lambda, t0=self._t, stochastic=stochastic,
+                                  stream=torch.cuda.current_stream().cuda_stream,
+                                  terminal_obs_ptr=term.data_ptr() if term is not None else 0, log_prob_ptr=0 if logp is None else logp.data_ptr(),
+                                  values_ptr=values.data_ptr() if has_v else 0, advantages_ptr=adv.data_ptr() if has_v else 0,
+                                  returns_ptr=ret.data_ptr() if has_v else 0)
+        self._t += K
+        self._last_rows = rows[K]
+        self.rollout_terminal_observation = term
+        return Collected(rows[:, :, : self.n_obs], bufs["acts"], rows[1:, :, self.n_obs], rows[1:, :, self.n_obs + 1] > 0.5,
+                         logp, values, adv, ret)
 
     @property
     def terminal_observation(self):

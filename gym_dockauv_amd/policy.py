@@ -4,8 +4,10 @@ device by libdockauv's policy kernel (include/dockauv.h: dockauv_policy_*, docka
 is SB3's ``MlpPolicy``, which train.py:64 instantiates and train.py:64-71 / 86-119 query once per step.
 
 ``MLPPolicy`` is a plain host object that holds the arrays; ``BatchedDocking3d.make_policy`` / ``TorchDocking3d.make_policy``
-put it on the device.  ``forward_reference`` and ``normals_reference`` are float64 NumPy statements of what the kernel
-computes (for tests and for callers who want to check a port); they are never used as a compute path.
+put it on the device.  An ``MLPPolicy`` with one raw output is a critic (SB3's ``mlp_extractor.value_net`` + ``value_net``;
+``value_from_torch``, ``make_value``): the PPO collector (dockauv_collect) evaluates it on the rollout's rows.
+``forward_reference``, ``normals_reference``, ``log_prob_reference`` and ``gae_reference`` are float64 NumPy statements of what
+the kernels compute (for tests and for callers who want to check a port); they are never used as a compute path.
 """
 from __future__ import annotations
 
@@ -111,7 +113,56 @@ class MLPPolicy:
             raise ValueError("the activations asked for are not the module's")
         return cls(layers, acts[0], acts[-1], log_std)
 
+    @classmethod
+    def value_from_torch(cls, module_or_state_dict, hidden_act: Optional[str] = None):
+        """The critic: an ``nn.Sequential`` ending in ``Linear(.., 1)``, or an SB3-style state dict with
+        ``mlp_extractor.value_net.{0,2}.*`` and ``value_net.*`` (hidden activation ``hidden_act``, SB3's default: tanh)."""
+        if isinstance(module_or_state_dict, dict) or hasattr(module_or_state_dict, "keys"):
+            sd = module_or_state_dict
+            if "mlp_extractor.value_net.0.weight" not in sd or "value_net.weight" not in sd:
+                raise ValueError("state dict needs mlp_extractor.value_net.0.* and value_net.*")
+            renamed = {}
+            for i in (0, 2):
+                for part in ("weight", "bias"):
+                    k = f"mlp_extractor.value_net.{i}.{part}"
+                    if k in sd:
+                        renamed[f"mlp_extractor.policy_net.{i}.{part}"] = sd[k]
+            renamed["action_net.weight"], renamed["action_net.bias"] = sd["value_net.weight"], sd["value_net.bias"]
+            critic = cls.from_torch(renamed, hidden_act, "none")
+        else:
+            critic = cls.from_torch(module_or_state_dict, hidden_act, "none")
+        if critic.n_out != 1:
+            raise ValueError(f"a critic has one output, this one has {critic.n_out}")
+        return critic
+
     # ------------------------------------------------------------------------------------------ float64 statements
+    @staticmethod
+    def log_prob_reference(z, log_std) -> np.ndarray:
+        """log pi(a|s) of a diagonal Gaussian at a = mean + exp(log_std) z: sum_j (-z_j^2 / 2 - log_std_j - log(2 pi) / 2);
+        z [..., n_out] (zeros: the deterministic action), log_std [n_out].  float64 [...]."""
+        z = np.asarray(z, dtype=np.float64)
+        ls = np.asarray(log_std, dtype=np.float64)
+        return (-0.5 * z * z - ls - 0.5 * np.log(2.0 * np.pi)).sum(axis=-1)
+
+    @staticmethod
+    def gae_reference(reward, done, values, gamma: float, gae_lambda: float):
+        """SB3's RolloutBuffer.compute_returns_and_advantage in float64: reward, done [K, N]; values [K + 1, N] with values[k] =
+        V of the observation step k acted on and values[K] = V of the last one; every done is terminal.  Returns
+        (advantages [K, N], returns [K, N])."""
+        r = np.asarray(reward, dtype=np.float64)
+        nt = 1.0 - (np.asarray(done) > 0.5).astype(np.float64)
+        v = np.asarray(values, dtype=np.float64)
+        K = r.shape[0]
+        if v.shape[0] != K + 1 or nt.shape != r.shape or v.shape[1:] != r.shape[1:]:
+            raise ValueError("reward, done: [K, N]; values: [K + 1, N]")
+        adv = np.zeros_like(r)
+        gae = np.zeros(r.shape[1:], dtype=np.float64)
+        for k in range(K - 1, -1, -1):
+            delta = r[k] + gamma * nt[k] * v[k + 1] - v[k]
+            gae = delta + gamma * gae_lambda * nt[k] * gae
+            adv[k] = gae
+        return adv, adv + v[:K]
+
     def forward_reference(self, obs: np.ndarray, z: Optional[np.ndarray] = None) -> np.ndarray:
         """float64 forward of float32 weights: obs [..., n_in] -> [..., n_out]; ``z`` [..., n_out]: exploration normals,
         added as exp(log_std) * z before the output activation."""
@@ -175,8 +226,9 @@ class MLPPolicy:
 class DevicePolicy:
     """A dockauv_policy of one BatchedDocking3d handle (made by ``make_policy``): the handle plus what a reload needs."""
 
-    def __init__(self, ptr: C.c_void_p, mlp: MLPPolicy, seed: int, env_id_offset: int):
+    def __init__(self, ptr: C.c_void_p, mlp: MLPPolicy, seed: int, env_id_offset: int, value_role: bool = False):
         self.ptr, self.seed, self.env_id_offset = ptr, int(seed), int(env_id_offset)
+        self.value_role = bool(value_role)       # a critic (make_value): dockauv_value_create
         self.shape = mlp.shape_desc()
         self.n_in, self.n_hidden, self.n_out = mlp.n_in, mlp.n_hidden, mlp.n_out
-        self.has_log_std = mlp.log_std is not None
+        self.has_log_std = mlp.log_std is not None and not self.value_role

@@ -340,7 +340,9 @@ int dockauv_step_gather_sequence(dockauv_handle h, const dockauv_step_io* ios, i
  * gfx950 matrix kernel directly on the packed [obs | reward | done] rows the step kernel writes, so that neither Python nor
  * torch nor a graph capture sits between two steps.  Arithmetic is float32 throughout: every pre-activation is one fused
  * multiply-add chain from the bias in a k order fixed by the shapes alone; env i's action depends on row i and the weights
- * only.  A value head, log-probabilities and GAE stay with the learner.
+ * only.  The critic, the log-probabilities of the drawn actions and GAE are further below (dockauv_value_*,
+ * dockauv_policy_forward_logp, dockauv_gae, dockauv_collect): one host call returns everything a PPO update reads; the update
+ * itself stays with the learner.
  */
 #define DOCKAUV_ACT_NONE 0       /* output: raw (PPO; the step kernel clips, objects/auvsim.py:74) */
 #define DOCKAUV_ACT_TANH 1       /* hidden: SB3's default; output: SAC-style squashing */
@@ -388,6 +390,68 @@ int dockauv_policy_forward(dockauv_handle h, dockauv_policy p, const float* rows
  * dockauv_poll_status returns, looked at once after queueing. */
 int dockauv_rollout(dockauv_handle h, dockauv_policy p, const float* rows_in, float* rows_out, float* actions_out,
                     float* terminal_obs, int n_steps, uint64_t t0, int stochastic, void* hip_stream);
+
+/*
+ * The PPO collector: what SB3's collect_rollouts + RolloutBuffer.compute_returns_and_advantage (train.py:64-71; gamma /
+ * gae_lambda of config/DRL_hyperparams.py) hand to the update -- V(s), log pi(a|s), advantages and returns -- computed on the
+ * device from the rollout's own buffers.  All pointers are device pointers, every call is asynchronous on the stream.
+ *
+ * The critic (SB3 MlpPolicy: mlp_extractor.value_net + value_net) is a dockauv_policy with a value role: the same descriptor,
+ * widths (<= 128, one or two hidden layers), packing and upload as the actor, with n_out == 1 and out_act == DOCKAUV_ACT_NONE;
+ * log_std, seed and env_id_offset are ignored.  dockauv_policy_load and dockauv_policy_destroy work on it;
+ * dockauv_policy_forward, dockauv_rollout and every actor argument refuse it, every critic argument refuses an actor.
+ */
+int dockauv_value_create(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out);
+/* values[r] = V(rows[r][0 .. n_obs)) for n_rows packed rows of stride n_obs + 2: any number of rows, not tied to n_envs, so
+ * that the [K][N] rows of a rollout go in one launch (the actor's kernel with one output unit: one group per 128 rows).  A
+ * row's value is a function of the row and the weights only. */
+int dockauv_value_forward(dockauv_handle h, dockauv_policy critic, const float* rows, long long n_rows, float* values,
+                          void* hip_stream);
+/* dockauv_policy_forward that also writes the log-probability of what it drew, log_prob: float32 [n_envs]:
+ *   log_prob[i] = sum_j (-z_ij^2 / 2 - log_std[j] - log(2 pi) / 2),  z the normal the kernel drew (0 with stochastic == 0).
+ * In float32: term_j = fmaf(-0.5f * z, z, -(log_std[j] + 0.918938533f)); (term_0 + .. + term_3) + (term_4 + .. + term_7), each
+ * sum from 0.0f in the order of j.  The actions are bit for bit those of dockauv_policy_forward.  Refused when the policy has
+ * no log_std, and when out_act == DOCKAUV_ACT_TANH: the log-probability of a squashed action needs the correction
+ * -sum_j log(1 - tanh(x_j)^2), which stays with the learner (SAC). */
+int dockauv_policy_forward_logp(dockauv_handle h, dockauv_policy p, const float* rows, float* actions, float* log_prob,
+                                uint64_t t, int stochastic, void* hip_stream);
+/* RolloutBuffer.compute_returns_and_advantage on the rows of a rollout.  rows_out: float32 [n_steps][n_envs][n_obs + 2] (only
+ * the reward and done columns are read); values: float32 [n_steps + 1][n_envs], values[k] = V of the observation the actor saw
+ * at step k, values[n_steps] = V(rows_out[n_steps - 1]); advantages, returns: float32 [n_steps][n_envs].  Per env, backwards
+ * from k = n_steps - 1 with gae = 0, in exactly this float32 order (the library is built with -ffp-contract=on: only the fmaf
+ * written here are fused):
+ *   nt    = done[k] > 0.5f ? 0.0f : 1.0f
+ *   gnt   = gamma * nt
+ *   delta = fmaf(gnt, values[k + 1], reward[k]) - values[k]
+ *   gae   = fmaf((gamma * gae_lambda) * nt, gae, delta)
+ *   advantages[k] = gae;  returns[k] = gae + values[k]
+ * Every done is terminal: the reference's env reports no truncation flag (docking3d.py:630), and the row after a done holds the
+ * reset observation, whose value is masked out by nt.  gamma and gae_lambda must lie in [0, 1]. */
+int dockauv_gae(dockauv_handle h, const float* rows_out, const float* values, int n_steps, float gamma, float gae_lambda,
+                float* advantages, float* returns, void* hip_stream);
+/* One PPO iteration's collection. */
+typedef struct dockauv_collect_io {
+    uint32_t struct_size;          /* sizeof(dockauv_collect_io): ABI check */
+    int32_t n_steps;               /* K >= 1 */
+    const float* rows_in;          /* [n_envs][n_obs + 2]: the rows the actor reads at step 0 */
+    float* rows_out;               /* [K][n_envs][n_obs + 2] */
+    float* actions_out;            /* [K][n_envs][n_u] */
+    float* terminal_obs;           /* nullable [K][n_envs][n_obs] */
+    float* log_prob;               /* nullable [K][n_envs] */
+    float* values;                 /* [K + 1][n_envs]; NULL without a critic, like advantages and returns */
+    float* advantages;             /* [K][n_envs] */
+    float* returns;                /* [K][n_envs] */
+    uint64_t t0;                   /* counter of step 0 (dockauv_rollout) */
+    int32_t stochastic;
+    float gamma, gae_lambda;       /* in [0, 1] */
+    int32_t reserved;
+} dockauv_collect_io;
+/* Queues exactly: the launches of dockauv_rollout (the actor in its dockauv_policy_forward_logp form when io->log_prob is
+ * given, writing log_prob[k]); one value launch on rows_in -> values[0]; one value launch on all of rows_out -> values[1 .. K];
+ * one GAE launch.  critic == NULL: rollout and log-probabilities only (values / advantages / returns must be NULL).  Returns
+ * what dockauv_poll_status returns, looked at once after queueing. */
+int dockauv_collect(dockauv_handle h, dockauv_policy actor, dockauv_policy critic, const dockauv_collect_io* io,
+                    void* hip_stream);
 
 #ifdef __cplusplus
 }
