@@ -118,6 +118,13 @@ class CollectIO(C.Structure):
     ]
 
 
+class PolicyGrads(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved", C.c_uint32),
+        ("dW1", C.c_void_p), ("db1", C.c_void_p), ("dW2", C.c_void_p), ("db2", C.c_void_p), ("dW3", C.c_void_p), ("db3", C.c_void_p),
+    ]
+
+
 # every symbol include/dockauv.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("dockauv_abi_version", C.c_int, []),
@@ -166,6 +173,9 @@ SYMBOLS = [
     ("dockauv_gae", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                               C.c_void_p]),
     ("dockauv_collect", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CollectIO), C.c_void_p]),
+    ("dockauv_policy_forward_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    ("dockauv_policy_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                          C.POINTER(PolicyGrads), C.c_void_p]),
 ]
 
 _lib: Optional[C.CDLL] = None

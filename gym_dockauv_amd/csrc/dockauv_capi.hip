@@ -1179,6 +1179,7 @@ struct dockauv_policy_s {
     bool has_log_std = false;
     bool value_role = false;      // a critic (dockauv_value_create): n_out == 1, raw output
     uint64_t seed = 0, env_id_offset = 0;
+    float* bwd_partial = nullptr; // dockauv_policy_backward's per-group partial sums, allocated by the first backward
 };
 
 namespace {
@@ -1389,6 +1390,7 @@ int dockauv_policy_destroy(dockauv_policy p) {
     if (p->packed) (void)hipFree(p->packed);
     if (p->raw) (void)hipFree(p->raw);
     if (p->log_std) (void)hipFree(p->log_std);
+    if (p->bwd_partial) (void)hipFree(p->bwd_partial);
     delete p;
     return 0;
 }
@@ -1421,6 +1423,50 @@ int dockauv_value_forward(dockauv_handle h, dockauv_policy critic, const float* 
     if (int rc = check_critic(h, critic, "dockauv_value_forward")) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     return value_forward(h, critic, rows, n_rows, values, (hipStream_t)hip_stream);
+}
+
+int dockauv_policy_forward_rows(dockauv_handle h, dockauv_policy p, const float* rows, const int64_t* row_index, long long n_rows,
+                                float* out, void* hip_stream) {
+    if (!rows || !out) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: rows/out must not be NULL");
+    if (n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: n_rows %lld must be >= 1", n_rows);
+    if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: null policy");
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: null handle");
+    if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: the policy was created for another handle");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = launch_policy_forward_rows(p->S, p->packed, rows, (const long long*)row_index, (long)n_rows, h->n_obs + 2, out,
+                                              (hipStream_t)hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "policy rows kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
+    return 0;
+}
+
+int dockauv_policy_backward(dockauv_handle h, dockauv_policy p, const float* rows, const int64_t* row_index, long long n_rows,
+                            const float* grad_out, const dockauv_policy_grads* grads, void* hip_stream) {
+    if (!rows || !grad_out || !grads) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: rows/grad_out/grads must not be NULL");
+    if (grads->struct_size != sizeof(dockauv_policy_grads))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_grads.struct_size: got %u, library has %zu", grads->struct_size, sizeof(dockauv_policy_grads));
+    if (!grads->dW1 || !grads->db1 || !grads->dW3 || !grads->db3)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_grads: dW1/db1/dW3/db3 must not be NULL");
+    if (n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: n_rows %lld must be >= 1", n_rows);
+    if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: null policy");
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_backward: null handle");
+    if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: the policy was created for another handle");
+    if (p->S.n_h2 > 0 && (!grads->dW2 || !grads->db2))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_grads: dW2/db2 are NULL, the policy has two hidden layers");
+    BackwardLayout L;
+    backward_layout(p->S, L);
+    if (backward_lds_bytes(L) > kPolMaxLds)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: the kernel needs %zu B of LDS for n_in %d, n_hidden %d / %d (weights, one "
+                    "pass's rows, activations and deltas), more than the 160 KiB of a group: narrower layers or observations",
+                    backward_lds_bytes(L), p->S.n_in, p->S.n_h1, p->S.n_h2);
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!p->bwd_partial) HIP_TRY(h, hipMalloc((void**)&p->bwd_partial, (size_t)kBwdMaxGroups * L.n_params * sizeof(float)));
+    const PolicyGrads g{grads->dW1, grads->db1, p->S.n_h2 ? grads->dW2 : nullptr, p->S.n_h2 ? grads->db2 : nullptr, grads->dW3, grads->db3};
+    const int rc = launch_policy_backward(p->S, p->packed, rows, (const long long*)row_index, (long)n_rows, h->n_obs + 2, grad_out,
+                                          p->bwd_partial, g, (hipStream_t)hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "policy backward launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
+    return 0;
 }
 
 int dockauv_gae(dockauv_handle h, const float* rows_out, const float* values, int n_steps, float gamma, float gae_lambda,

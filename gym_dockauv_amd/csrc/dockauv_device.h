@@ -307,6 +307,68 @@ int launch_policy_forward(const PolicyShape& s, const float* packed, const float
                           int act_stride, unsigned long long t, int stochastic, unsigned long long seed,
                           unsigned long long env_id_offset, void* stream, float* log_prob = nullptr,
                           const float* log_std = nullptr);
+// out[r][0 .. n_out) = W3 h_last + b3 (before out_act, no noise) of row rows[row_index ? row_index[r] : r], r < n: the tile
+// body of launch_policy_forward with a gathered row, so the same bits.  out: [n][n_out].  Returns a hipError_t as int.
+int launch_policy_forward_rows(const PolicyShape& s, const float* packed, const float* rows, const long long* row_index, long n,
+                               int row_stride, float* out, void* stream);
+
+// ------------------------------------------------------------------------------------------ MLP backward (dockauv_backward.hip)
+// Parameter gradients of the MLP for upstream gradients on its raw output (include/dockauv.h: dockauv_policy_backward).  A
+// group of four waves walks passes of 32 rt rows.  Everything a pass touches lies in LDS as plain row-major matrices with odd
+// strides, so that each is an MFMA A operand (lane = row of the matrix) and a B operand (lane = column) without bank conflicts:
+//   W1 [32 mt1][ws1], W2 [32 mt2][ws2], W3 [8][ws3]   torch.nn.Linear layout, zero-padded (un-permuted from `packed` once per group)
+//   X [2 ks1][rs], G [8][rs]                           the pass's observations and upstream gradients, [column][row of the pass]
+//   H1 [32 mt1][rs], H2 [32 max(mt1, mt2)][rs], D [32 mtl][rs]   activations and deltas, [unit][row]; delta 1 of two layers reuses H2
+//   ACC [slots][4][1024]                               dW1 tiles a wave holds beyond its two register tiles (wide observations)
+// Offsets in floats.  n_params / p_*: one partial (and the reduction's index space): W1 b1 W2 b2 W3 b3 back to back, Linear layout.
+constexpr int kBwdMaxGroups = 256;        // the bounded grid: one resident group per CU
+struct BackwardLayout {
+    int rt, rs, kt1, ws1, ws2, ws3, acc_slots;
+    int off_w1, off_w2, off_w3, off_b1, off_b2, off_x, off_g, off_h1, off_h2, off_d, off_acc, total;
+    int p_w1, p_b1, p_w2, p_b2, p_w3, p_b3, n_params;
+};
+inline void backward_layout(const PolicyShape& s, BackwardLayout& l) {
+    const int mtl = s.mt2 ? s.mt2 : s.mt1, mtmax = s.mt1 > s.mt2 ? s.mt1 : s.mt2;
+    l.rt = mtmax >= 3 ? 1 : (mtmax == 2 ? 2 : 4);
+    l.rs = 32 * l.rt + 1;
+    l.kt1 = (s.n_in + 31) / 32;
+    l.ws1 = 2 * s.ks1 + 1;
+    l.ws2 = 32 * s.mt1 + 1;
+    l.ws3 = 32 * mtl + 1;
+    const int per_wave = (s.mt1 * l.kt1 + 3) / 4;
+    l.acc_slots = per_wave > 2 ? per_wave - 2 : 0;
+    int o = 0;
+    l.off_w1 = o; o += 32 * s.mt1 * l.ws1;
+    l.off_w2 = o; o += 32 * s.mt2 * l.ws2;
+    l.off_w3 = o; o += 8 * l.ws3;
+    l.off_b1 = o; o += 32 * s.mt1;
+    l.off_b2 = o; o += 32 * s.mt2;
+    l.off_x = o; o += 2 * s.ks1 * l.rs;
+    l.off_g = o; o += 8 * l.rs;
+    l.off_h1 = o; o += 32 * s.mt1 * l.rs;
+    l.off_h2 = o; o += (s.mt2 ? 32 * mtmax : 0) * l.rs;   // (delta 1, mt1 tiles, is written here too)
+    l.off_d = o; o += 32 * mtl * l.rs;
+    l.off_acc = o; o += l.acc_slots * 4 * 1024;
+    l.total = o;
+    const int n_last = s.n_h2 ? s.n_h2 : s.n_h1;
+    int p = 0;
+    l.p_w1 = p; p += s.n_h1 * s.n_in;
+    l.p_b1 = p; p += s.n_h1;
+    l.p_w2 = p; p += s.n_h2 * s.n_h1;
+    l.p_b2 = p; p += s.n_h2;
+    l.p_w3 = p; p += s.n_out * n_last;
+    l.p_b3 = p; p += s.n_out;
+    l.n_params = p;
+}
+inline size_t backward_lds_bytes(const BackwardLayout& l) { return (size_t)l.total * sizeof(float); }
+struct PolicyGrads {   // device pointers, Linear layout; dW2 / db2 null with one hidden layer
+    float *dW1, *db1, *dW2, *db2, *dW3, *db3;
+};
+// grads = sum over rows r < n of the gradient for grad_out[r] ([n][n_out]) at row rows[row_index ? row_index[r] : r];
+// partial: [kBwdMaxGroups][n_params] floats of workspace.  Two launches on stream: the groups' partial sums, then their sum in
+// group order.  backward_lds_bytes must be <= kPolMaxLds (the caller checks).  Returns a hipError_t as int.
+int launch_policy_backward(const PolicyShape& s, const float* packed, const float* rows, const long long* row_index, long n,
+                           int row_stride, const float* grad_out, float* partial, const PolicyGrads& grads, void* stream);
 
 // ------------------------------------------------------------------------------------------ GAE (dockauv_collect.hip)
 // SB3's compute_returns_and_advantage over packed rows: rows [K][N][row_stride] with the reward in column n_obs and done in

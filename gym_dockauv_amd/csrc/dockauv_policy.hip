@@ -39,6 +39,7 @@ struct PolicyArgs {
     PolicyShape S;
     const float* packed;
     const float* rows;
+    const long long* row_index;        // ROWS kernels only, nullable [n]: env slot i reads row row_index[i]
     float* actions;
     float* log_prob;                   // nullable [n]: sum_j (-z_ij^2 / 2 - log_std[j] - log(2 pi) / 2)
     const float* log_std;              // [n_out] raw log_std (read with log_prob only; the LDS image keeps exp(log_std))
@@ -112,14 +113,19 @@ __device__ __forceinline__ void stage_weights_(const PolicyArgs& a, float* lds) 
     __syncthreads();
 }
 
-// one tile of 32 envs through all layers, by one wave (tile * 32 < a.n); LOGP: also a.log_prob
-template <int MT1, int MT2, bool LOGP>
+// one tile of 32 envs through all layers, by one wave (tile * 32 < a.n); LOGP: also a.log_prob; ROWS: the row of slot i is
+// a.row_index[i] when an index is given (dockauv_policy_forward_rows) -- the arithmetic is the same instruction sequence
+template <int MT1, int MT2, bool LOGP, bool ROWS = false>
 __device__ __forceinline__ void policy_tile_(const PolicyArgs& a, const float* lds, long tile) {
     const PolicyShape& S = a.S;
     const int lane = threadIdx.x & 63, half = lane >> 5;
     const long env = tile * 32 + (lane & 31);
     const bool live = env < a.n;                        // tail: rows >= n are neither read nor written
-    const float* row = a.rows + (live ? env : 0) * (long)a.row_stride;
+    long src = live ? env : 0;
+    if constexpr (ROWS) {
+        if (live && a.row_index) src = (long)a.row_index[env];
+    }
+    const float* row = a.rows + src * (long)a.row_stride;
 
     // ---- layer 1
     f32x16 h1[MT1];
@@ -203,6 +209,16 @@ __global__ __launch_bounds__(kPolThreads) void policy_logp_kernel(const PolicyAr
     policy_tile_<MT1, MT2, true>(a, lds, tile);
 }
 
+// the pre-activation output of any rows, dense or through an index (dockauv_policy_forward_rows)
+template <int MT1, int MT2>
+__global__ __launch_bounds__(kPolThreads) void policy_rows_kernel(const PolicyArgs a) {
+    extern __shared__ float lds[];
+    stage_weights_(a, lds);
+    const long tile = (long)blockIdx.x * (kPolThreads / 64) + (threadIdx.x >> 6);
+    if (tile * 32 >= a.n) return;                       // (no barrier below)
+    policy_tile_<MT1, MT2, false, true>(a, lds, tile);
+}
+
 struct PackArgs {
     PolicyShape S;
     PolicyRaw raw;
@@ -245,11 +261,11 @@ __global__ void policy_pack_kernel(const PackArgs a) {
     }
 }
 
-template <int MT1, int MT2>
+template <int MT1, int MT2, bool ROWS>
 int launch_forward_(const PolicyArgs& a, size_t lds, hipStream_t stream) {
     const long tiles = ((long)a.n + 31) / 32;
     const long groups = (tiles + kPolThreads / 64 - 1) / (kPolThreads / 64);
-    void (*kernel)(const PolicyArgs) = a.log_prob ? policy_logp_kernel<MT1, MT2> : policy_mlp_kernel<MT1, MT2>;
+    void (*kernel)(const PolicyArgs) = ROWS ? policy_rows_kernel<MT1, MT2> : (a.log_prob ? policy_logp_kernel<MT1, MT2> : policy_mlp_kernel<MT1, MT2>);
     if (groups > 0x7fffffffL) return (int)hipErrorInvalidValue;
     if (lds > 64 * 1024) {
         // more than 64 KiB of LDS per group must be requested explicitly; the attribute belongs to the (device, function)
@@ -261,14 +277,25 @@ int launch_forward_(const PolicyArgs& a, size_t lds, hipStream_t stream) {
     return (int)hipGetLastError();
 }
 
-template <int MT1>
+template <int MT1, bool ROWS>
 int launch_forward_mt1_(const PolicyArgs& a, size_t lds, hipStream_t stream) {
     switch (a.S.mt2) {
-        case 0: return launch_forward_<MT1, 0>(a, lds, stream);
-        case 1: return launch_forward_<MT1, 1>(a, lds, stream);
-        case 2: return launch_forward_<MT1, 2>(a, lds, stream);
-        case 3: return launch_forward_<MT1, 3>(a, lds, stream);
-        case 4: return launch_forward_<MT1, 4>(a, lds, stream);
+        case 0: return launch_forward_<MT1, 0, ROWS>(a, lds, stream);
+        case 1: return launch_forward_<MT1, 1, ROWS>(a, lds, stream);
+        case 2: return launch_forward_<MT1, 2, ROWS>(a, lds, stream);
+        case 3: return launch_forward_<MT1, 3, ROWS>(a, lds, stream);
+        case 4: return launch_forward_<MT1, 4, ROWS>(a, lds, stream);
+    }
+    return (int)hipErrorInvalidValue;
+}
+
+template <bool ROWS>
+int launch_forward_any_(const PolicyArgs& a, size_t lds, hipStream_t stream) {
+    switch (a.S.mt1) {
+        case 1: return launch_forward_mt1_<1, ROWS>(a, lds, stream);
+        case 2: return launch_forward_mt1_<2, ROWS>(a, lds, stream);
+        case 3: return launch_forward_mt1_<3, ROWS>(a, lds, stream);
+        case 4: return launch_forward_mt1_<4, ROWS>(a, lds, stream);
     }
     return (int)hipErrorInvalidValue;
 }
@@ -288,6 +315,7 @@ int launch_policy_forward(const PolicyShape& s, const float* packed, const float
     a.S = s;
     a.packed = packed;
     a.rows = rows;
+    a.row_index = nullptr;
     a.actions = actions;
     a.log_prob = log_prob;
     a.log_std = log_std;
@@ -300,13 +328,24 @@ int launch_policy_forward(const PolicyShape& s, const float* packed, const float
     a.seed = seed;
     const size_t lds = policy_lds_bytes(s);
     if (n <= 0 || lds > kPolMaxLds || (log_prob && !log_std)) return (int)hipErrorInvalidValue;
-    switch (s.mt1) {
-        case 1: return launch_forward_mt1_<1>(a, lds, (hipStream_t)stream);
-        case 2: return launch_forward_mt1_<2>(a, lds, (hipStream_t)stream);
-        case 3: return launch_forward_mt1_<3>(a, lds, (hipStream_t)stream);
-        case 4: return launch_forward_mt1_<4>(a, lds, (hipStream_t)stream);
-    }
-    return (int)hipErrorInvalidValue;
+    return launch_forward_any_<false>(a, lds, (hipStream_t)stream);
+}
+
+int launch_policy_forward_rows(const PolicyShape& s, const float* packed, const float* rows, const long long* row_index, long n,
+                               int row_stride, float* out, void* stream) {
+    PolicyArgs a{};
+    a.S = s;
+    a.S.out_act = DOCKAUV_ACT_NONE;                     // the output before out_act
+    a.packed = packed;
+    a.rows = rows;
+    a.row_index = row_index;
+    a.actions = out;
+    a.n = n;
+    a.row_stride = row_stride;
+    a.act_stride = s.n_out;
+    const size_t lds = policy_lds_bytes(s);
+    if (n <= 0 || lds > kPolMaxLds) return (int)hipErrorInvalidValue;
+    return launch_forward_any_<true>(a, lds, (hipStream_t)stream);
 }
 
 }  // namespace dockauv

@@ -720,6 +720,26 @@ class BatchedDocking3d:
                                        C.c_void_p(stream or None))
         _capi.check(self._lib, self._handle, rc, "dockauv_collect")
 
+    def policy_forward_rows_device(self, policy, rows_ptr: int, n_rows: int, out_ptr: int, index_ptr: int = 0, stream: int = 0) -> None:
+        """The MLP's output before its output activation, without noise, for any rows (dockauv_policy_forward_rows; an actor or
+        a critic): rows float32 packed rows [n_obs + 2], index int64 [n_rows] or 0 (row r is rows[index[r]]), out float32
+        [n_rows][n_out]; asynchronous."""
+        rc = self._lib.dockauv_policy_forward_rows(self._handle, policy.ptr, C.c_void_p(rows_ptr or None), C.c_void_p(index_ptr or None),
+                                                   int(n_rows), C.c_void_p(out_ptr or None), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_policy_forward_rows")
+
+    def policy_backward_device(self, policy, rows_ptr: int, n_rows: int, grad_out_ptr: int, grad_ptrs, index_ptr: int = 0,
+                               stream: int = 0) -> None:
+        """Gradients of all weights and biases for grad_out float32 [n_rows][n_out] on the output of
+        ``policy_forward_rows_device`` (dockauv_policy_backward): ``grad_ptrs`` = (dW1, db1, dW2, db2, dW3, db3) device
+        addresses of float32 arrays in torch.nn.Linear layout (dW2 / db2 0 with one hidden layer), overwritten; asynchronous."""
+        g = _capi.PolicyGrads()
+        g.struct_size = C.sizeof(_capi.PolicyGrads)
+        g.dW1, g.db1, g.dW2, g.db2, g.dW3, g.db3 = [int(x) or None for x in grad_ptrs]
+        rc = self._lib.dockauv_policy_backward(self._handle, policy.ptr, C.c_void_p(rows_ptr or None), C.c_void_p(index_ptr or None),
+                                               int(n_rows), C.c_void_p(grad_out_ptr or None), C.byref(g), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_policy_backward")
+
     def destroy_policy(self, policy) -> None:
         if policy.ptr is not None and policy.ptr.value:
             self._lib.dockauv_policy_destroy(policy.ptr)

@@ -131,6 +131,15 @@ class TorchDocking3d:
         self.batch.load_policy(policy, device_ptrs=[0 if t is None else t.data_ptr() for t in ts],
                                log_std_ptr=0 if log_std is None else log_std.detach().data_ptr(),
                                stream=torch.cuda.current_stream().cuda_stream)
+        policy.log_std_tensor = log_std       # (mlp_apply reloads the weights with the same log_std)
+
+    def _load_weights(self, policy, tensors) -> None:
+        """load_policy with the log_std the policy last got from a device tensor"""
+        log_std = getattr(policy, "log_std_tensor", None)
+        if policy.has_log_std and log_std is None:
+            raise ValueError("the actor's log_std came from host arrays: hand it over as a device tensor once "
+                             "(load_policy(policy, params, log_std=...)) so that mlp_apply can keep it")
+        self.load_policy(policy, tensors, log_std=log_std)
 
     def rollout(self, policy, n_steps: int, stochastic: bool = False, want_terminal_obs: bool = False):
         """``n_steps`` x (policy, step) queued by ONE host call (dockauv_rollout) on the current stream, starting from the rows
@@ -199,6 +208,83 @@ class TorchDocking3d:
         self.rollout_terminal_observation = term
         return Collected(rows[:, :, : self.n_obs], bufs["acts"], rows[1:, :, self.n_obs], rows[1:, :, self.n_obs + 1] > 0.5,
                          logp, values, adv, ret)
+
+    # ------------------------------------------------------------------------------------------ the network's share of the update
+    def _mlp_rows(self, policy, rows, index):
+        """(pointer to the first packed row, number of rows the call addresses) after validation.  ``rows``: float32 on this device,
+        [..., n_obs + 2] packed rows or the [..., n_obs] observation view of such a buffer (``Collected.obs``): last stride 1, the
+        leading dimensions one run of rows n_obs + 2 floats apart."""
+        torch = self.torch
+        stride = self.n_obs + 2
+        if rows.device != self.device or rows.dtype != torch.float32 or rows.dim() < 2 or rows.shape[-1] not in (self.n_obs, stride) \
+                or policy.n_in != self.n_obs:
+            raise ValueError(f"rows must be float32 [..., {stride}] packed rows (or their [..., {self.n_obs}] view) on {self.device}")
+        n, expect = 1, stride
+        ok = rows.stride(-1) == 1
+        for size, st in zip(reversed(rows.shape[:-1]), reversed(rows.stride()[:-1])):
+            ok = ok and (size == 1 or st == expect)
+            expect *= size
+            n *= size
+        if not ok or n < 1:
+            raise ValueError(f"rows must be a contiguous run of packed rows, {stride} floats apart")
+        if index is not None:
+            if index.device != self.device or index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous() or index.numel() < 1:
+                raise ValueError(f"index must be a contiguous int64 [B] tensor on {self.device}")
+        return rows.data_ptr(), (n if index is None else int(index.numel()))
+
+    def mlp_forward(self, policy, rows, index=None):
+        """[B, n_out]: the output of ``policy`` (an actor or a critic) before its output activation, without noise, for the packed
+        ``rows`` (all of them, B = their number) or for rows[index[r]] (``index`` int64 [B], e.g. a slice of torch.randperm):
+        dockauv_policy_forward_rows on the current stream.  A fresh tensor."""
+        torch = self.torch
+        ptr, B = self._mlp_rows(policy, rows, index)
+        out = torch.empty((B, policy.n_out), device=self.device, dtype=torch.float32)
+        self.batch.policy_forward_rows_device(policy, ptr, B, out.data_ptr(), index_ptr=0 if index is None else index.data_ptr(),
+                                              stream=torch.cuda.current_stream().cuda_stream)
+        return out
+
+    def mlp_backward(self, policy, rows, grad_out, index=None):
+        """The gradients of all weights and biases of ``policy`` for ``grad_out`` [B, n_out] = dL/d(mlp_forward(policy, rows,
+        index)): dockauv_policy_backward on the current stream.  Returns fresh tensors (dW1, db1[, dW2, db2], dW3, db3) in
+        torch.nn.Linear layout.  Reproducible bit for bit; no gradient with respect to the rows."""
+        torch = self.torch
+        ptr, B = self._mlp_rows(policy, rows, index)
+        if grad_out.device != self.device or grad_out.dtype != torch.float32 or not grad_out.is_contiguous() \
+                or tuple(grad_out.shape) != (B, policy.n_out):
+            raise ValueError(f"grad_out must be a contiguous float32 [{B}, {policy.n_out}] tensor on {self.device}")
+        widths = [policy.n_in] + policy.n_hidden + [policy.n_out]
+        grads = []
+        for i in range(len(widths) - 1):
+            grads += [torch.empty((widths[i + 1], widths[i]), device=self.device, dtype=torch.float32),
+                      torch.empty((widths[i + 1],), device=self.device, dtype=torch.float32)]
+        ptrs = [g.data_ptr() for g in grads]
+        if len(ptrs) == 4:
+            ptrs[2:2] = [0, 0]
+        self.batch.policy_backward_device(policy, ptr, B, grad_out.data_ptr(), ptrs, index_ptr=0 if index is None else index.data_ptr(),
+                                          stream=torch.cuda.current_stream().cuda_stream)
+        return tuple(grads)
+
+    def mlp_apply(self, policy, params, rows, index=None):
+        """``mlp_forward`` as a differentiable torch operation: ``params`` = the learner's (W1, b1[, W2, b2], W3, b3) device
+        tensors (leaves that require grad, e.g. ``list(net.parameters())`` of an nn.Sequential of Linear layers).  They are
+        loaded into ``policy`` on the current stream (``load_policy``, with the log_std device tensor of the last ``load_policy``) and the forward
+        kernel runs; ``.backward()`` runs the backward kernel and hands each parameter its gradient.  ``rows`` and ``index``
+        get none."""
+        torch = self.torch
+        env = self
+
+        class _Apply(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, *ps):
+                return env.mlp_forward(policy, rows, index)
+
+            @staticmethod
+            def backward(ctx, grad):
+                return env.mlp_backward(policy, rows, grad.contiguous(), index)
+
+        params = tuple(params)
+        self._load_weights(policy, [p.detach() for p in params])
+        return _Apply.apply(*params)
 
     @property
     def terminal_observation(self):

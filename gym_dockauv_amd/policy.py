@@ -6,8 +6,8 @@ is SB3's ``MlpPolicy``, which train.py:64 instantiates and train.py:64-71 / 86-1
 ``MLPPolicy`` is a plain host object that holds the arrays; ``BatchedDocking3d.make_policy`` / ``TorchDocking3d.make_policy``
 put it on the device.  An ``MLPPolicy`` with one raw output is a critic (SB3's ``mlp_extractor.value_net`` + ``value_net``;
 ``value_from_torch``, ``make_value``): the PPO collector (dockauv_collect) evaluates it on the rollout's rows.
-``forward_reference``, ``normals_reference``, ``log_prob_reference`` and ``gae_reference`` are float64 NumPy statements of what
-the kernels compute (for tests and for callers who want to check a port); they are never used as a compute path.
+``forward_reference``, ``backward_reference``, ``normals_reference``, ``log_prob_reference`` and ``gae_reference`` are float64
+NumPy statements of what the kernels compute (for tests and for callers who want to check a port); they are never used as a compute path.
 """
 from __future__ import annotations
 
@@ -176,6 +176,25 @@ class MLPPolicy:
                 raise ValueError("z given but the policy has no log_std")
             x = x + np.exp(self.log_std.astype(np.float64)) * np.asarray(z, dtype=np.float64)
         return _act(x, self.out_act)
+
+    def backward_reference(self, obs: np.ndarray, grad_out: np.ndarray):
+        """float64 statement of dockauv_policy_backward: obs [B, n_in], grad_out [B, n_out] = dL/d(out) with out = W3 h_last +
+        b3 (before out_act, no noise).  Returns the gradients in layer order, (dW1, db1[, dW2, db2], dW3, db3), each summed over
+        the rows, torch.nn.Linear layout.  tanh' = 1 - h^2; relu' = 1 where the pre-activation is > 0, else 0."""
+        x = np.asarray(obs, dtype=np.float64).reshape(-1, self.n_in)
+        g = np.asarray(grad_out, dtype=np.float64).reshape(-1, self.n_out)
+        if x.shape[0] != g.shape[0]:
+            raise ValueError("obs [B, n_in] and grad_out [B, n_out] need the same B")
+        hs = [x]
+        for W, b in self.layers[:-1]:
+            hs.append(_act(hs[-1] @ W.astype(np.float64).T + b.astype(np.float64), self.hidden_act))
+        grads = []
+        for i in range(len(self.layers) - 1, -1, -1):
+            grads[:0] = [g.T @ hs[i], g.sum(axis=0)]
+            if i > 0:
+                h = hs[i]
+                g = (g @ self.layers[i][0].astype(np.float64)) * (1.0 - h * h if self.hidden_act == "tanh" else (h > 0.0).astype(np.float64))
+        return tuple(grads)
 
     @staticmethod
     def normals_reference(seed: int, env_ids, t: int, n_out: int) -> np.ndarray:

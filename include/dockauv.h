@@ -341,8 +341,11 @@ int dockauv_step_gather_sequence(dockauv_handle h, const dockauv_step_io* ios, i
  * torch nor a graph capture sits between two steps.  Arithmetic is float32 throughout: every pre-activation is one fused
  * multiply-add chain from the bias in a k order fixed by the shapes alone; env i's action depends on row i and the weights
  * only.  The critic, the log-probabilities of the drawn actions and GAE are further below (dockauv_value_*,
- * dockauv_policy_forward_logp, dockauv_gae, dockauv_collect): one host call returns everything a PPO update reads; the update
- * itself stays with the learner.
+ * dockauv_policy_forward_logp, dockauv_gae, dockauv_collect): one host call returns everything a PPO update reads.  Of the
+ * update, the library computes the network's share -- the MLP's output on any minibatch of those rows and the gradients of
+ * all weights and biases for gradients on that output (dockauv_policy_forward_rows, dockauv_policy_backward, at the end of this
+ * header); the PPO head (ratio, clipping, value loss, entropy, the gradient of log_std) and the optimiser step stay with the
+ * learner.
  */
 #define DOCKAUV_ACT_NONE 0       /* output: raw (PPO; the step kernel clips, objects/auvsim.py:74) */
 #define DOCKAUV_ACT_TANH 1       /* hidden: SB3's default; output: SAC-style squashing */
@@ -452,6 +455,42 @@ typedef struct dockauv_collect_io {
  * what dockauv_poll_status returns, looked at once after queueing. */
 int dockauv_collect(dockauv_handle h, dockauv_policy actor, dockauv_policy critic, const dockauv_collect_io* io,
                     void* hip_stream);
+
+/*
+ * The network's share of the update (PPO.train of train.py:64-71: the MlpPolicy forward on a minibatch and autograd's backward
+ * through it), for an actor and for a critic alike.  All pointers are device pointers, both calls are asynchronous on the
+ * stream, the weights are the ones the policy holds at that point of the stream (dockauv_policy_load).
+ *
+ * out[r][0 .. n_out) = W3 h_last + b3 of packed row rows[row_index ? row_index[r] : r], r < n_rows: the output BEFORE out_act
+ * and without exploration noise.  rows: float32, row stride n_obs + 2, only the first n_obs columns are read; row_index:
+ * nullable int64 [n_rows] (a minibatch, e.g. of torch.randperm; duplicates allowed, the range is the caller's contract); out:
+ * float32 [n_rows][n_out].  Bit for bit what dockauv_policy_forward (deterministic, out_act NONE) and dockauv_value_forward give
+ * for the same row.
+ */
+int dockauv_policy_forward_rows(dockauv_handle h, dockauv_policy p, const float* rows, const int64_t* row_index,
+                                long long n_rows, float* out, void* hip_stream);
+/* The gradients dockauv_policy_backward writes: torch.nn.Linear layout ([out][in], [out]), float32, overwritten (not
+ * accumulated).  dW2 / db2 are NULL with one hidden layer. */
+typedef struct dockauv_policy_grads {
+    uint32_t struct_size;          /* sizeof(dockauv_policy_grads): ABI check */
+    uint32_t reserved;
+    float *dW1, *db1, *dW2, *db2, *dW3, *db3;
+} dockauv_policy_grads;
+/* grad_out: float32 [n_rows][n_out] = dL/d(out), out as dockauv_policy_forward_rows defines it.  Per row r, summed over r in
+ * float32:  db3 = sum g_r;  dW3 = sum g_r (x) h_last,r;  delta = (W3^T g_r) . act'  and so on down to dW1 = sum delta1,r (x) x_r,
+ * with tanh' = 1 - h^2 of the recomputed h and relu' = 1 where the pre-activation is > 0, else 0 (torch's convention).  No
+ * gradient with respect to the rows.
+ * Reproducible: no floating-point atomics; two calls with the same inputs give the same bits, and rows reached through row_index
+ * give the same bits as the same rows laid out densely in that order (the summation order is a function of the position in the
+ * minibatch, n_rows and the shapes only).
+ * Workspace: the library owns the per-group partial sums (at most 256 groups, each looping over its share of the rows, then a
+ * second launch that adds the partials in group order); their size does not depend on n_rows.  They are allocated at the first
+ * backward of a policy and freed by dockauv_policy_destroy; later calls allocate nothing.
+ * The kernel keeps the weights (torch.nn.Linear layout, padded), one pass's rows, activations and deltas in LDS.  Shapes whose
+ * need exceeds the 160 KiB are refused with a message that names it: a 128-128 network takes n_obs <= 62, narrower networks
+ * wider observations. */
+int dockauv_policy_backward(dockauv_handle h, dockauv_policy p, const float* rows, const int64_t* row_index, long long n_rows,
+                            const float* grad_out, const dockauv_policy_grads* grads, void* hip_stream);
 
 #ifdef __cplusplus
 }
