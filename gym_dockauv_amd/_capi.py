@@ -125,6 +125,17 @@ class PolicyGrads(C.Structure):
     ]
 
 
+class PPOHeadIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("normalize_advantage", C.c_int32),
+        ("mean", C.c_void_p), ("v", C.c_void_p),
+        ("actions", C.c_void_p), ("log_prob_old", C.c_void_p), ("advantages", C.c_void_p), ("returns", C.c_void_p),
+        ("row_index", C.c_void_p), ("n_rows", C.c_longlong),
+        ("clip_range", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float), ("reserved", C.c_int32),
+        ("grad_mean", C.c_void_p), ("grad_v", C.c_void_p), ("grad_log_std", C.c_void_p), ("stats", C.c_void_p),
+    ]
+
+
 # every symbol include/dockauv.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("dockauv_abi_version", C.c_int, []),
@@ -176,6 +187,7 @@ SYMBOLS = [
     ("dockauv_policy_forward_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
     ("dockauv_policy_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
                                           C.POINTER(PolicyGrads), C.c_void_p]),
+    ("dockauv_ppo_head", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PPOHeadIO), C.c_void_p]),
 ]
 
 _lib: Optional[C.CDLL] = None

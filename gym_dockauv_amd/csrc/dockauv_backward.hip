@@ -1,6 +1,7 @@
 // dockauv_backward.hip -- the backward pass of the library's MLP for gfx950 (MI355X): the gradients of all weights and biases for
 // upstream gradients on the network's raw output (include/dockauv.h: dockauv_policy_backward; the reference's counterpart is
-// what torch autograd does for SB3's MlpPolicy inside PPO.train, train.py:64-71).  The PPO head and the optimiser stay in torch.
+// what torch autograd does for SB3's MlpPolicy inside PPO.train, train.py:64-71).  The upstream gradients are the PPO head's
+// (dockauv_head.hip) or the learner's own; the optimiser stays in torch.
 //
 // Two launches.  policy_backward_kernel<MT1, MT2>: a bounded grid of groups of four waves; a group walks the passes
 // b = blockIdx.x, blockIdx.x + gridDim.x, ... of 32 rt rows each and keeps its sums over all of them.  Everything of a pass lies

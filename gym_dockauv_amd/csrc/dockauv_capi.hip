@@ -1180,6 +1180,7 @@ struct dockauv_policy_s {
     bool value_role = false;      // a critic (dockauv_value_create): n_out == 1, raw output
     uint64_t seed = 0, env_id_offset = 0;
     float* bwd_partial = nullptr; // dockauv_policy_backward's per-group partial sums, allocated by the first backward
+    double* head_ws = nullptr;    // dockauv_ppo_head's moment and row-sum partials (kHeadWorkspaceBytes), allocated by the first head call
 };
 
 namespace {
@@ -1391,6 +1392,7 @@ int dockauv_policy_destroy(dockauv_policy p) {
     if (p->raw) (void)hipFree(p->raw);
     if (p->log_std) (void)hipFree(p->log_std);
     if (p->bwd_partial) (void)hipFree(p->bwd_partial);
+    if (p->head_ws) (void)hipFree(p->head_ws);
     delete p;
     return 0;
 }
@@ -1465,6 +1467,56 @@ int dockauv_policy_backward(dockauv_handle h, dockauv_policy p, const float* row
     const int rc = launch_policy_backward(p->S, p->packed, rows, (const long long*)row_index, (long)n_rows, h->n_obs + 2, grad_out,
                                           p->bwd_partial, g, (hipStream_t)hip_stream);
     if (rc != 0) return fail(h, DOCKAUV_E_HIP, "policy backward launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
+    return 0;
+}
+
+int dockauv_ppo_head(dockauv_handle h, dockauv_policy actor, const dockauv_ppo_head_io* io, void* hip_stream) {
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_ppo_head: null handle");
+    if (!actor) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head: null actor");
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head: io is NULL");
+    if (io->struct_size != sizeof(dockauv_ppo_head_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_ppo_head_io));
+    if (int rc = check_actor(h, actor, "dockauv_ppo_head", true)) return rc;
+    if (io->n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.n_rows: %lld must be >= 1", io->n_rows);
+    if (io->normalize_advantage && io->n_rows < 2)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.n_rows: %lld must be >= 2 with normalize_advantage (the unbiased deviation)", io->n_rows);
+    if (!(io->clip_range > 0.0f)) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.clip_range: %g must be > 0", (double)io->clip_range);
+    if (!io->mean) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.mean is NULL");
+    if (!io->actions) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.actions is NULL");
+    if (!io->log_prob_old) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.log_prob_old is NULL");
+    if (!io->advantages) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.advantages is NULL");
+    if (!io->grad_mean) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.grad_mean is NULL");
+    if (!io->grad_log_std) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.grad_log_std is NULL");
+    if (!io->stats) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.stats is NULL");
+    if ((io->v == nullptr) != (io->grad_v == nullptr))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.v / grad_v: both or neither must be NULL (NULL: no critic)");
+    if (io->v && !io->returns) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.returns is NULL (v is given)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!actor->head_ws) HIP_TRY(h, hipMalloc((void**)&actor->head_ws, kHeadWorkspaceBytes));
+    HeadArgs a{};
+    a.mean = io->mean;
+    a.v = io->v;
+    a.actions = io->actions;
+    a.log_prob_old = io->log_prob_old;
+    a.advantages = io->advantages;
+    a.returns = io->returns;
+    a.row_index = (const long long*)io->row_index;
+    a.log_std = actor->log_std;
+    a.grad_mean = io->grad_mean;
+    a.grad_v = io->grad_v;
+    a.grad_log_std = io->grad_log_std;
+    a.stats = io->stats;
+    a.moments = actor->head_ws;
+    a.partial = actor->head_ws + (size_t)kBwdMaxGroups * kHeadMoments;
+    a.n = (long)io->n_rows;
+    a.n_out = actor->S.n_out;
+    a.normalize = io->normalize_advantage ? 1 : 0;
+    a.clip = io->clip_range;
+    a.vf_coef = io->vf_coef;
+    a.ent_coef = io->ent_coef;
+    const int rc = launch_ppo_head(a, hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "PPO head launch failed: %s", hipGetErrorString((hipError_t)rc));
     h->last_stream = (hipStream_t)hip_stream;
     return 0;
 }

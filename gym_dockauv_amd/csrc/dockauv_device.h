@@ -377,6 +377,33 @@ int launch_policy_backward(const PolicyShape& s, const float* packed, const floa
 int launch_gae(const float* rows, const float* values, float* advantages, float* returns, int n_steps, int n_envs, int n_obs,
                float gamma, float gae_lambda, void* stream);
 
+// ------------------------------------------------------------------------------------------ PPO head (dockauv_head.hip)
+// Loss terms, statistics and the gradients on the networks' raw outputs and on log_std for one minibatch (include/dockauv.h:
+// dockauv_ppo_head states the arithmetic).  Groups of kHeadThreads lanes on the backward's bounded grid (kBwdMaxGroups); a lane
+// has the loads of kHeadChunk rows in flight, a group takes kHeadPassRows rows a pass.  Workspace, float64, its size independent
+// of n: kHeadMoments words a group from the advantage-moment launch (sum, squares about the group's centre, that centre, rows)
+// and kHeadSums row sums a group (surrogate, squared value error, KL term, clipped rows, then DOCKAUV_MAX_U of d log_std).
+constexpr int kHeadThreads = 256;
+constexpr int kHeadChunk = 4;
+constexpr int kHeadPassRows = kHeadThreads * kHeadChunk;
+constexpr int kHeadMoments = 4;
+constexpr int kHeadSums = 4 + 8;          // 8 = DOCKAUV_MAX_U
+constexpr size_t kHeadWorkspaceBytes = (size_t)kBwdMaxGroups * (kHeadMoments + kHeadSums) * sizeof(double);
+struct HeadArgs {
+    const float *mean, *v;                // [n][n_out]; [n] or null (no critic)
+    const float *actions, *log_prob_old, *advantages, *returns;   // row arrays, read at row_index[r]
+    const long long* row_index;           // nullable [n]
+    const float* log_std;                 // [n_out], the actor's
+    float *grad_mean, *grad_v, *grad_log_std, *stats;
+    double *moments, *partial;            // [kBwdMaxGroups][kHeadMoments], [kBwdMaxGroups][kHeadSums]
+    long n;
+    int n_out, normalize;
+    float clip, vf_coef, ent_coef;
+};
+// Up to three launches on stream: the advantage moments (normalize only), the rows and the groups' partial sums, their sum in
+// group order.  Returns a hipError_t as int.
+int launch_ppo_head(const HeadArgs& a, void* stream);
+
 #ifdef DOCKAUV_STAMPS
 int read_stamps(unsigned long long* out);   // diagnostic build only
 int read_span(unsigned long long* out, int groups);

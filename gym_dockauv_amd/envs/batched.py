@@ -740,6 +740,27 @@ class BatchedDocking3d:
                                                int(n_rows), C.c_void_p(grad_out_ptr or None), C.byref(g), C.c_void_p(stream or None))
         _capi.check(self._lib, self._handle, rc, "dockauv_policy_backward")
 
+    def ppo_head_device(self, policy, n_rows: int, mean_ptr: int, v_ptr: int, actions_ptr: int, log_prob_old_ptr: int,
+                        advantages_ptr: int, returns_ptr: int, grad_mean_ptr: int, grad_v_ptr: int, grad_log_std_ptr: int,
+                        stats_ptr: int, clip_range: float, vf_coef: float, ent_coef: float, normalize_advantage: bool = True,
+                        index_ptr: int = 0, stream: int = 0) -> None:
+        """The PPO head on a minibatch of n_rows rows (dockauv_ppo_head; ``policy`` is the actor, whose log_std is used): mean
+        float32 [n_rows][n_u] and v float32 [n_rows] (0: no critic, then grad_v 0 too) are the networks' outputs, the row arrays
+        are read at index[r] (int64 [n_rows] or 0); writes grad_mean [n_rows][n_u], grad_v [n_rows], grad_log_std [n_u] and
+        stats [8] (loss, policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction, advantage mean and std); asynchronous."""
+        io = _capi.PPOHeadIO()
+        io.struct_size = C.sizeof(_capi.PPOHeadIO)
+        io.normalize_advantage = 1 if normalize_advantage else 0
+        io.mean, io.v = mean_ptr or None, v_ptr or None
+        io.actions, io.log_prob_old = actions_ptr or None, log_prob_old_ptr or None
+        io.advantages, io.returns = advantages_ptr or None, returns_ptr or None
+        io.row_index, io.n_rows = index_ptr or None, int(n_rows)
+        io.clip_range, io.vf_coef, io.ent_coef = float(clip_range), float(vf_coef), float(ent_coef)
+        io.grad_mean, io.grad_v, io.grad_log_std = grad_mean_ptr or None, grad_v_ptr or None, grad_log_std_ptr or None
+        io.stats = stats_ptr or None
+        rc = self._lib.dockauv_ppo_head(self._handle, policy.ptr, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_ppo_head")
+
     def destroy_policy(self, policy) -> None:
         if policy.ptr is not None and policy.ptr.value:
             self._lib.dockauv_policy_destroy(policy.ptr)

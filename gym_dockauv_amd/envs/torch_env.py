@@ -286,6 +286,66 @@ class TorchDocking3d:
         self._load_weights(policy, [p.detach() for p in params])
         return _Apply.apply(*params)
 
+    # ------------------------------------------------------------------------------------------ the PPO head
+    def ppo_head(self, policy, mean, v, actions, log_prob_old, advantages, returns, index=None, *, clip_range: float,
+                 vf_coef: float, ent_coef: float, normalize_advantage: bool = True):
+        """The PPO head on one minibatch (dockauv_ppo_head on the current stream; ``policy`` is the actor, whose log_std the
+        kernel reads): ``mean`` [B, n_u] and ``v`` [B] (None: no critic) are ``mlp_forward`` of the actor and the critic;
+        ``actions`` [M, n_u], ``log_prob_old`` / ``advantages`` / ``returns`` [M] are the collection's arrays, read at
+        ``index`` (int64 [B], the one the forward took; None: M == B, in order).  Returns fresh tensors (grad_mean [B, n_u],
+        grad_v [B] or None, grad_log_std [n_u], stats [8]): the gradients of SB3's PPO loss on the two network outputs and on
+        log_std, and (loss, policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction, advantage mean, advantage std).
+        Reproducible bit for bit; does not synchronise."""
+        torch = self.torch
+        ok = lambda t, shape: t.device == self.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+        if mean.dim() != 2 or not ok(mean, (mean.shape[0], policy.n_out)) or mean.shape[0] < 1:
+            raise ValueError(f"mean must be a contiguous float32 [B, {policy.n_out}] tensor on {self.device}")
+        B = int(mean.shape[0])
+        if v is not None and not ok(v, (B,)):
+            raise ValueError(f"v must be a contiguous float32 [{B}] tensor on {self.device} (or None)")
+        if index is not None:
+            if index.device != self.device or index.dtype != torch.int64 or not index.is_contiguous() or tuple(index.shape) != (B,):
+                raise ValueError(f"index must be a contiguous int64 [{B}] tensor on {self.device}")
+        M = B if index is None else (int(actions.shape[0]) if actions.dim() == 2 else -1)
+        if not ok(actions, (M, policy.n_out)):
+            raise ValueError(f"actions must be a contiguous float32 [M, {policy.n_out}] tensor on {self.device} (M = {B} without an index)")
+        for name, t in (("log_prob_old", log_prob_old), ("advantages", advantages)) + ((("returns", returns),) if v is not None else ()):
+            if not ok(t, (M,)):
+                raise ValueError(f"{name} must be a contiguous float32 [{M}] tensor on {self.device}")
+        if normalize_advantage and B < 2:
+            raise ValueError("normalize_advantage needs at least two rows")
+        new = lambda *shape: torch.empty(shape, device=self.device, dtype=torch.float32)
+        grad_mean, grad_v, grad_log_std, stats = new(B, policy.n_out), (new(B) if v is not None else None), new(policy.n_out), new(8)
+        self.batch.ppo_head_device(policy, B, mean.data_ptr(), 0 if v is None else v.data_ptr(), actions.data_ptr(),
+                                   log_prob_old.data_ptr(), advantages.data_ptr(), 0 if v is None else returns.data_ptr(),
+                                   grad_mean.data_ptr(), 0 if v is None else grad_v.data_ptr(), grad_log_std.data_ptr(),
+                                   stats.data_ptr(), clip_range, vf_coef, ent_coef, normalize_advantage=normalize_advantage,
+                                   index_ptr=0 if index is None else index.data_ptr(),
+                                   stream=torch.cuda.current_stream().cuda_stream)
+        return grad_mean, grad_v, grad_log_std, stats
+
+    def ppo_minibatch(self, policy, value, actor_params, log_std, critic_params, actions, log_prob_old, advantages, returns,
+                      rows, index, **head_args):
+        """One PPO minibatch step without autograd, up to the optimiser: the weights of ``actor_params`` / ``critic_params``
+        (the learner's (W1, b1[, W2, b2], W3, b3) device tensors) and ``log_std`` are loaded into ``policy`` / ``value`` on the
+        current stream as ``mlp_apply`` does, then ``mlp_forward`` of both on rows[index], ``ppo_head`` (``head_args``:
+        clip_range, vf_coef, ent_coef[, normalize_advantage]) and ``mlp_backward`` of both.  Every parameter's and log_std's
+        ``.grad`` is set to its gradient (what was there is replaced, not added to).  Returns ``stats`` [8] as ``ppo_head``
+        does, on the device, without a synchronisation; ``clip_grad_norm_`` and ``opt.step()`` stay with the caller."""
+        actor_params, critic_params = list(actor_params), list(critic_params)
+        self.load_policy(policy, [p.detach() for p in actor_params], log_std=log_std.detach())
+        self.load_policy(value, [p.detach() for p in critic_params])
+        mean = self.mlp_forward(policy, rows, index)
+        v = self.mlp_forward(value, rows, index).view(-1)
+        grad_mean, grad_v, grad_log_std, stats = self.ppo_head(policy, mean, v, actions, log_prob_old, advantages, returns, index,
+                                                               **head_args)
+        for p, g in zip(actor_params, self.mlp_backward(policy, rows, grad_mean, index)):
+            p.grad = g
+        for p, g in zip(critic_params, self.mlp_backward(value, rows, grad_v.view(-1, 1), index)):
+            p.grad = g
+        log_std.grad = grad_log_std
+        return stats
+
     @property
     def terminal_observation(self):
         return self._terminal

@@ -163,6 +163,49 @@ class MLPPolicy:
             adv[k] = gae
         return adv, adv + v[:K]
 
+    @staticmethod
+    def ppo_head_reference(mean, v, actions, log_prob_old, advantages, returns, log_std, clip_range: float, vf_coef: float,
+                           ent_coef: float, normalize_advantage: bool = True):
+        """float64 statement of dockauv_ppo_head on one minibatch, every array already gathered: mean, actions [B, n_out];
+        v (None: no critic), log_prob_old, advantages, returns [B]; log_std [n_out].  The loss is SB3's: the clipped surrogate
+        on advantages normalised with the unbiased standard deviation, vf_coef x the squared value error, ent_coef x the
+        negative Gaussian entropy.  Returns (grad_mean [B, n_out], grad_v [B] or None, grad_log_std [n_out], stats [8]):
+        d loss / d mean, d loss / d v, d loss / d log_std and (loss, policy_loss, value_loss, entropy_loss, approx_kl,
+        clip_fraction, advantage mean, advantage std -- 0 and 1 without normalisation).  Where the two surrogates tie (inside
+        the clip range, and on its edges) the gradient is the unclipped one, as torch.min and clamp give it."""
+        f = lambda x: np.asarray(x, dtype=np.float64)
+        mean, a, lpo, adv, ls = f(mean), f(actions), f(log_prob_old).reshape(-1), f(advantages).reshape(-1), f(log_std).reshape(-1)
+        B, n_out = mean.shape
+        if a.shape != (B, n_out) or lpo.shape != (B,) or adv.shape != (B,) or ls.shape != (n_out,):
+            raise ValueError("mean, actions: [B, n_out]; log_prob_old, advantages: [B]; log_std: [n_out]")
+        m, s = 0.0, 1.0
+        if normalize_advantage:
+            if B < 2:
+                raise ValueError("normalize_advantage needs B >= 2")
+            m, s = float(adv.mean()), float(adv.std(ddof=1))
+            adv = (adv - m) / (s + 1e-8)
+        clip = float(clip_range)
+        z = (a - mean) * np.exp(-ls)
+        lr = MLPPolicy.log_prob_reference(z, ls) - lpo
+        ratio = np.exp(lr)
+        live = ~(((adv > 0) & (ratio > 1.0 + clip)) | ((adv < 0) & (ratio < 1.0 - clip)))
+        policy_loss = -np.minimum(ratio * adv, np.clip(ratio, 1.0 - clip, 1.0 + clip) * adv).mean()
+        g = -(adv * ratio * live) / B
+        grad_mean = g[:, None] * z * np.exp(-ls)
+        grad_log_std = (g[:, None] * (z * z - 1.0)).sum(axis=0) - ent_coef
+        entropy_loss = -float((0.5 + 0.5 * np.log(2.0 * np.pi) + ls).sum())
+        value_loss, grad_v = 0.0, None
+        if v is not None:
+            v, ret = f(v).reshape(-1), f(returns).reshape(-1)
+            if v.shape != (B,) or ret.shape != (B,):
+                raise ValueError("v, returns: [B]")
+            value_loss = float(((ret - v) ** 2).mean())
+            grad_v = 2.0 * vf_coef * (v - ret) / B
+        loss = policy_loss + ent_coef * entropy_loss + vf_coef * value_loss
+        stats = np.array([loss, policy_loss, value_loss, entropy_loss, ((ratio - 1.0) - lr).mean(),
+                          (np.abs(ratio - 1.0) > clip).mean(), m, s], dtype=np.float64)
+        return grad_mean, grad_v, grad_log_std, stats
+
     def forward_reference(self, obs: np.ndarray, z: Optional[np.ndarray] = None) -> np.ndarray:
         """float64 forward of float32 weights: obs [..., n_in] -> [..., n_out]; ``z`` [..., n_out]: exploration normals,
         added as exp(log_std) * z before the output activation."""

@@ -344,8 +344,9 @@ int dockauv_step_gather_sequence(dockauv_handle h, const dockauv_step_io* ios, i
  * dockauv_policy_forward_logp, dockauv_gae, dockauv_collect): one host call returns everything a PPO update reads.  Of the
  * update, the library computes the network's share -- the MLP's output on any minibatch of those rows and the gradients of
  * all weights and biases for gradients on that output (dockauv_policy_forward_rows, dockauv_policy_backward, at the end of this
- * header); the PPO head (ratio, clipping, value loss, entropy, the gradient of log_std) and the optimiser step stay with the
- * learner.
+ * header) -- and the PPO head between the two: advantage normalisation, log-probability, ratio and clipping, value loss,
+ * entropy, the gradients on both networks' outputs and on log_std, and the statistics SB3 logs (dockauv_ppo_head, the last
+ * entry of this header).  Gradient-norm clipping and the optimiser step stay with the learner.
  */
 #define DOCKAUV_ACT_NONE 0       /* output: raw (PPO; the step kernel clips, objects/auvsim.py:74) */
 #define DOCKAUV_ACT_TANH 1       /* hidden: SB3's default; output: SAC-style squashing */
@@ -491,6 +492,64 @@ typedef struct dockauv_policy_grads {
  * wider observations. */
 int dockauv_policy_backward(dockauv_handle h, dockauv_policy p, const float* rows, const int64_t* row_index, long long n_rows,
                             const float* grad_out, const dockauv_policy_grads* grads, void* hip_stream);
+
+/*
+ * The PPO head on one minibatch of B = n_rows rows (the loss block of SB3's PPO.train, train.py:64-71): everything between
+ * dockauv_policy_forward_rows and dockauv_policy_backward.  All pointers are device pointers, float32; asynchronous on the
+ * stream.  mean [B][n_out] and v [B] are the actor's and the critic's dockauv_policy_forward_rows outputs for the minibatch;
+ * the row arrays actions [M][n_out], log_prob_old [M], advantages [M], returns [M] are read at i = row_index ? row_index[r] : r
+ * (the same index the forward took; duplicates allowed, the range is the caller's contract); log_std is the one the actor
+ * holds at this point of the stream (dockauv_policy_load).  For row r, in exactly this float32 order (only the fmaf written
+ * here are fused); m and s are the mean and the unbiased (n - 1) standard deviation of the minibatch's advantages:
+ *   A      = normalize_advantage ? (adv_i - m) / (s + 1e-8f) : adv_i
+ *   z_j    = (a_ij - mean_rj) * expf(-log_std[j])
+ *   term_j = fmaf(-0.5f * z_j, z_j, -(log_std[j] + 0.918938533f))
+ *   logp   = (term_0 + .. + term_3) + (term_4 + .. + term_7), each sum from 0.0f in the order of j (dockauv_policy_forward_logp)
+ *   lr     = logp - log_prob_old_i;  ratio = expf(lr)
+ *   live   = !((A > 0 && ratio > 1.0f + clip_range) || (A < 0 && ratio < 1.0f - clip_range))
+ *   surr   = fminf(ratio * A, fminf(fmaxf(ratio, 1.0f - clip_range), 1.0f + clip_range) * A)
+ *   g      = live ? -(A * ratio) / (float)B : 0.0f                              (= d loss / d logp_r)
+ *   grad_mean[r][j] = (g * z_j) * expf(-log_std[j])
+ *   dv     = v_r - ret_i;  grad_v[r] = ((2.0f * vf_coef) * dv) / (float)B
+ * and the sums over the rows, each accumulated in float64 from the float32 per-row terms and rounded to float32 once:
+ *   policy_loss   = -(sum surr) / B;  value_loss = (sum dv * dv) / B
+ *   approx_kl     = (sum ((ratio - 1.0f) - lr)) / B;  clip_fraction = (rows with fabsf(ratio - 1.0f) > clip_range) / B
+ *   grad_log_std[j] = (float)(sum g * fmaf(z_j, z_j, -1.0f)) - ent_coef
+ *   entropy_loss  = -(e_0 + e_1 + ..), e_j = 1.418938533f + log_std[j], from 0.0f in the order of j
+ *   loss          = fmaf(vf_coef, value_loss, fmaf(ent_coef, entropy_loss, policy_loss))
+ * stats: loss, policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction, m, s (0 and 1 without normalisation).
+ * m and s: a group of the first launch forms the float64 sum of its advantages, then -- reading them again -- the float64 sum
+ * of the float32 squares (adv - c)^2 about c = the float32 of its own mean; m is the float64 sum of the groups' sums over B, and
+ * the squares are moved from the groups' centres to m in float64 (sum (x - m)^2 = sum (x - c)^2 + 2 (c - m) sum (x - c) +
+ * n_g (c - m)^2, exact algebra between numbers of the same size: nothing cancels, as it would in sum x^2 - n m^2).
+ * v == NULL: no critic; grad_v must be NULL too, value_loss is 0 and returns is not read.
+ * Reproducible: no floating-point atomics.  A bounded grid of at most 256 groups of 256 lanes, a lane taking every 256th row of
+ * a pass of 1 024; a group's sums are added over the lanes by a fixed tree and the groups' partials in group order, so the
+ * bits depend on the inputs, on a row's position in the minibatch and on B only: two calls give the same bits, and rows reached
+ * through row_index the bits of the same rows laid out densely.  At most three launches (moments, rows, final sums; two
+ * without normalisation).  The workspace (32 KiB) belongs to the actor: allocated at its first head call, freed by
+ * dockauv_policy_destroy.  Every head call on one actor uses that one workspace, so the calls on one actor must be ordered on
+ * one stream (or by events): two calls on different streams race on it.  The first call on an actor allocates (hipMalloc, which
+ * synchronises the device), so make it before a stream capture, not inside one; later calls allocate nothing.  The same two
+ * rules hold for dockauv_policy_backward and its partial sums.
+ * Refused before any device call, the message naming the field: a NULL handle, policy or io; a critic as `actor`; an actor
+ * without log_std or with out_act == DOCKAUV_ACT_TANH (as dockauv_policy_forward_logp); a wrong struct_size; n_rows < 1, or
+ * < 2 with normalize_advantage; clip_range <= 0; a NULL mean / actions / log_prob_old / advantages / grad_mean / grad_log_std /
+ * stats; returns NULL with a critic; exactly one of v and grad_v NULL.
+ */
+typedef struct dockauv_ppo_head_io {
+    uint32_t struct_size;          /* sizeof(dockauv_ppo_head_io): ABI check */
+    int32_t normalize_advantage;
+    const float *mean, *v;         /* [B][n_out]; [B], NULL: no critic (value terms 0, grad_v must be NULL) */
+    const float *actions, *log_prob_old, *advantages, *returns;   /* row arrays, read at row_index[r] */
+    const int64_t* row_index;      /* nullable [B]; duplicates allowed; range is the caller's contract */
+    long long n_rows;              /* B >= 1; >= 2 with normalize_advantage */
+    float clip_range, vf_coef, ent_coef;   /* clip_range > 0 */
+    int32_t reserved;
+    float *grad_mean, *grad_v, *grad_log_std;   /* [B][n_out], [B], [n_out]: overwritten; must not alias the inputs */
+    float* stats;                  /* [8]: loss, policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction, adv mean, adv std */
+} dockauv_ppo_head_io;
+int dockauv_ppo_head(dockauv_handle h, dockauv_policy actor, const dockauv_ppo_head_io* io, void* hip_stream);
 
 #ifdef __cplusplus
 }
