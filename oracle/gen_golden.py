@@ -4,6 +4,9 @@ oracle/gen_golden.py -- generate the golden vectors under tests/golden/ by IMPOR
 (/root/reference, present only in the build container; never on the GPU box).
 
 TEST INFRASTRUCTURE ONLY.  Run:  python oracle/gen_golden.py            (re-creates tests/golden/*.npz)
+                                 python oracle/gen_golden.py --vehicles-only   (G1 / G2 / G3 only: g1_constants, g2_state_dot,
+                                 g3_auv_step; the others, --mixed-partner-only, --near-only, --ram-only, write the trajectory
+                                 fixtures that were added later and leave the rest alone)
 
 The reference needs two third-party packages that are not installed here (``gym`` ~0.21 and
 ``skimage.measure.block_reduce``); both are replaced by minimal in-memory stand-ins *inside this script
@@ -123,6 +126,11 @@ def vehicles():
         "bluerov2_direct": BlueROV2(control_mode="direct"),
         "bluerov2_testxml": BlueROV2(test_xml),
         "lauv": LAUV(),
+        # vehicles outside the structural (symmetric) form: x_G, y_G, x_B, y_B, I_xy, I_yz != 0 (tests/golden/*_asym_params.xml).
+        # LAST: the generators below share one RandomState across vehicles, so every earlier array regenerates unchanged
+        "bluerov2_asym": BlueROV2(os.path.join(OUT, "bluerov2_asym_params.xml")),
+        "bluerov2_direct_asym": BlueROV2(os.path.join(OUT, "bluerov2_asym_params.xml"), control_mode="direct"),
+        "lauv_asym": LAUV(os.path.join(OUT, "lauv_asym_params.xml")),
     }
 
 
@@ -662,6 +670,11 @@ if __name__ == "__main__":
         sys.exit(0)
     if "--ram-only" in sys.argv:              # added in round 3
         gen_lauv_collision()
+        sys.exit(0)
+    if "--vehicles-only" in sys.argv:         # G1 / G2 / G3 only (the asymmetric vehicles were added to them)
+        gen_constants()
+        gen_state_dot()
+        gen_auv_step()
         sys.exit(0)
     gen_constants()
     gen_state_dot()

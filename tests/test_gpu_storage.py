@@ -95,18 +95,25 @@ def _oracle_for(g):
 
 @pytest.mark.parametrize("precision", ["f64", "f32"])
 def test_state_dot_output_matches_oracle(precision):
-    """dockauv_step_io.state_dot (AUVSim._state_dot, auvsim.py:108) on random states against the oracle's auv_step."""
+    """dockauv_step_io.state_dot (AUVSim._state_dot, auvsim.py:108) on random states against the oracle's auv_step: the shipped
+    vehicles, and the asymmetric ones (tests/golden/*_asym_params.xml: the post-step RHS with the general kinetics expressions)."""
+    import copy
     from gym_dockauv_amd import _capi
+    from gym_dockauv_amd.config.env_config import BASE_CONFIG
     from gym_dockauv_amd.envs.batched import BatchedDocking3d
+    from gym_dockauv_amd.objects.vehicle_models import BlueROV2, LAUV
     from oracle import dockauv_oracle as orc
-    for veh, h in (("BlueROV2", 0.1), ("LAUV", 0.02)):
-        import copy
-        from gym_dockauv_amd.config.env_config import BASE_CONFIG
+    from tests.test_oracle_golden import GOLDEN, xml_params
+    import os
+    for veh, h, xml in (("BlueROV2", 0.1, None), ("LAUV", 0.02, None),
+                        ("BlueROV2", 0.1, "bluerov2_asym_params.xml"), ("LAUV", 0.02, "lauv_asym_params.xml")):
         cfg = copy.deepcopy(BASE_CONFIG)
         cfg["vehicle"], cfg["t_step_size"] = veh, h
         N = 96
         rs = np.random.RandomState(3)
-        env = BatchedDocking3d(cfg, num_envs=N, scenario="SimpleCurrentDocking3d", precision=precision, reset_mode="none", rng="batched")
+        vm = None if xml is None else [{"BlueROV2": BlueROV2, "LAUV": LAUV}[veh](os.path.join(GOLDEN, xml))]
+        env = BatchedDocking3d(cfg, num_envs=N, scenario="SimpleCurrentDocking3d", precision=precision, reset_mode="none", rng="batched",
+                               vehicle_models=vm)
         try:
             env._gen = np.random.default_rng(2)
             env.reset()
@@ -117,13 +124,16 @@ def test_state_dot_output_matches_oracle(precision):
             a = rs.uniform(-1, 1, (N, env.n_u))
             env.step(a, extras=True)
             sd = np.asarray(env.state_dot, dtype=np.float64)
-            model = orc.VehicleModel(orc.VEHICLE_KINDS[veh])
+            model = orc.VehicleModel(orc.VEHICLE_KINDS[veh], None if xml is None else xml_params(xml))
+            worst = 0.0
             for i in range(N):
                 c = orc.CurrentState(mu=0.005, V_min=cur[i, 1], V_max=cur[i, 2], V_c=cur[i, 0], alpha=cur[i, 3], beta=cur[i, 4], sigma=0.0)
                 c.sim(h, 0.0)
                 nu_c = c.body(state[i, 3:6])
                 _, _, sd_ref = orc.auv_step(model, state[i], np.zeros(model.n_u), a[i, :model.n_u], nu_c, h)
+                worst = max(worst, np.abs(sd[i] - sd_ref).max())
                 np.testing.assert_allclose(sd[i], sd_ref, rtol=1e-7 if precision == "f64" else 2e-3, atol=1e-8 if precision == "f64" else 2e-4)
+            print(f"[state_dot {precision}] {veh} {xml or 'shipped'}: max |state_dot - oracle| {worst:.3e}")
         finally:
             env.close()
 
