@@ -1,87 +1,17 @@
 // dockauv_capi.hip -- C ABI of libdockauv.so (include/dockauv.h): handle, HBM buffers, field I/O, step launch.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <string>
-#include <vector>
 
-#include "../../include/dockauv.h"
-#include "dockauv_device.h"
+#include "dockauv_capi.h"
 
-namespace dockauv {
-thread_local std::string g_create_error;   // dockauv_last_error(NULL); shared with dockauv_p2p.hip
-// dockauv_p2p.hip
-int launch_gather(const dockauv_p2p_plan* pl, const void* src, uint32_t stamp, uint32_t wait_stamp, hipStream_t stream);
-}
 using namespace dockauv;
 
-namespace {
+namespace dockauv {
 
-struct FieldDesc {
-    void* base;   // device base of row 0
-    int rows;     // device rows
-    int kind;     // 0 = T, 1 = int32, 2 = uint8
-};
-
-}  // namespace
-
-struct dockauv_env_s {
-    dockauv_config cfg;
-    int device = 0;
-    bool f64 = false;
-    size_t tsz = 4;
-    long S = 0;   // SoA row stride (envs rounded up to 64)
-    int n_rays = 0, n_red = 0, n_obs = 0, n_u_max = 0;
-    double fan_cos = -1.0, fan_sin = 0.0, sum_beta = 0.0;   // cone around the ray fan, sum of the ray weights
-    int vk = VK_JOY;
-    bool has_rays = false;
-    bool sym = false;
-    int threads = 64;
-    Buffers B{};
-    std::vector<void*> allocs;
-    KernelArgs<float, 2> a32{};
-    KernelArgs<double, 2> a64{};
-    std::string err;
-    bool seq_resident = true;   // dockauv_set_option(DOCKAUV_OPT_SEQUENCE_RESIDENT)
-    volatile unsigned int* status_host = nullptr;   // the kernels' sticky status word: pinned, host-coherent, mapped into the device
-    hipStream_t last_stream = nullptr;
-    // host-pointer step staging
-    void* d_actions = nullptr;
-    void* d_noise = nullptr;
-    float* d_obs = nullptr;
-    void* d_reward = nullptr;
-    uint8_t* d_done = nullptr;
-    void* d_terms = nullptr;
-    uint8_t* d_cond = nullptr;
-    void* d_nav = nullptr;
-    void* d_raydist = nullptr;
-    float* d_termobs = nullptr;
-    void* d_statedot = nullptr;
-    // pinned host mirrors of the above (dockauv_step_host), allocated on first use
-    struct Pinned {
-        void* actions = nullptr; void* noise = nullptr; float* obs = nullptr; void* reward = nullptr;
-        uint8_t* done = nullptr; void* terms = nullptr; uint8_t* cond = nullptr; void* nav = nullptr;
-        void* raydist = nullptr; float* termobs = nullptr; void* statedot = nullptr;
-        bool ready = false;
-    } pin;
-    std::vector<void*> pinned_allocs;
-    hipStream_t host_stream = nullptr;
-    void* ride_plans_dev = nullptr;                 // device copies of the caller's gather plans (lag-1 sequences)
-    std::vector<unsigned char> ride_plans_host;
-    hipEvent_t ev_step[2] = {nullptr, nullptr};     // dockauv_step_gather_sequence: step kernel / gather of row buffer k
-    hipEvent_t ev_gather[2] = {nullptr, nullptr};
-    // episode-storage trace (dockauv_trace_*): ring buffers + their device-side description
-    TraceDev trace{};
-    void* trace_dev = nullptr;                      // device copy of `trace`
-    std::vector<void*> trace_allocs;
-    long long trace_step = 0;
-};
-
-namespace {
+thread_local std::string g_create_error;   // dockauv_last_error(NULL)
 
 int fail(dockauv_handle h, int code, const char* fmt, ...) {
     char buf[512];
@@ -92,12 +22,6 @@ int fail(dockauv_handle h, int code, const char* fmt, ...) {
     if (h) h->err = buf; else g_create_error = buf;
     return code;
 }
-
-#define HIP_TRY(h, expr)                                                                                   \
-    do {                                                                                                   \
-        hipError_t e_ = (expr);                                                                            \
-        if (e_ != hipSuccess) return fail(h, DOCKAUV_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 // Sticky status word of the handle's kernels.  It lives in pinned host memory that the device maps (coherent): a kernel
 // that gives up a wait ORs its bit in over the bus (the failure path only), and the host reads the word with a plain load --
@@ -112,6 +36,21 @@ int check_status(dockauv_handle h) {
                     "results since are invalid, destroy the handle", v);
     return 0;
 }
+
+int sync_last(dockauv_handle h) {
+    if (h->last_stream) HIP_TRY(h, hipStreamSynchronize(h->last_stream)); else HIP_TRY(h, hipDeviceSynchronize());
+    return 0;
+}
+
+}  // namespace dockauv
+
+namespace {
+
+struct FieldDesc {
+    void* base;   // device base of row 0
+    int rows;     // device rows
+    int kind;     // 0 = T, 1 = int32, 2 = uint8
+};
 
 int dalloc(dockauv_handle h, void** p, size_t bytes) {
     if (bytes == 0) bytes = 256;
@@ -208,11 +147,8 @@ void fill_env(EnvP<T>& e, const dockauv_env_s& h) {
     e.ray_max = (T)c.radar_max_dist;
     e.alpha_max = (T)c.radar_alpha_max;
     e.beta_max = (T)c.radar_beta_max;
-    int pad = 1;
-    while (pad < h.n_rays) pad *= 2;
-    e.ray_pad = pad;
-    e.ray_pad_log2 = 0;
-    while ((1 << e.ray_pad_log2) < pad) ++e.ray_pad_log2;
+    e.ray_pad_log2 = ceil_log2(h.n_rays);
+    e.ray_pad = 1 << e.ray_pad_log2;
     e.device_noise = c.device_noise ? 1 : 0;
     e.fan_cos = (T)h.fan_cos;
     e.fan_sin = (T)h.fan_sin;
@@ -299,7 +235,146 @@ void set_io(StepIO& d, const dockauv_step_io& s) {
     d.pack = s.pack_reward_done == 2 ? 2 : (s.pack_reward_done ? 1 : 0);
 }
 
-int launch(dockauv_handle h, const dockauv_step_io* io, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
+// dockauv_create behind its validation: fills the fresh handle `h` and allocates everything it owns.  A failure is reported
+// through fail(h, ...); the caller destroys the handle.
+int init_handle(dockauv_handle h, const dockauv_config& c, int device) {
+    h->cfg = c;
+    h->cfg.ray_table = nullptr;
+    h->device = device;
+    h->f64 = c.precision == DOCKAUV_F64;
+    h->tsz = h->f64 ? 8 : 4;
+    h->S = ((long)c.n_envs + 63) / 64 * 64;
+    h->n_rays = c.n_v * c.n_h;
+    {
+        // circular cone around the body x axis that contains every ray of the fan, widened by 1e-3 rad (used to skip
+        // obstacles no ray can reach), and the sum of the obstacle-avoidance weights
+        double min_bx = 1.0, sb = 0.0;
+        for (int r = 0; r < h->n_rays; ++r) {
+            const double* q = c.ray_table + (size_t)r * 4;
+            const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
+            min_bx = std::min(min_bx, q[0] / n);
+            sb += q[3];
+        }
+        const double half = std::min(std::acos(std::max(-1.0, std::min(1.0, min_bx))) + 1e-3, 3.14159265358979);
+        h->fan_cos = std::cos(half);
+        h->fan_sin = std::sin(half);
+        h->sum_beta = sb;
+    }
+    const int blk = c.blocksize_reduce;
+    h->n_red = ((c.n_v + blk - 1) / blk) * ((c.n_h + blk - 1) / blk);
+    h->n_obs = DOCKAUV_N_OBS_BASE + h->n_red;
+    h->n_u_max = c.vehicle[0].n_u;
+    if (c.n_vehicles == 2 && c.vehicle[1].n_u > h->n_u_max) h->n_u_max = c.vehicle[1].n_u;
+    h->has_rays = (c.max_capsules + c.max_spheres) > 0;
+    h->threads = choose_threads(h->f64, c.n_envs, h->n_rays, c.max_capsules, c.max_spheres, c.n_vehicles, c.threads_per_group);
+    if (c.n_vehicles == 2) {
+        if (!(c.vehicle[0].kind == DOCKAUV_VEH_CONSTB && b_is_diagonal(c.vehicle[0]) && c.vehicle[1].kind == DOCKAUV_VEH_LAUV))
+            return fail(h, DOCKAUV_E_INVALID, "mixed batches support vehicle[0] = diagonal-B (BlueROV2 joystick), vehicle[1] = LAUV");
+        h->vk = VK_MIXED;
+    } else if (c.vehicle[0].kind == DOCKAUV_VEH_LAUV) {
+        h->vk = VK_LAUV;
+    } else {
+        h->vk = b_is_diagonal(c.vehicle[0]) ? VK_JOY : VK_DENSEB;
+    }
+
+    h->sym = true;
+    for (int v = 0; v < c.n_vehicles; ++v) h->sym = h->sym && is_symmetric_vehicle(c.vehicle[v]);
+    if (c.envs_per_group == -1) h->sym = false;   // test hook: force the general expressions
+
+    const size_t S = (size_t)h->S, t = h->tsz, N = (size_t)c.n_envs;
+    const size_t caps = (size_t)c.max_capsules * 7 * S * t, sph = (size_t)c.max_spheres * 4 * S * t;
+    Buffers& B = h->B;
+    B.stride = h->S;
+    void *rays_dev = nullptr, *lt_dev = nullptr, *lc_dev = nullptr, *pdev = nullptr;   // (lane table: Buffers::lane_tab)
+    const size_t pbytes = h->f64 ? sizeof(h->a64.P) : sizeof(h->a32.P);
+    // host-pointer staging: the sizes of the arrays of dockauv_step_io
+    const size_t stage_bytes[ST_COUNT] = {N * h->n_u_max * t, N * t, N * h->n_obs * 4, N * t, N, N * kNRew * t, N, N * 4 * t,
+                                          N * h->n_rays * t, N * h->n_obs * 4, N * 12 * t};
+    for (int k = 0; k < ST_COUNT; ++k) h->stage[k].bytes = stage_bytes[k];
+    const struct { void** p; size_t bytes; } device_arrays[] = {
+        {&B.state, 12 * S * t}, {&B.pos_lo, kLoRows * S * t}, {&B.u, kMaxU * S * t}, {&B.goal, 4 * S * t}, {&B.cur, 8 * S * t},
+        {&B.cum_reward, S * t}, {(void**)&B.t_steps, S * 4}, {(void**)&B.episode, S * 4}, {(void**)&B.veh_id, S},
+        {&B.cur_sigma, S * t}, {&B.caps, caps}, {&B.sph, sph}, {&B.p_pose, 6 * S * t}, {&B.p_goal, 4 * S * t},
+        {&B.p_cur, 8 * S * t}, {&B.p_caps, caps}, {&B.p_sph, sph}, {&rays_dev, (size_t)h->n_rays * 4 * t},
+        {&lt_dev, (size_t)64 * 4 * t}, {&lc_dev, (size_t)64 * 4}, {&pdev, pbytes}};
+    for (const auto& d : device_arrays)
+        if (int rc = dalloc(h, d.p, d.bytes)) return rc;
+    for (auto& st : h->stage)
+        if (int rc = dalloc(h, &st.dev, st.bytes)) return rc;
+    hipError_t e;
+    {
+        std::vector<unsigned char> tmp((size_t)h->n_rays * 4 * t);
+        for (int i = 0; i < h->n_rays * 4; ++i) store_elem(h, 0, tmp.data(), i, c.ray_table[i]);
+        e = hipMemcpy(rays_dev, tmp.data(), tmp.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(h, DOCKAUV_E_HIP, "ray table upload: %s", hipGetErrorString(e));
+    }
+    B.rays = rays_dev;
+    if (h->n_rays <= 64) {
+        // lane table of the lane = ray stage (dockauv_device.h: Buffers::lane_tab)
+        const int pad = 1 << ceil_log2(h->n_rays);
+        const int n_hr = (c.n_h + blk - 1) / blk;
+        std::vector<unsigned char> tmp((size_t)64 * 4 * t);
+        int32_t cells[64];
+        for (int l = 0; l < 64; ++l) {
+            const int r = l % pad;
+            const bool ok = r < h->n_rays;
+            const double dir[4] = {ok ? c.ray_table[r * 4 + 0] : 1.0, ok ? c.ray_table[r * 4 + 1] : 0.0,
+                                   ok ? c.ray_table[r * 4 + 2] : 0.0, ok ? c.ray_table[r * 4 + 3] : 0.0};
+            for (int k = 0; k < 4; ++k) store_elem(h, 0, tmp.data(), (size_t)l * 4 + k, dir[k]);
+            const int iv = ok ? r / c.n_h : 0, ih = ok ? r % c.n_h : 0;
+            cells[l] = (iv / blk) * n_hr + ih / blk;
+        }
+        e = hipMemcpy(lt_dev, tmp.data(), tmp.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(lc_dev, cells, sizeof cells, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(h, DOCKAUV_E_HIP, "lane table upload: %s", hipGetErrorString(e));
+    }
+    B.lane_tab = lt_dev;
+    B.lane_cell = static_cast<const int32_t*>(lc_dev);
+    {
+        // sticky status word (dockauv_device.h: Buffers::status): host-coherent, mapped (see check_status)
+        void* st_host = nullptr;
+        void* st_dev = nullptr;
+        e = hipHostMalloc(&st_host, 256, hipHostMallocMapped | hipHostMallocCoherent);
+        if (e == hipSuccess) {
+            memset(st_host, 0, 256);
+            h->pinned_allocs.push_back(st_host);
+            e = hipHostGetDevicePointer(&st_dev, st_host, 0);
+        }
+        if (e != hipSuccess) return fail(h, DOCKAUV_E_HIP, "status word (mapped host memory): %s", hipGetErrorString(e));
+        h->status_host = static_cast<volatile unsigned int*>(st_host);
+        B.status = static_cast<unsigned int*>(st_dev);
+    }
+    if (h->f64) {
+        fill_env(h->a64.P.E, *h);
+        for (int v = 0; v < c.n_vehicles; ++v) fill_vehicle(h->a64.P.V[v], c.vehicle[v]);
+        h->a64.B = B;
+    } else {
+        fill_env(h->a32.P.E, *h);
+        for (int v = 0; v < c.n_vehicles; ++v) fill_vehicle(h->a32.P.V[v], c.vehicle[v]);
+        h->a32.B = B;
+    }
+    // the parameter block is read by the kernel from device memory (dockauv_device.h: ParamBlock)
+    e = hipMemcpy(pdev, h->f64 ? (const void*)&h->a64.P : (const void*)&h->a32.P, pbytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(h, DOCKAUV_E_HIP, "parameter block upload: %s", hipGetErrorString(e));
+    h->a32.params_dev = h->a64.params_dev = pdev;
+    // the dynamic-LDS request must fit the 160 KiB of a gfx950 CU
+    const size_t lds = h->f64 ? lds_bytes<double>(64, 512, c.max_capsules, c.max_spheres, h->n_obs, h->has_rays)
+                              : lds_bytes<float>(64, 512, c.max_capsules, c.max_spheres, h->n_obs, h->has_rays);
+    if (lds > 160 * 1024)
+        return fail(h, DOCKAUV_E_INVALID, "configuration needs %zu B of LDS per group (> 160 KiB): fewer rays/obstacles", lds);
+    return 0;
+}
+
+// what select_step / select_sequence are asked (dockauv_device.h): the handle's constants and what this step's io wants
+StepRequest step_request(dockauv_handle h, const dockauv_step_io& io, bool ride) {
+    const bool extras = io.noise || io.reward_terms || io.conditions || io.nav || io.ray_dist || io.state_dot || h->trace_dev || h->cfg.device_noise;
+    return StepRequest{h->f64, h->sym, h->vk, h->has_rays, h->threads, h->cfg.n_envs, ceil_log2(h->n_rays), h->cfg.reset_mode,
+                       h->cfg.reward_set, extras, io.terminal_obs != nullptr, io.pack_reward_done == 2 ? 2 : (io.pack_reward_done ? 1 : 0), ride};
+}
+
+}  // namespace
+
+int dockauv::launch(dockauv_handle h, const dockauv_step_io* io, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
     int rc;
     StepIO& sio = h->f64 ? h->a64.io : h->a32.io;
     if (h->trace_dev) {
@@ -313,20 +388,14 @@ int launch(dockauv_handle h, const dockauv_step_io* io, hipStream_t stream, hipE
     sio.trace = h->trace_dev;
     sio.trace_step = h->trace_dev ? h->trace_step : 0;
     sio.device_noise = (h->cfg.device_noise && !io->noise) ? 1 : 0;
-    if (h->f64) {
-        set_io(h->a64.io, *io);
-        rc = launch_step_f64(h->a64, h->vk, h->sym, h->has_rays, h->threads, stream, ev0, ev1);
-    } else {
-        set_io(h->a32.io, *io);
-        rc = launch_step_f32(h->a32, h->vk, h->sym, h->has_rays, h->threads, stream, ev0, ev1);
-    }
+    set_io(sio, *io);
+    const StepRequest r = step_request(h, *io, h->a32.ride.plan != nullptr);
+    rc = h->f64 ? launch_step_f64(h->a64, r, stream, ev0, ev1) : launch_step_f32(h->a32, r, stream, ev0, ev1);
     if (rc != 0) return fail(h, DOCKAUV_E_HIP, "step kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     if (h->trace_dev) ++h->trace_step;   // (only a launch that went out has written its row)
     h->last_stream = stream;
     return 0;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -390,219 +459,11 @@ int dockauv_create(const dockauv_config* cfg, int device, dockauv_handle* out) {
     if (e != hipSuccess) return fail(nullptr, DOCKAUV_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
 
     dockauv_handle h = new dockauv_env_s();
-    h->cfg = c;
-    h->cfg.ray_table = nullptr;
-    h->device = device;
-    h->f64 = c.precision == DOCKAUV_F64;
-    h->tsz = h->f64 ? 8 : 4;
-    h->S = ((long)c.n_envs + 63) / 64 * 64;
-    h->n_rays = c.n_v * c.n_h;
-    {
-        // circular cone around the body x axis that contains every ray of the fan, widened by 1e-3 rad (used to skip
-        // obstacles no ray can reach), and the sum of the obstacle-avoidance weights
-        double min_bx = 1.0, sb = 0.0;
-        for (int r = 0; r < h->n_rays; ++r) {
-            const double* q = c.ray_table + (size_t)r * 4;
-            const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
-            min_bx = std::min(min_bx, q[0] / n);
-            sb += q[3];
-        }
-        const double half = std::min(std::acos(std::max(-1.0, std::min(1.0, min_bx))) + 1e-3, 3.14159265358979);
-        h->fan_cos = std::cos(half);
-        h->fan_sin = std::sin(half);
-        h->sum_beta = sb;
-    }
-    const int blk = c.blocksize_reduce;
-    h->n_red = ((c.n_v + blk - 1) / blk) * ((c.n_h + blk - 1) / blk);
-    h->n_obs = DOCKAUV_N_OBS_BASE + h->n_red;
-    h->n_u_max = c.vehicle[0].n_u;
-    if (c.n_vehicles == 2 && c.vehicle[1].n_u > h->n_u_max) h->n_u_max = c.vehicle[1].n_u;
-    h->has_rays = (c.max_capsules + c.max_spheres) > 0;
-    // threads per 64-env group: the ray stage spreads over all waves of the group.  Heavy fans on small batches
-    // (fewer than ~2 resident waves per SIMD at 256 threads) get 8 waves per group; measured on MI355X: LAUV,
-    // 63 rays x 5 capsules, 32 768 envs: 27.5 -> 22.8 us; at 65 536+ envs 256 threads are faster.
-    // Without obstacles extra waves per group (bookkeeper, resetter, second observation wave: the tail of the step cut
-    // in two or four) shorten the step while the chip has idle SIMDs; at very large batches one wave per group does
-    // the least total work.
-    if (c.threads_per_group > 0) h->threads = c.threads_per_group;
-    else if (!h->has_rays) h->threads = c.n_envs <= 65536 ? 256 : (c.n_envs <= 131072 ? 128 : 64);
-    else {
-        // Beyond the batch sizes at which every group is resident at once, ONE wave per group does the least total work and
-        // -- since round 4, when its LDS footprint was halved (dockauv_step.hip.inc: SOLO; 16 instead of 8 groups per CU for
-        // config 3's fan) -- keeps the most groups in flight.  Same-box measurements (profiles/r4/threads_large.txt), light
-        // fan (config 3, 16 beams x 8 spheres) 64 against 256 threads: 131 072 envs 18.4 / 16.7 us, 196 608: 23.0 / 26.0,
-        // 262 144: 27.0 / 34.3, 524 288: 50.9 / 69.3, 1 048 576: 117.9 / 175.7; heavy fan (config 4, 63 rays x 5 capsules):
-        // 524 288: 115.6 / 113.7, 1 048 576: 236 / 251; mixed vehicles (config 5): 256 threads at every size (229 / 251 at 1 M).
-        // One-wave groups of the 63-ray fan against <= 5 capsules keep their completed records in registers (float32:
-        // dockauv_step.hip.inc: regrec; 8 -> 16 groups per CU); 64 against 256 threads with that (profiles/r4/threads_large.txt,
-        // second table): config 4 163 840 envs 41.4 / 38.2 us, 196 608: 43.1 / 43.8, 262 144: 51.0 / 56.9, 393 216: 69.3 / 82.8,
-        // 1 048 576: 154 / 246; config 5 (mixed) 262 144: 53.6 / 50.0, 393 216: 74.5 / 73.9, 524 288: 86.3 / 94.7,
-        // 1 048 576: 161 / 215 (vehicle-sorted: 154 / 211).
-        const long tests = (long)h->n_rays * (c.max_capsules + c.max_spheres);
-        const bool light = tests < 256;
-        int pad_log2 = 0;
-        while ((1 << pad_log2) < h->n_rays) ++pad_log2;
-        const bool regrec = !h->f64 && solo_regrec(c.max_capsules, c.max_spheres, pad_log2);
-        if (!light && c.n_envs <= 32768) h->threads = 512;
-        else if (light) h->threads = c.n_envs > 163840 ? 64 : 256;
-        else if (regrec) h->threads = c.n_envs > (c.n_vehicles == 1 ? 196608 : 393216) ? 64 : 256;
-        else h->threads = (c.n_vehicles == 1 && c.n_envs > 786432) ? 64 : 256;
-    }
-    if (c.n_vehicles == 2) {
-        if (!(c.vehicle[0].kind == DOCKAUV_VEH_CONSTB && b_is_diagonal(c.vehicle[0]) && c.vehicle[1].kind == DOCKAUV_VEH_LAUV)) {
-            delete h;
-            return fail(nullptr, DOCKAUV_E_INVALID, "mixed batches support vehicle[0] = diagonal-B (BlueROV2 joystick), vehicle[1] = LAUV");
-        }
-        h->vk = VK_MIXED;
-    } else if (c.vehicle[0].kind == DOCKAUV_VEH_LAUV) {
-        h->vk = VK_LAUV;
-    } else {
-        h->vk = b_is_diagonal(c.vehicle[0]) ? VK_JOY : VK_DENSEB;
-    }
-
-    h->sym = true;
-    for (int v = 0; v < c.n_vehicles; ++v) h->sym = h->sym && is_symmetric_vehicle(c.vehicle[v]);
-    if (c.envs_per_group == -1) h->sym = false;   // test hook: force the general expressions
-
-    const size_t S = (size_t)h->S, t = h->tsz;
-    int rc = 0;
-    Buffers& B = h->B;
-    B.stride = h->S;
-#define ALLOC(ptr, bytes)                                  \
-    if ((rc = dalloc(h, (void**)&(ptr), (bytes))) != 0) {  \
-        g_create_error = h->err;                           \
-        dockauv_destroy(h);                                \
-        return rc;                                         \
-    }
-    ALLOC(B.state, 12 * S * t);
-    ALLOC(B.pos_lo, kLoRows * S * t);
-    ALLOC(B.u, kMaxU * S * t);
-    ALLOC(B.goal, 4 * S * t);
-    ALLOC(B.cur, 8 * S * t);
-    ALLOC(B.cum_reward, S * t);
-    ALLOC(B.t_steps, S * 4);
-    ALLOC(B.episode, S * 4);
-    ALLOC(B.veh_id, S);
-    ALLOC(B.cur_sigma, S * t);
-    ALLOC(B.caps, (size_t)c.max_capsules * 7 * S * t);
-    ALLOC(B.sph, (size_t)c.max_spheres * 4 * S * t);
-    ALLOC(B.p_pose, 6 * S * t);
-    ALLOC(B.p_goal, 4 * S * t);
-    ALLOC(B.p_cur, 8 * S * t);
-    ALLOC(B.p_caps, (size_t)c.max_capsules * 7 * S * t);
-    ALLOC(B.p_sph, (size_t)c.max_spheres * 4 * S * t);
-    void* rays_dev = nullptr;
-    ALLOC(rays_dev, (size_t)h->n_rays * 4 * t);
-    {
-        std::vector<unsigned char> tmp((size_t)h->n_rays * 4 * t);
-        for (int i = 0; i < h->n_rays * 4; ++i) store_elem(h, 0, tmp.data(), i, c.ray_table[i]);
-        e = hipMemcpy(rays_dev, tmp.data(), tmp.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            fail(nullptr, DOCKAUV_E_HIP, "ray table upload: %s", hipGetErrorString(e));
-            dockauv_destroy(h);
-            return DOCKAUV_E_HIP;
-        }
-    }
-    B.rays = rays_dev;
-    {
-        // lane table of the lane = ray stage (dockauv_device.h: Buffers::lane_tab)
-        void* lt_dev = nullptr;
-        int32_t* lc_dev = nullptr;
-        ALLOC(lt_dev, (size_t)64 * 4 * t);
-        ALLOC(lc_dev, (size_t)64 * 4);
-        if (h->n_rays <= 64) {
-            int pad = 1;
-            while (pad < h->n_rays) pad *= 2;
-            const int blk_ = c.blocksize_reduce, n_hr = (c.n_h + blk_ - 1) / blk_;
-            std::vector<unsigned char> tmp((size_t)64 * 4 * t);
-            int32_t cells[64];
-            for (int l = 0; l < 64; ++l) {
-                const int r = l % pad;
-                const bool ok = r < h->n_rays;
-                const double dir[4] = {ok ? c.ray_table[r * 4 + 0] : 1.0, ok ? c.ray_table[r * 4 + 1] : 0.0,
-                                       ok ? c.ray_table[r * 4 + 2] : 0.0, ok ? c.ray_table[r * 4 + 3] : 0.0};
-                for (int k = 0; k < 4; ++k) store_elem(h, 0, tmp.data(), (size_t)l * 4 + k, dir[k]);
-                const int iv = ok ? r / c.n_h : 0, ih = ok ? r % c.n_h : 0;
-                cells[l] = (iv / blk_) * n_hr + ih / blk_;
-            }
-            e = hipMemcpy(lt_dev, tmp.data(), tmp.size(), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(lc_dev, cells, sizeof cells, hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                fail(nullptr, DOCKAUV_E_HIP, "lane table upload: %s", hipGetErrorString(e));
-                dockauv_destroy(h);
-                return DOCKAUV_E_HIP;
-            }
-        }
-        B.lane_tab = lt_dev;
-        B.lane_cell = lc_dev;
-    }
-    {
-        // sticky status word (dockauv_device.h: Buffers::status): host-coherent, mapped (see check_status)
-        void* st_host = nullptr;
-        void* st_dev = nullptr;
-        e = hipHostMalloc(&st_host, 256, hipHostMallocMapped | hipHostMallocCoherent);
-        if (e == hipSuccess) {
-            memset(st_host, 0, 256);
-            h->pinned_allocs.push_back(st_host);
-            e = hipHostGetDevicePointer(&st_dev, st_host, 0);
-        }
-        if (e != hipSuccess) {
-            fail(nullptr, DOCKAUV_E_HIP, "status word (mapped host memory): %s", hipGetErrorString(e));
-            dockauv_destroy(h);
-            return DOCKAUV_E_HIP;
-        }
-        h->status_host = static_cast<volatile unsigned int*>(st_host);
-        B.status = static_cast<unsigned int*>(st_dev);
-    }
-    // host-pointer staging buffers
-    const size_t N = (size_t)c.n_envs;
-    ALLOC(h->d_actions, N * h->n_u_max * t);
-    ALLOC(h->d_noise, N * t);
-    ALLOC(h->d_obs, N * h->n_obs * 4);
-    ALLOC(h->d_reward, N * t);
-    ALLOC(h->d_done, N);
-    ALLOC(h->d_terms, N * kNRew * t);
-    ALLOC(h->d_cond, N);
-    ALLOC(h->d_nav, N * 4 * t);
-    ALLOC(h->d_raydist, N * h->n_rays * t);
-    ALLOC(h->d_termobs, N * h->n_obs * 4);
-    ALLOC(h->d_statedot, N * 12 * t);
-#undef ALLOC
-
-    if (h->f64) {
-        fill_env(h->a64.P.E, *h);
-        for (int v = 0; v < c.n_vehicles; ++v) fill_vehicle(h->a64.P.V[v], c.vehicle[v]);
-        h->a64.B = B;
-    } else {
-        fill_env(h->a32.P.E, *h);
-        for (int v = 0; v < c.n_vehicles; ++v) fill_vehicle(h->a32.P.V[v], c.vehicle[v]);
-        h->a32.B = B;
-    }
-    {
-        // the parameter block is read by the kernel from device memory (dockauv_device.h: ParamBlock)
-        const void* src = h->f64 ? (const void*)&h->a64.P : (const void*)&h->a32.P;
-        const size_t bytes = h->f64 ? sizeof(h->a64.P) : sizeof(h->a32.P);
-        void* pdev = nullptr;
-        if ((rc = dalloc(h, &pdev, bytes)) != 0) {
-            g_create_error = h->err;
-            dockauv_destroy(h);
-            return rc;
-        }
-        e = hipMemcpy(pdev, src, bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            fail(nullptr, DOCKAUV_E_HIP, "parameter block upload: %s", hipGetErrorString(e));
-            dockauv_destroy(h);
-            return DOCKAUV_E_HIP;
-        }
-        h->a32.params_dev = h->a64.params_dev = pdev;
-    }
-    // the dynamic-LDS request must fit the 160 KiB of a gfx950 CU
-    size_t lds = h->f64 ? lds_bytes<double>(64, 512, c.max_capsules, c.max_spheres, h->n_obs, h->has_rays)
-                        : lds_bytes<float>(64, 512, c.max_capsules, c.max_spheres, h->n_obs, h->has_rays);
-    if (lds > 160 * 1024) {
-        fail(nullptr, DOCKAUV_E_INVALID, "configuration needs %zu B of LDS per group (> 160 KiB): fewer rays/obstacles", lds);
+    const int rc = init_handle(h, c, device);
+    if (rc != 0) {
+        g_create_error = h->err;
         dockauv_destroy(h);
-        return DOCKAUV_E_INVALID;
+        return rc;
     }
     *out = h;
     return 0;
@@ -688,8 +549,7 @@ int dockauv_get_field(dockauv_handle h, int field, int first, int count, double*
     if (first < 0 || count < 0 || (long)first + count > h->cfg.n_envs) return fail(h, DOCKAUV_E_RANGE, "env range [%d, %d) outside [0, %d)", first, first + count, h->cfg.n_envs);
     if (count == 0 || fd.rows == 0) return 0;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->last_stream) HIP_TRY(h, hipStreamSynchronize(h->last_stream)); else HIP_TRY(h, hipDeviceSynchronize());
-    if ((rc = check_status(h)) != 0) return rc;
+    if ((rc = sync_last(h)) != 0 || (rc = check_status(h)) != 0) return rc;
     const size_t es = elem_size(h, fd.kind);
     std::vector<unsigned char> tmp((size_t)fd.rows * count * es);
     const unsigned char* srcp = static_cast<const unsigned char*>(fd.base) + (size_t)first * es;
@@ -717,7 +577,7 @@ int dockauv_reset_envs(dockauv_handle h, int first, int count) {
     if (first < 0 || count < 0 || (long)first + count > h->cfg.n_envs) return fail(h, DOCKAUV_E_RANGE, "env range outside [0, %d)", h->cfg.n_envs);
     if (count == 0) return 0;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->last_stream) HIP_TRY(h, hipStreamSynchronize(h->last_stream)); else HIP_TRY(h, hipDeviceSynchronize());
+    if (int rc = sync_last(h)) return rc;
     const size_t t = h->tsz, S = (size_t)h->S;
     HIP_TRY(h, hipMemset2D(static_cast<unsigned char*>(h->B.state) + first * t, S * t, 0, count * t, 12));
     HIP_TRY(h, hipMemset2D(static_cast<unsigned char*>(h->B.pos_lo) + first * t, S * t, 0, count * t, kLoRows));
@@ -740,19 +600,13 @@ int dockauv_step(dockauv_handle h, const dockauv_step_io* io, void* hip_stream) 
 }
 
 namespace {
-// Can the steps ios[0..n) run as ONE resident launch (dockauv_step.hip.inc: step_seq_kernel)?  What the plain float32 product
-// kernels of the structural fast path serve, with packed rows of one kind: everything else is launched step by step.
+// Can the steps ios[0..n) run as ONE resident launch (dockauv_step.hip.inc: step_seq_kernel)?  Steps that select_sequence
+// has a kernel for, with packed rows of one kind: everything else is launched step by step.
 bool sequence_is_resident_material(dockauv_handle h, const dockauv_step_io* ios, int n) {
-    if (!h->seq_resident || n < 2 || h->f64 || !h->sym || h->vk == VK_DENSEB) return false;
-    int pl = 0;
-    while ((1 << pl) < h->n_rays) ++pl;
-    const bool odd_fan = h->has_rays && !(pl == 6 || pl == 4);
-    if (h->cfg.reset_mode == DOCKAUV_RESET_POOL || h->cfg.reward_set == 2 || odd_fan || h->trace_dev || h->cfg.device_noise) return false;
+    if (!h->seq_resident || n < 2) return false;
     for (int i = 0; i < n; ++i) {
-        if (ios[i].noise || ios[i].reward_terms || ios[i].conditions || ios[i].nav || ios[i].ray_dist || ios[i].terminal_obs ||
-            ios[i].state_dot || ios[i].reward || ios[i].done)
-            return false;
-        if (ios[i].pack_reward_done == 0 || ios[i].pack_reward_done != ios[0].pack_reward_done) return false;
+        if (select_sequence(step_request(h, ios[i], false)).unsupported || ios[i].reward || ios[i].done) return false;
+        if (ios[i].pack_reward_done != ios[0].pack_reward_done) return false;
     }
     return true;
 }
@@ -790,7 +644,7 @@ int dockauv_step_sequence(dockauv_handle h, const dockauv_step_io* ios, int n, v
                 seq.actions[k] = ios[i].actions;
                 seq.obs[k] = ios[i].obs;
             }
-            const int rc = launch_sequence_f32(h->a32, h->vk, h->sym, h->has_rays, h->threads, seq, (hipStream_t)hip_stream);
+            const int rc = launch_sequence_f32(h->a32, step_request(h, ios[0], false), seq, (hipStream_t)hip_stream);
             if (rc == (int)hipErrorNotSupported && i0 == 0) { fell_back = true; break; }
             if (rc != 0) return fail(h, DOCKAUV_E_HIP, "resident step sequence launch failed: %s", hipGetErrorString((hipError_t)rc));
         }
@@ -830,17 +684,16 @@ int dockauv_step_gather_sequence(dockauv_handle h, const dockauv_step_io* ios, i
     if (!two && lag == 1) {
         // the gather of step t rides in the grid of step kernel t + 1 (dockauv_ride.h); the last one is flushed by a
         // gather kernel of its own, so that on return everything queued here is covered by the stream
-        if (h->f64 || !h->sym) return fail(h, DOCKAUV_E_INVALID, "lag 1 needs the float kernels of the structural fast path");
-        {
-            // ... and a step the product instantiations serve (dockauv_step.hip.inc: launch_vk)
-            int pl = 0;
-            while ((1 << pl) < h->n_rays) ++pl;
-            const bool odd_fan = h->has_rays && !(pl == 6 || pl == 4);
-            if (h->cfg.reset_mode == DOCKAUV_RESET_POOL || h->cfg.reward_set == 2 || odd_fan || h->trace_dev || h->cfg.device_noise)
-                return fail(h, DOCKAUV_E_INVALID, "lag 1 needs the product kernels (no pool reset, reward set 1, fans of 9-16 or 33-64 rays, no logging)");
-            for (int i = 0; i < n; ++i)
-                if (ios[i].noise || ios[i].reward_terms || ios[i].conditions || ios[i].nav || ios[i].ray_dist || ios[i].terminal_obs || ios[i].state_dot)
-                    return fail(h, DOCKAUV_E_INVALID, "lag 1 needs the product kernels: step %d asks for optional inputs / outputs", i);
+        // float32, structural fast path, and steps the product instantiations serve (dockauv_device.h: select_step); first
+        // what the handle alone decides, then what each step asks for
+        StepRequest r = step_request(h, dockauv_step_io{}, true);
+        if (r.f64 || !r.sym) return fail(h, DOCKAUV_E_INVALID, "lag 1 needs the float kernels of the structural fast path");
+        if (needs_full_kernel(r))
+            return fail(h, DOCKAUV_E_INVALID, "lag 1 needs the product kernels (no pool reset, reward set 1, fans of 9-16 or 33-64 rays, no logging)");
+        for (int i = 0; i < n; ++i) {
+            r = step_request(h, ios[i], true);
+            if (r.extras || r.terminal_obs)
+                return fail(h, DOCKAUV_E_INVALID, "lag 1 needs the product kernels: step %d asks for optional inputs / outputs", i);
         }
         if (n_plans < 4) return fail(h, DOCKAUV_E_INVALID, "lag 1 needs at least 4 plans (gather buffers)");
         for (int i = 1; i < n; ++i)
@@ -931,22 +784,11 @@ int pinned_alloc(dockauv_handle h, void** p, size_t bytes) {
 }
 
 int ensure_pinned(dockauv_handle h) {
-    if (h->pin.ready) return 0;
-    const size_t N = (size_t)h->cfg.n_envs, t = h->tsz;
-    int rc;
-    if ((rc = pinned_alloc(h, &h->pin.actions, N * h->n_u_max * t))) return rc;
-    if ((rc = pinned_alloc(h, &h->pin.noise, N * t))) return rc;
-    if ((rc = pinned_alloc(h, (void**)&h->pin.obs, N * h->n_obs * 4))) return rc;
-    if ((rc = pinned_alloc(h, &h->pin.reward, N * t))) return rc;
-    if ((rc = pinned_alloc(h, (void**)&h->pin.done, N))) return rc;
-    if ((rc = pinned_alloc(h, &h->pin.terms, N * kNRew * t))) return rc;
-    if ((rc = pinned_alloc(h, (void**)&h->pin.cond, N))) return rc;
-    if ((rc = pinned_alloc(h, &h->pin.nav, N * 4 * t))) return rc;
-    if ((rc = pinned_alloc(h, &h->pin.raydist, N * h->n_rays * t))) return rc;
-    if ((rc = pinned_alloc(h, (void**)&h->pin.termobs, N * h->n_obs * 4))) return rc;
-    if ((rc = pinned_alloc(h, &h->pin.statedot, N * 12 * t))) return rc;
+    if (h->pinned_ready) return 0;
+    for (auto& st : h->stage)
+        if (int rc = pinned_alloc(h, &st.pin, st.bytes)) return rc;
     HIP_TRY(h, hipStreamCreate(&h->host_stream));   // blocking stream: ordered after the null-stream copies of set_field / reset_envs
-    h->pin.ready = true;
+    h->pinned_ready = true;
     return 0;
 }
 }  // namespace
@@ -962,42 +804,36 @@ int dockauv_step_host(dockauv_handle h, const dockauv_step_io* io) {
     if (rc) return rc;
     // work queued by the caller on another stream (dockauv_step) must be visible first
     if (h->last_stream && h->last_stream != h->host_stream) HIP_TRY(h, hipStreamSynchronize(h->last_stream));
-    const size_t N = (size_t)h->cfg.n_envs, t = h->tsz;
+    const size_t N = (size_t)h->cfg.n_envs;
     hipStream_t s = h->host_stream;
-    std::memcpy(h->pin.actions, io->actions, N * h->n_u_max * t);
-    HIP_TRY(h, hipMemcpyAsync(h->d_actions, h->pin.actions, N * h->n_u_max * t, hipMemcpyHostToDevice, s));
-    if (io->noise) {
-        std::memcpy(h->pin.noise, io->noise, N * t);
-        HIP_TRY(h, hipMemcpyAsync(h->d_noise, h->pin.noise, N * t, hipMemcpyHostToDevice, s));
+    // the caller's array of every slot (null: not asked for) and the device buffer that stands in for it
+    void* const user[ST_COUNT] = {const_cast<void*>(io->actions), const_cast<void*>(io->noise), io->obs, io->reward, io->done,
+                                  io->reward_terms, io->conditions, io->nav, io->ray_dist, io->terminal_obs, io->state_dot};
+    const auto dev = [&](int k) { return user[k] ? h->stage[k].dev : nullptr; };
+    for (int k = ST_ACTIONS; k <= ST_NOISE; ++k) {
+        const auto& st = h->stage[k];
+        if (!user[k]) continue;
+        std::memcpy(st.pin, user[k], st.bytes);
+        HIP_TRY(h, hipMemcpyAsync(st.dev, st.pin, st.bytes, hipMemcpyHostToDevice, s));
     }
     dockauv_step_io d{};
-    d.actions = h->d_actions;
-    d.noise = io->noise ? h->d_noise : nullptr;
-    d.obs = h->d_obs;
-    d.reward = h->d_reward;
-    d.done = h->d_done;
-    d.reward_terms = io->reward_terms ? h->d_terms : nullptr;
-    d.conditions = io->conditions ? h->d_cond : nullptr;
-    d.nav = io->nav ? h->d_nav : nullptr;
-    d.ray_dist = io->ray_dist ? h->d_raydist : nullptr;
-    d.terminal_obs = io->terminal_obs ? h->d_termobs : nullptr;
-    d.state_dot = io->state_dot ? h->d_statedot : nullptr;
+    d.actions = dev(ST_ACTIONS), d.noise = dev(ST_NOISE), d.obs = (float*)dev(ST_OBS), d.reward = dev(ST_REWARD);
+    d.done = (uint8_t*)dev(ST_DONE), d.reward_terms = dev(ST_TERMS), d.conditions = (uint8_t*)dev(ST_COND), d.nav = dev(ST_NAV);
+    d.ray_dist = dev(ST_RAYDIST), d.terminal_obs = (float*)dev(ST_TERMOBS), d.state_dot = dev(ST_STATEDOT);
     rc = launch(h, &d, s);
     if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->pin.obs, h->d_obs, N * h->n_obs * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(h->pin.reward, h->d_reward, N * t, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(h->pin.done, h->d_done, N, hipMemcpyDeviceToHost, s));
-    if (io->reward_terms) HIP_TRY(h, hipMemcpyAsync(h->pin.terms, h->d_terms, N * kNRew * t, hipMemcpyDeviceToHost, s));
-    if (io->conditions) HIP_TRY(h, hipMemcpyAsync(h->pin.cond, h->d_cond, N, hipMemcpyDeviceToHost, s));
-    if (io->nav) HIP_TRY(h, hipMemcpyAsync(h->pin.nav, h->d_nav, N * 4 * t, hipMemcpyDeviceToHost, s));
-    if (io->ray_dist) HIP_TRY(h, hipMemcpyAsync(h->pin.raydist, h->d_raydist, N * h->n_rays * t, hipMemcpyDeviceToHost, s));
-    if (io->state_dot) HIP_TRY(h, hipMemcpyAsync(h->pin.statedot, h->d_statedot, N * 12 * t, hipMemcpyDeviceToHost, s));
+    // (terminal observations: only the rows of finished envs, below)
+    for (int k = ST_OBS; k < ST_COUNT; ++k)
+        if (user[k] && k != ST_TERMOBS)
+            HIP_TRY(h, hipMemcpyAsync(h->stage[k].pin, h->stage[k].dev, h->stage[k].bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     if ((rc = check_status(h)) != 0) return rc;
     if (io->terminal_obs) {
         // terminal observations only exist for envs that finished in this step: fetch the rows of those envs only
         // (typically none or a few; the buffer is as large as the observations themselves)
-        const uint8_t* dn = h->pin.done;
+        const uint8_t* dn = static_cast<const uint8_t*>(h->stage[ST_DONE].pin);
+        float* const pin_term = static_cast<float*>(h->stage[ST_TERMOBS].pin);
+        const float* const dev_term = static_cast<const float*>(h->stage[ST_TERMOBS].dev);
         size_t first = N, last = 0, runs = 0;
         for (size_t i = 0; i < N; ++i)
             if (dn[i]) {
@@ -1011,27 +847,21 @@ int dockauv_step_host(dockauv_handle h, const dockauv_step_io* io) {
                     if (!dn[i]) { ++i; continue; }
                     size_t j = i;
                     while (j <= last && dn[j]) ++j;
-                    HIP_TRY(h, hipMemcpyAsync(h->pin.termobs + i * h->n_obs, h->d_termobs + i * h->n_obs,
+                    HIP_TRY(h, hipMemcpyAsync(pin_term + i * h->n_obs, dev_term + i * h->n_obs,
                                               (j - i) * h->n_obs * 4, hipMemcpyDeviceToHost, s));
                     i = j;
                 }
             } else {   // many scattered rows: one DMA over the span beats a launch per row
-                HIP_TRY(h, hipMemcpyAsync(h->pin.termobs + first * h->n_obs, h->d_termobs + first * h->n_obs,
+                HIP_TRY(h, hipMemcpyAsync(pin_term + first * h->n_obs, dev_term + first * h->n_obs,
                                           (last - first + 1) * h->n_obs * 4, hipMemcpyDeviceToHost, s));
             }
             HIP_TRY(h, hipStreamSynchronize(s));
             for (size_t i = first; i <= last; ++i)
-                if (dn[i]) std::memcpy(io->terminal_obs + i * h->n_obs, h->pin.termobs + i * h->n_obs, (size_t)h->n_obs * 4);
+                if (dn[i]) std::memcpy(io->terminal_obs + i * h->n_obs, pin_term + i * h->n_obs, (size_t)h->n_obs * 4);
         }
     }
-    std::memcpy(io->obs, h->pin.obs, N * h->n_obs * 4);
-    std::memcpy(io->reward, h->pin.reward, N * t);
-    std::memcpy(io->done, h->pin.done, N);
-    if (io->reward_terms) std::memcpy(io->reward_terms, h->pin.terms, N * kNRew * t);
-    if (io->conditions) std::memcpy(io->conditions, h->pin.cond, N);
-    if (io->nav) std::memcpy(io->nav, h->pin.nav, N * 4 * t);
-    if (io->ray_dist) std::memcpy(io->ray_dist, h->pin.raydist, N * h->n_rays * t);
-    if (io->state_dot) std::memcpy(io->state_dot, h->pin.statedot, N * 12 * t);
+    for (int k = ST_OBS; k < ST_COUNT; ++k)
+        if (user[k] && k != ST_TERMOBS) std::memcpy(user[k], h->stage[k].pin, h->stage[k].bytes);
     return 0;
 }
 
@@ -1050,7 +880,7 @@ void trace_free(dockauv_handle h) {
 int dockauv_trace_enable(dockauv_handle h, const int32_t* env_ids, int n_rows, int capacity) {
     if (!h) return DOCKAUV_E_INVALID;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->last_stream) HIP_TRY(h, hipStreamSynchronize(h->last_stream)); else HIP_TRY(h, hipDeviceSynchronize());
+    if (int rc = sync_last(h)) return rc;
     trace_free(h);
     if (n_rows == 0) return 0;
     if (!env_ids || n_rows < 0 || capacity < 1) return fail(h, DOCKAUV_E_INVALID, "bad trace arguments");
@@ -1104,7 +934,7 @@ int dockauv_trace_read(dockauv_handle h, long long first_step, int n_steps, doub
                     first_step + n_steps, h->trace_step, tr.capacity);
     if (n_steps == 0) return 0;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->last_stream) HIP_TRY(h, hipStreamSynchronize(h->last_stream)); else HIP_TRY(h, hipDeviceSynchronize());
+    if (int rc_ = sync_last(h)) return rc_;
     if (int rc_ = check_status(h)) return rc_;
     const size_t R = (size_t)tr.n_rows;
     std::vector<unsigned char> tmp;
@@ -1133,7 +963,7 @@ int dockauv_trace_read(dockauv_handle h, long long first_step, int n_steps, doub
 int dockauv_synchronize(dockauv_handle h) {
     if (!h) return DOCKAUV_E_INVALID;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->last_stream) HIP_TRY(h, hipStreamSynchronize(h->last_stream)); else HIP_TRY(h, hipDeviceSynchronize());
+    if (int rc = sync_last(h)) return rc;
     return check_status(h);
 }
 
@@ -1165,418 +995,6 @@ int dockauv_time_steps(dockauv_handle h, const dockauv_step_io* io, void* hip_st
     for (auto& e : ev) (void)hipEventDestroy(e);
     *avg_us = total_ms * 1000.0 / steps;
     return check_status(h);
-}
-
-// ------------------------------------------------------------------------------------------ policy + closed-loop rollout
-}  // extern "C"
-
-struct dockauv_policy_s {
-    dockauv_handle h = nullptr;
-    PolicyShape S{};
-    float* packed = nullptr;      // the weights as the kernel reads them (dockauv_device.h: PolicyShape)
-    float* raw = nullptr;         // device staging of host arrays: W1 b1 W2 b2 W3 b3 log_std back to back
-    float* log_std = nullptr;     // the raw log_std [DOCKAUV_MAX_U] (the packed image keeps exp(log_std)): read by the log-prob epilogue
-    bool has_log_std = false;
-    bool value_role = false;      // a critic (dockauv_value_create): n_out == 1, raw output
-    uint64_t seed = 0, env_id_offset = 0;
-    float* bwd_partial = nullptr; // dockauv_policy_backward's per-group partial sums, allocated by the first backward
-    double* head_ws = nullptr;    // dockauv_ppo_head's moment and row-sum partials (kHeadWorkspaceBytes), allocated by the first head call
-};
-
-namespace {
-
-// the descriptor's own fields; `like` != nullptr: a reload, shapes and activations must be those of the policy
-int validate_policy_desc(dockauv_handle h, const dockauv_policy_desc* d, const PolicyShape* like) {
-    if (d->struct_size != sizeof(dockauv_policy_desc))
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.struct_size: got %u, library has %zu", d->struct_size, sizeof(dockauv_policy_desc));
-    if (d->precision != DOCKAUV_F32) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.precision: %d, only DOCKAUV_F32 is implemented", d->precision);
-    if (d->n_in < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_in: %d must be >= 1", d->n_in);
-    if (d->n_hidden[0] < 1 || d->n_hidden[0] > DOCKAUV_POLICY_MAX_WIDTH)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_hidden[0]: %d outside 1..%d", d->n_hidden[0], DOCKAUV_POLICY_MAX_WIDTH);
-    if (d->n_hidden[1] < 0 || d->n_hidden[1] > DOCKAUV_POLICY_MAX_WIDTH)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_hidden[1]: %d outside 0..%d (0 = one hidden layer)", d->n_hidden[1], DOCKAUV_POLICY_MAX_WIDTH);
-    if (d->n_out < 1 || d->n_out > DOCKAUV_MAX_U) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_out: %d outside 1..%d", d->n_out, DOCKAUV_MAX_U);
-    if (d->hidden_act != DOCKAUV_ACT_TANH && d->hidden_act != DOCKAUV_ACT_RELU)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.hidden_act: %d is neither DOCKAUV_ACT_TANH nor DOCKAUV_ACT_RELU", d->hidden_act);
-    if (d->out_act != DOCKAUV_ACT_NONE && d->out_act != DOCKAUV_ACT_TANH)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.out_act: %d is neither DOCKAUV_ACT_NONE nor DOCKAUV_ACT_TANH", d->out_act);
-    if (d->pointers_on_device != 0 && d->pointers_on_device != 1)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.pointers_on_device: %d must be 0 or 1", d->pointers_on_device);
-    if (!d->W1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.W1 is NULL");
-    if (!d->b1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.b1 is NULL");
-    if (d->n_hidden[1] > 0 && !d->W2) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.W2 is NULL (n_hidden[1] > 0)");
-    if (d->n_hidden[1] > 0 && !d->b2) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.b2 is NULL (n_hidden[1] > 0)");
-    if (!d->W3) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.W3 is NULL");
-    if (!d->b3) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.b3 is NULL");
-    if (like && (d->n_in != like->n_in || d->n_hidden[0] != like->n_h1 || d->n_hidden[1] != like->n_h2 || d->n_out != like->n_out ||
-                 d->hidden_act != like->hidden_act || d->out_act != like->out_act))
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_load: n_in / n_hidden / n_out / activations differ from the policy's (%d-%d-%d-%d)",
-                    like->n_in, like->n_h1, like->n_h2, like->n_out);
-    return 0;
-}
-
-// weights of `d` -> p->packed, ordered on `stream`; host arrays go through p->raw and the call waits for the copies
-int upload_policy(dockauv_policy p, const dockauv_policy_desc* d, hipStream_t stream) {
-    dockauv_handle h = p->h;
-    const PolicyShape& S = p->S;
-    const int n_last = S.n_h2 ? S.n_h2 : S.n_h1;
-    const float* src[7] = {d->W1, d->b1, d->W2, d->b2, d->W3, d->b3, d->log_std};
-    const size_t cnt[7] = {(size_t)S.n_h1 * S.n_in, (size_t)S.n_h1, (size_t)S.n_h2 * S.n_h1, (size_t)S.n_h2,
-                           (size_t)S.n_out * n_last, (size_t)S.n_out, (size_t)S.n_out};
-    const float* dev[7];
-    if (d->pointers_on_device) {
-        for (int i = 0; i < 7; ++i) dev[i] = src[i];
-    } else {
-        size_t off = 0;
-        for (int i = 0; i < 7; ++i) {
-            dev[i] = (src[i] && cnt[i] && !(i == 6 && p->value_role)) ? p->raw + off : nullptr;
-            if (dev[i]) HIP_TRY(h, hipMemcpyAsync(p->raw + off, src[i], cnt[i] * sizeof(float), hipMemcpyHostToDevice, stream));
-            off += cnt[i];
-        }
-        HIP_TRY(h, hipStreamSynchronize(stream));   // the caller's host arrays are free on return
-    }
-    if (!S.n_h2) dev[2] = dev[3] = nullptr;
-    if (p->value_role) dev[6] = nullptr;   // (a critic has no exploration noise)
-    if (dev[6]) HIP_TRY(h, hipMemcpyAsync(p->log_std, dev[6], cnt[6] * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    const PolicyRaw raw{dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6]};
-    const int rc = launch_policy_pack(S, raw, p->packed, stream);
-    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "policy weight packing launch failed: %s", hipGetErrorString((hipError_t)rc));
-    p->has_log_std = dev[6] != nullptr;
-    p->seed = d->seed;
-    p->env_id_offset = d->env_id_offset;
-    return 0;
-}
-
-int policy_forward(dockauv_handle h, dockauv_policy p, const float* rows, float* actions, uint64_t t, int stochastic, hipStream_t stream,
-                   float* log_prob = nullptr) {
-    const int rc = launch_policy_forward(p->S, p->packed, rows, actions, h->cfg.n_envs, h->n_obs + 2, h->n_u_max, t,
-                                         (stochastic && p->has_log_std) ? 1 : 0, p->seed, p->env_id_offset, stream, log_prob,
-                                         log_prob ? p->log_std : nullptr);
-    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "policy kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    h->last_stream = stream;
-    return 0;
-}
-
-// V(rows[r]) for n_rows packed rows -> values[r]: the critic's kernel with one output unit and an action stride of 1
-int value_forward(dockauv_handle h, dockauv_policy c, const float* rows, long long n_rows, float* values, hipStream_t stream) {
-    const int rc = launch_policy_forward(c->S, c->packed, rows, values, (long)n_rows, h->n_obs + 2, 1, 0, 0, 0, 0, stream);
-    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "value kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    h->last_stream = stream;
-    return 0;
-}
-
-// what the actor argument of `fn` must be: of this handle, not a critic; with want_logp also a log_std and a raw output
-int check_actor(dockauv_handle h, dockauv_policy p, const char* fn, bool want_logp) {
-    if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "%s: the policy was created for another handle", fn);
-    if (p->value_role) return fail(h, DOCKAUV_E_INVALID, "%s: the policy is a critic (dockauv_value_create), an actor is needed", fn);
-    if (want_logp && !p->has_log_std) return fail(h, DOCKAUV_E_INVALID, "%s: log_prob needs a policy with a log_std", fn);
-    if (want_logp && p->S.out_act == DOCKAUV_ACT_TANH)
-        return fail(h, DOCKAUV_E_INVALID, "%s: log_prob of a policy with out_act DOCKAUV_ACT_TANH needs the squashing correction, "
-                    "which stays with the learner", fn);
-    return 0;
-}
-
-int check_critic(dockauv_handle h, dockauv_policy c, const char* fn) {
-    if (c->h != h) return fail(h, DOCKAUV_E_INVALID, "%s: the critic was created for another handle", fn);
-    if (!c->value_role) return fail(h, DOCKAUV_E_INVALID, "%s: the critic argument is an actor (dockauv_policy_create), not a critic", fn);
-    return 0;
-}
-
-int check_gae_factors(dockauv_handle h, const char* fn, float gamma, float gae_lambda) {
-    if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail(h, DOCKAUV_E_INVALID, "%s: gamma %g outside [0, 1]", fn, (double)gamma);
-    if (!(gae_lambda >= 0.0f && gae_lambda <= 1.0f)) return fail(h, DOCKAUV_E_INVALID, "%s: gae_lambda %g outside [0, 1]", fn, (double)gae_lambda);
-    return 0;
-}
-
-// the launches of dockauv_rollout; log_prob (nullable, [n_steps][n_envs]): the actor in its log-prob form
-int queue_rollout(dockauv_handle h, dockauv_policy p, const float* rows_in, float* rows_out, float* actions_out, float* terminal_obs,
-                  float* log_prob, int n_steps, uint64_t t0, int stochastic, hipStream_t stream) {
-    const size_t N = (size_t)h->cfg.n_envs, row = (size_t)h->n_obs + 2;
-    for (int k = 0; k < n_steps; ++k) {
-        const float* rows = k == 0 ? rows_in : rows_out + (size_t)(k - 1) * N * row;
-        float* act = actions_out + (size_t)k * N * h->n_u_max;
-        int rc = policy_forward(h, p, rows, act, t0 + (uint64_t)k, stochastic, stream, log_prob ? log_prob + (size_t)k * N : nullptr);
-        if (rc) return rc;
-        dockauv_step_io io{};
-        io.actions = act;
-        io.obs = rows_out + (size_t)k * N * row;
-        io.terminal_obs = terminal_obs ? terminal_obs + (size_t)k * N * h->n_obs : nullptr;
-        io.pack_reward_done = 1;
-        if ((rc = launch(h, &io, stream)) != 0) return rc;
-    }
-    return 0;
-}
-
-int gae(dockauv_handle h, const float* rows_out, const float* values, int n_steps, float gamma, float gae_lambda, float* advantages,
-        float* returns, hipStream_t stream) {
-    const int rc = launch_gae(rows_out, values, advantages, returns, n_steps, h->cfg.n_envs, h->n_obs, gamma, gae_lambda, stream);
-    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "GAE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    h->last_stream = stream;
-    return 0;
-}
-
-// actor (dockauv_policy_create) or critic (dockauv_value_create): `fn` names the entry point in the messages
-int create_policy(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out, bool value_role, const char* fn) {
-    if (!d || !out) return fail(h, DOCKAUV_E_INVALID, "%s: null argument", fn);
-    *out = nullptr;
-    int rc = validate_policy_desc(h, d, nullptr);
-    if (rc) return rc;
-    if (value_role && d->n_out != 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_out: %d, a critic has one output", d->n_out);
-    if (value_role && d->out_act != DOCKAUV_ACT_NONE)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.out_act: %d, a critic's output is raw (DOCKAUV_ACT_NONE)", d->out_act);
-    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
-    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "%s: the policy kernel is float32; the handle's precision is DOCKAUV_F64", fn);
-    if (d->n_in != h->n_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_in: %d, the handle's n_obs is %d", d->n_in, h->n_obs);
-    if (!value_role && d->n_out != h->n_u_max)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_out: %d, the handle's n_u is %d", d->n_out, h->n_u_max);
-    PolicyShape S{};
-    S.n_in = d->n_in;
-    S.n_h1 = d->n_hidden[0];
-    S.n_h2 = d->n_hidden[1];
-    S.n_out = d->n_out;
-    S.hidden_act = d->hidden_act;
-    S.out_act = d->out_act;
-    policy_layout(S);
-    if (policy_lds_bytes(S) > kPolMaxLds)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc: the padded weights (%zu B for n_in %d, n_hidden %d / %d) exceed "
-                    "the 160 KiB of LDS the policy kernel keeps them in: narrower layers", policy_lds_bytes(S), S.n_in, S.n_h1, S.n_h2);
-    HIP_TRY(h, hipSetDevice(h->device));
-    dockauv_policy p = new dockauv_policy_s();
-    p->h = h;
-    p->S = S;
-    p->value_role = value_role;
-    const int n_last = S.n_h2 ? S.n_h2 : S.n_h1;
-    const size_t raw_floats = (size_t)S.n_h1 * S.n_in + S.n_h1 + (size_t)S.n_h2 * S.n_h1 + S.n_h2 + (size_t)S.n_out * n_last + 2 * (size_t)S.n_out;
-    hipError_t e = hipMalloc((void**)&p->packed, (size_t)S.total * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&p->raw, raw_floats * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&p->log_std, DOCKAUV_MAX_U * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(p->log_std, 0, DOCKAUV_MAX_U * sizeof(float));
-    if (e != hipSuccess) {
-        dockauv_policy_destroy(p);
-        return fail(h, DOCKAUV_E_HIP, "policy buffers: %s", hipGetErrorString(e));
-    }
-    if ((rc = upload_policy(p, d, nullptr)) != 0) {
-        dockauv_policy_destroy(p);
-        return rc;
-    }
-    *out = p;
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int dockauv_policy_create(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out) {
-    return create_policy(h, d, out, false, "dockauv_policy_create");
-}
-
-int dockauv_value_create(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out) {
-    return create_policy(h, d, out, true, "dockauv_value_create");
-}
-
-int dockauv_policy_load(dockauv_policy p, const dockauv_policy_desc* d, void* hip_stream) {
-    if (!p) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_load: null policy");
-    if (!d) return fail(p->h, DOCKAUV_E_INVALID, "dockauv_policy_load: null descriptor");
-    int rc = validate_policy_desc(p->h, d, &p->S);
-    if (rc) return rc;
-    HIP_TRY(p->h, hipSetDevice(p->h->device));
-    return upload_policy(p, d, (hipStream_t)hip_stream);
-}
-
-int dockauv_policy_destroy(dockauv_policy p) {
-    if (!p) return 0;
-    if (p->h) (void)hipSetDevice(p->h->device);
-    (void)hipDeviceSynchronize();
-    if (p->packed) (void)hipFree(p->packed);
-    if (p->raw) (void)hipFree(p->raw);
-    if (p->log_std) (void)hipFree(p->log_std);
-    if (p->bwd_partial) (void)hipFree(p->bwd_partial);
-    if (p->head_ws) (void)hipFree(p->head_ws);
-    delete p;
-    return 0;
-}
-
-int dockauv_policy_forward(dockauv_handle h, dockauv_policy p, const float* rows, float* actions, uint64_t t, int stochastic,
-                           void* hip_stream) {
-    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_forward: null handle");
-    if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward: null policy");
-    if (int rc = check_actor(h, p, "dockauv_policy_forward", false)) return rc;
-    if (!rows || !actions) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward: rows/actions must not be NULL");
-    HIP_TRY(h, hipSetDevice(h->device));
-    return policy_forward(h, p, rows, actions, t, stochastic, (hipStream_t)hip_stream);
-}
-
-int dockauv_policy_forward_logp(dockauv_handle h, dockauv_policy p, const float* rows, float* actions, float* log_prob, uint64_t t,
-                                int stochastic, void* hip_stream) {
-    if (!rows || !actions || !log_prob) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_logp: rows/actions/log_prob must not be NULL");
-    if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_logp: null policy");
-    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_forward_logp: null handle");
-    if (int rc = check_actor(h, p, "dockauv_policy_forward_logp", true)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    return policy_forward(h, p, rows, actions, t, stochastic, (hipStream_t)hip_stream, log_prob);
-}
-
-int dockauv_value_forward(dockauv_handle h, dockauv_policy critic, const float* rows, long long n_rows, float* values, void* hip_stream) {
-    if (!rows || !values) return fail(h, DOCKAUV_E_INVALID, "dockauv_value_forward: rows/values must not be NULL");
-    if (n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_value_forward: n_rows %lld must be >= 1", n_rows);
-    if (!critic) return fail(h, DOCKAUV_E_INVALID, "dockauv_value_forward: null critic");
-    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_value_forward: null handle");
-    if (int rc = check_critic(h, critic, "dockauv_value_forward")) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    return value_forward(h, critic, rows, n_rows, values, (hipStream_t)hip_stream);
-}
-
-int dockauv_policy_forward_rows(dockauv_handle h, dockauv_policy p, const float* rows, const int64_t* row_index, long long n_rows,
-                                float* out, void* hip_stream) {
-    if (!rows || !out) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: rows/out must not be NULL");
-    if (n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: n_rows %lld must be >= 1", n_rows);
-    if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: null policy");
-    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: null handle");
-    if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: the policy was created for another handle");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int rc = launch_policy_forward_rows(p->S, p->packed, rows, (const long long*)row_index, (long)n_rows, h->n_obs + 2, out,
-                                              (hipStream_t)hip_stream);
-    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "policy rows kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    h->last_stream = (hipStream_t)hip_stream;
-    return 0;
-}
-
-int dockauv_policy_backward(dockauv_handle h, dockauv_policy p, const float* rows, const int64_t* row_index, long long n_rows,
-                            const float* grad_out, const dockauv_policy_grads* grads, void* hip_stream) {
-    if (!rows || !grad_out || !grads) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: rows/grad_out/grads must not be NULL");
-    if (grads->struct_size != sizeof(dockauv_policy_grads))
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_grads.struct_size: got %u, library has %zu", grads->struct_size, sizeof(dockauv_policy_grads));
-    if (!grads->dW1 || !grads->db1 || !grads->dW3 || !grads->db3)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_grads: dW1/db1/dW3/db3 must not be NULL");
-    if (n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: n_rows %lld must be >= 1", n_rows);
-    if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: null policy");
-    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_backward: null handle");
-    if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: the policy was created for another handle");
-    if (p->S.n_h2 > 0 && (!grads->dW2 || !grads->db2))
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_grads: dW2/db2 are NULL, the policy has two hidden layers");
-    BackwardLayout L;
-    backward_layout(p->S, L);
-    if (backward_lds_bytes(L) > kPolMaxLds)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: the kernel needs %zu B of LDS for n_in %d, n_hidden %d / %d (weights, one "
-                    "pass's rows, activations and deltas), more than the 160 KiB of a group: narrower layers or observations",
-                    backward_lds_bytes(L), p->S.n_in, p->S.n_h1, p->S.n_h2);
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (!p->bwd_partial) HIP_TRY(h, hipMalloc((void**)&p->bwd_partial, (size_t)kBwdMaxGroups * L.n_params * sizeof(float)));
-    const PolicyGrads g{grads->dW1, grads->db1, p->S.n_h2 ? grads->dW2 : nullptr, p->S.n_h2 ? grads->db2 : nullptr, grads->dW3, grads->db3};
-    const int rc = launch_policy_backward(p->S, p->packed, rows, (const long long*)row_index, (long)n_rows, h->n_obs + 2, grad_out,
-                                          p->bwd_partial, g, (hipStream_t)hip_stream);
-    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "policy backward launch failed: %s", hipGetErrorString((hipError_t)rc));
-    h->last_stream = (hipStream_t)hip_stream;
-    return 0;
-}
-
-int dockauv_ppo_head(dockauv_handle h, dockauv_policy actor, const dockauv_ppo_head_io* io, void* hip_stream) {
-    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_ppo_head: null handle");
-    if (!actor) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head: null actor");
-    if (!io) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head: io is NULL");
-    if (io->struct_size != sizeof(dockauv_ppo_head_io))
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_ppo_head_io));
-    if (int rc = check_actor(h, actor, "dockauv_ppo_head", true)) return rc;
-    if (io->n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.n_rows: %lld must be >= 1", io->n_rows);
-    if (io->normalize_advantage && io->n_rows < 2)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.n_rows: %lld must be >= 2 with normalize_advantage (the unbiased deviation)", io->n_rows);
-    if (!(io->clip_range > 0.0f)) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.clip_range: %g must be > 0", (double)io->clip_range);
-    if (!io->mean) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.mean is NULL");
-    if (!io->actions) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.actions is NULL");
-    if (!io->log_prob_old) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.log_prob_old is NULL");
-    if (!io->advantages) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.advantages is NULL");
-    if (!io->grad_mean) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.grad_mean is NULL");
-    if (!io->grad_log_std) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.grad_log_std is NULL");
-    if (!io->stats) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.stats is NULL");
-    if ((io->v == nullptr) != (io->grad_v == nullptr))
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.v / grad_v: both or neither must be NULL (NULL: no critic)");
-    if (io->v && !io->returns) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.returns is NULL (v is given)");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (!actor->head_ws) HIP_TRY(h, hipMalloc((void**)&actor->head_ws, kHeadWorkspaceBytes));
-    HeadArgs a{};
-    a.mean = io->mean;
-    a.v = io->v;
-    a.actions = io->actions;
-    a.log_prob_old = io->log_prob_old;
-    a.advantages = io->advantages;
-    a.returns = io->returns;
-    a.row_index = (const long long*)io->row_index;
-    a.log_std = actor->log_std;
-    a.grad_mean = io->grad_mean;
-    a.grad_v = io->grad_v;
-    a.grad_log_std = io->grad_log_std;
-    a.stats = io->stats;
-    a.moments = actor->head_ws;
-    a.partial = actor->head_ws + (size_t)kBwdMaxGroups * kHeadMoments;
-    a.n = (long)io->n_rows;
-    a.n_out = actor->S.n_out;
-    a.normalize = io->normalize_advantage ? 1 : 0;
-    a.clip = io->clip_range;
-    a.vf_coef = io->vf_coef;
-    a.ent_coef = io->ent_coef;
-    const int rc = launch_ppo_head(a, hip_stream);
-    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "PPO head launch failed: %s", hipGetErrorString((hipError_t)rc));
-    h->last_stream = (hipStream_t)hip_stream;
-    return 0;
-}
-
-int dockauv_gae(dockauv_handle h, const float* rows_out, const float* values, int n_steps, float gamma, float gae_lambda,
-                float* advantages, float* returns, void* hip_stream) {
-    if (!rows_out || !values || !advantages || !returns)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_gae: rows_out/values/advantages/returns must not be NULL");
-    if (n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_gae: n_steps %d must be >= 1", n_steps);
-    if (int rc = check_gae_factors(h, "dockauv_gae", gamma, gae_lambda)) return rc;
-    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_gae: null handle");
-    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "dockauv_gae: the packed rows are float32; the handle's precision is DOCKAUV_F64");
-    HIP_TRY(h, hipSetDevice(h->device));
-    return gae(h, rows_out, values, n_steps, gamma, gae_lambda, advantages, returns, (hipStream_t)hip_stream);
-}
-
-int dockauv_collect(dockauv_handle h, dockauv_policy actor, dockauv_policy critic, const dockauv_collect_io* io, void* hip_stream) {
-    if (!io) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect: io is NULL");
-    if (io->struct_size != sizeof(dockauv_collect_io))
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_collect_io));
-    if (io->n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.n_steps: %d must be >= 1", io->n_steps);
-    if (!io->rows_in || !io->rows_out || !io->actions_out)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: rows_in/rows_out/actions_out must not be NULL");
-    if (critic && (!io->values || !io->advantages || !io->returns))
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: values/advantages/returns must not be NULL with a critic");
-    if (!critic && (io->values || io->advantages || io->returns))
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: values/advantages/returns must be NULL without a critic");
-    if (critic)
-        if (int rc = check_gae_factors(h, "dockauv_collect_io", io->gamma, io->gae_lambda)) return rc;
-    if (!actor) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect: null actor");
-    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_collect: null handle");
-    if (int rc = check_actor(h, actor, "dockauv_collect", io->log_prob != nullptr)) return rc;
-    if (critic)
-        if (int rc = check_critic(h, critic, "dockauv_collect")) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const int K = io->n_steps;
-    int rc = queue_rollout(h, actor, io->rows_in, io->rows_out, io->actions_out, io->terminal_obs, io->log_prob, K, io->t0,
-                           io->stochastic, stream);
-    if (rc) return rc;
-    if (critic) {
-        const size_t N = (size_t)h->cfg.n_envs;
-        if ((rc = value_forward(h, critic, io->rows_in, (long long)N, io->values, stream)) != 0) return rc;
-        if ((rc = value_forward(h, critic, io->rows_out, (long long)K * (long long)N, io->values + N, stream)) != 0) return rc;
-        if ((rc = gae(h, io->rows_out, io->values, K, io->gamma, io->gae_lambda, io->advantages, io->returns, stream)) != 0) return rc;
-    }
-    return check_status(h);   // (what dockauv_poll_status looks at: no synchronisation)
-}
-
-int dockauv_rollout(dockauv_handle h, dockauv_policy p, const float* rows_in, float* rows_out, float* actions_out,
-                    float* terminal_obs, int n_steps, uint64_t t0, int stochastic, void* hip_stream) {
-    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_rollout: null handle");
-    if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: null policy");
-    if (int rc = check_actor(h, p, "dockauv_rollout", false)) return rc;
-    if (n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: n_steps %d must be >= 1", n_steps);
-    if (!rows_in || !rows_out || !actions_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: rows_in/rows_out/actions_out must not be NULL");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = queue_rollout(h, p, rows_in, rows_out, actions_out, terminal_obs, nullptr, n_steps, t0, stochastic, (hipStream_t)hip_stream))
-        return rc;
-    return check_status(h);   // (what dockauv_poll_status looks at: no synchronisation)
 }
 
 #ifdef DOCKAUV_STAMPS

@@ -1,0 +1,418 @@
+// dockauv_capi_policy.hip -- C ABI of libdockauv.so (include/dockauv.h), second part: MLP policy and critic, closed-loop
+// rollout, PPO collector, backward and head.  The kernels are in dockauv_policy / _collect / _backward / _head.hip.
+#include <cstring>
+
+#include "dockauv_capi.h"
+
+using namespace dockauv;
+
+struct dockauv_policy_s {
+    dockauv_handle h = nullptr;
+    PolicyShape S{};
+    float* packed = nullptr;      // the weights as the kernel reads them (dockauv_device.h: PolicyShape)
+    float* raw = nullptr;         // device staging of host arrays: W1 b1 W2 b2 W3 b3 log_std back to back
+    float* log_std = nullptr;     // the raw log_std [DOCKAUV_MAX_U] (the packed image keeps exp(log_std)): read by the log-prob epilogue
+    bool has_log_std = false;
+    bool value_role = false;      // a critic (dockauv_value_create): n_out == 1, raw output
+    uint64_t seed = 0, env_id_offset = 0;
+    float* bwd_partial = nullptr; // dockauv_policy_backward's per-group partial sums, allocated by the first backward
+    double* head_ws = nullptr;    // dockauv_ppo_head's moment and row-sum partials (kHeadWorkspaceBytes), allocated by the first head call
+};
+
+namespace {
+
+// the descriptor's own fields; `like` != nullptr: a reload, shapes and activations must be those of the policy
+int validate_policy_desc(dockauv_handle h, const dockauv_policy_desc* d, const PolicyShape* like) {
+    if (d->struct_size != sizeof(dockauv_policy_desc))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.struct_size: got %u, library has %zu", d->struct_size, sizeof(dockauv_policy_desc));
+    if (d->precision != DOCKAUV_F32) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.precision: %d, only DOCKAUV_F32 is implemented", d->precision);
+    if (d->n_in < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_in: %d must be >= 1", d->n_in);
+    if (d->n_hidden[0] < 1 || d->n_hidden[0] > DOCKAUV_POLICY_MAX_WIDTH)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_hidden[0]: %d outside 1..%d", d->n_hidden[0], DOCKAUV_POLICY_MAX_WIDTH);
+    if (d->n_hidden[1] < 0 || d->n_hidden[1] > DOCKAUV_POLICY_MAX_WIDTH)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_hidden[1]: %d outside 0..%d (0 = one hidden layer)", d->n_hidden[1], DOCKAUV_POLICY_MAX_WIDTH);
+    if (d->n_out < 1 || d->n_out > DOCKAUV_MAX_U) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_out: %d outside 1..%d", d->n_out, DOCKAUV_MAX_U);
+    if (d->hidden_act != DOCKAUV_ACT_TANH && d->hidden_act != DOCKAUV_ACT_RELU)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.hidden_act: %d is neither DOCKAUV_ACT_TANH nor DOCKAUV_ACT_RELU", d->hidden_act);
+    if (d->out_act != DOCKAUV_ACT_NONE && d->out_act != DOCKAUV_ACT_TANH)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.out_act: %d is neither DOCKAUV_ACT_NONE nor DOCKAUV_ACT_TANH", d->out_act);
+    if (d->pointers_on_device != 0 && d->pointers_on_device != 1)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.pointers_on_device: %d must be 0 or 1", d->pointers_on_device);
+    if (!d->W1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.W1 is NULL");
+    if (!d->b1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.b1 is NULL");
+    if (d->n_hidden[1] > 0 && !d->W2) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.W2 is NULL (n_hidden[1] > 0)");
+    if (d->n_hidden[1] > 0 && !d->b2) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.b2 is NULL (n_hidden[1] > 0)");
+    if (!d->W3) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.W3 is NULL");
+    if (!d->b3) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.b3 is NULL");
+    if (like && (d->n_in != like->n_in || d->n_hidden[0] != like->n_h1 || d->n_hidden[1] != like->n_h2 || d->n_out != like->n_out ||
+                 d->hidden_act != like->hidden_act || d->out_act != like->out_act))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_load: n_in / n_hidden / n_out / activations differ from the policy's (%d-%d-%d-%d)",
+                    like->n_in, like->n_h1, like->n_h2, like->n_out);
+    return 0;
+}
+
+// weights of `d` -> p->packed, ordered on `stream`; host arrays go through p->raw and the call waits for the copies
+int upload_policy(dockauv_policy p, const dockauv_policy_desc* d, hipStream_t stream) {
+    dockauv_handle h = p->h;
+    const PolicyShape& S = p->S;
+    const int n_last = S.n_h2 ? S.n_h2 : S.n_h1;
+    const float* src[7] = {d->W1, d->b1, d->W2, d->b2, d->W3, d->b3, d->log_std};
+    const size_t cnt[7] = {(size_t)S.n_h1 * S.n_in, (size_t)S.n_h1, (size_t)S.n_h2 * S.n_h1, (size_t)S.n_h2,
+                           (size_t)S.n_out * n_last, (size_t)S.n_out, (size_t)S.n_out};
+    const float* dev[7];
+    if (d->pointers_on_device) {
+        for (int i = 0; i < 7; ++i) dev[i] = src[i];
+    } else {
+        size_t off = 0;
+        for (int i = 0; i < 7; ++i) {
+            dev[i] = (src[i] && cnt[i] && !(i == 6 && p->value_role)) ? p->raw + off : nullptr;
+            if (dev[i]) HIP_TRY(h, hipMemcpyAsync(p->raw + off, src[i], cnt[i] * sizeof(float), hipMemcpyHostToDevice, stream));
+            off += cnt[i];
+        }
+        HIP_TRY(h, hipStreamSynchronize(stream));   // the caller's host arrays are free on return
+    }
+    if (!S.n_h2) dev[2] = dev[3] = nullptr;
+    if (p->value_role) dev[6] = nullptr;   // (a critic has no exploration noise)
+    if (dev[6]) HIP_TRY(h, hipMemcpyAsync(p->log_std, dev[6], cnt[6] * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    const PolicyRaw raw{dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6]};
+    const int rc = launch_policy_pack(S, raw, p->packed, stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "policy weight packing launch failed: %s", hipGetErrorString((hipError_t)rc));
+    p->has_log_std = dev[6] != nullptr;
+    p->seed = d->seed;
+    p->env_id_offset = d->env_id_offset;
+    return 0;
+}
+
+int policy_forward(dockauv_handle h, dockauv_policy p, const float* rows, float* actions, uint64_t t, int stochastic, hipStream_t stream,
+                   float* log_prob = nullptr) {
+    const int rc = launch_policy_forward(p->S, p->packed, rows, actions, h->cfg.n_envs, h->n_obs + 2, h->n_u_max, t,
+                                         (stochastic && p->has_log_std) ? 1 : 0, p->seed, p->env_id_offset, stream, log_prob,
+                                         log_prob ? p->log_std : nullptr);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "policy kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = stream;
+    return 0;
+}
+
+// V(rows[r]) for n_rows packed rows -> values[r]: the critic's kernel with one output unit and an action stride of 1
+int value_forward(dockauv_handle h, dockauv_policy c, const float* rows, long long n_rows, float* values, hipStream_t stream) {
+    const int rc = launch_policy_forward(c->S, c->packed, rows, values, (long)n_rows, h->n_obs + 2, 1, 0, 0, 0, 0, stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "value kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = stream;
+    return 0;
+}
+
+// what the actor argument of `fn` must be: of this handle, not a critic; with want_logp also a log_std and a raw output
+int check_actor(dockauv_handle h, dockauv_policy p, const char* fn, bool want_logp) {
+    if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "%s: the policy was created for another handle", fn);
+    if (p->value_role) return fail(h, DOCKAUV_E_INVALID, "%s: the policy is a critic (dockauv_value_create), an actor is needed", fn);
+    if (want_logp && !p->has_log_std) return fail(h, DOCKAUV_E_INVALID, "%s: log_prob needs a policy with a log_std", fn);
+    if (want_logp && p->S.out_act == DOCKAUV_ACT_TANH)
+        return fail(h, DOCKAUV_E_INVALID, "%s: log_prob of a policy with out_act DOCKAUV_ACT_TANH needs the squashing correction, "
+                    "which stays with the learner", fn);
+    return 0;
+}
+
+int check_critic(dockauv_handle h, dockauv_policy c, const char* fn) {
+    if (c->h != h) return fail(h, DOCKAUV_E_INVALID, "%s: the critic was created for another handle", fn);
+    if (!c->value_role) return fail(h, DOCKAUV_E_INVALID, "%s: the critic argument is an actor (dockauv_policy_create), not a critic", fn);
+    return 0;
+}
+
+int check_gae_factors(dockauv_handle h, const char* fn, float gamma, float gae_lambda) {
+    if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail(h, DOCKAUV_E_INVALID, "%s: gamma %g outside [0, 1]", fn, (double)gamma);
+    if (!(gae_lambda >= 0.0f && gae_lambda <= 1.0f)) return fail(h, DOCKAUV_E_INVALID, "%s: gae_lambda %g outside [0, 1]", fn, (double)gae_lambda);
+    return 0;
+}
+
+// the launches of dockauv_rollout; log_prob (nullable, [n_steps][n_envs]): the actor in its log-prob form
+int queue_rollout(dockauv_handle h, dockauv_policy p, const float* rows_in, float* rows_out, float* actions_out, float* terminal_obs,
+                  float* log_prob, int n_steps, uint64_t t0, int stochastic, hipStream_t stream) {
+    const size_t N = (size_t)h->cfg.n_envs, row = (size_t)h->n_obs + 2;
+    for (int k = 0; k < n_steps; ++k) {
+        const float* rows = k == 0 ? rows_in : rows_out + (size_t)(k - 1) * N * row;
+        float* act = actions_out + (size_t)k * N * h->n_u_max;
+        int rc = policy_forward(h, p, rows, act, t0 + (uint64_t)k, stochastic, stream, log_prob ? log_prob + (size_t)k * N : nullptr);
+        if (rc) return rc;
+        dockauv_step_io io{};
+        io.actions = act;
+        io.obs = rows_out + (size_t)k * N * row;
+        io.terminal_obs = terminal_obs ? terminal_obs + (size_t)k * N * h->n_obs : nullptr;
+        io.pack_reward_done = 1;
+        if ((rc = launch(h, &io, stream)) != 0) return rc;
+    }
+    return 0;
+}
+
+int gae(dockauv_handle h, const float* rows_out, const float* values, int n_steps, float gamma, float gae_lambda, float* advantages,
+        float* returns, hipStream_t stream) {
+    const int rc = launch_gae(rows_out, values, advantages, returns, n_steps, h->cfg.n_envs, h->n_obs, gamma, gae_lambda, stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "GAE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = stream;
+    return 0;
+}
+
+// actor (dockauv_policy_create) or critic (dockauv_value_create): `fn` names the entry point in the messages
+int create_policy(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out, bool value_role, const char* fn) {
+    if (!d || !out) return fail(h, DOCKAUV_E_INVALID, "%s: null argument", fn);
+    *out = nullptr;
+    int rc = validate_policy_desc(h, d, nullptr);
+    if (rc) return rc;
+    if (value_role && d->n_out != 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_out: %d, a critic has one output", d->n_out);
+    if (value_role && d->out_act != DOCKAUV_ACT_NONE)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.out_act: %d, a critic's output is raw (DOCKAUV_ACT_NONE)", d->out_act);
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
+    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "%s: the policy kernel is float32; the handle's precision is DOCKAUV_F64", fn);
+    if (d->n_in != h->n_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_in: %d, the handle's n_obs is %d", d->n_in, h->n_obs);
+    if (!value_role && d->n_out != h->n_u_max)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_out: %d, the handle's n_u is %d", d->n_out, h->n_u_max);
+    PolicyShape S{};
+    S.n_in = d->n_in;
+    S.n_h1 = d->n_hidden[0];
+    S.n_h2 = d->n_hidden[1];
+    S.n_out = d->n_out;
+    S.hidden_act = d->hidden_act;
+    S.out_act = d->out_act;
+    policy_layout(S);
+    if (policy_lds_bytes(S) > kPolMaxLds)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc: the padded weights (%zu B for n_in %d, n_hidden %d / %d) exceed "
+                    "the 160 KiB of LDS the policy kernel keeps them in: narrower layers", policy_lds_bytes(S), S.n_in, S.n_h1, S.n_h2);
+    HIP_TRY(h, hipSetDevice(h->device));
+    dockauv_policy p = new dockauv_policy_s();
+    p->h = h;
+    p->S = S;
+    p->value_role = value_role;
+    const int n_last = S.n_h2 ? S.n_h2 : S.n_h1;
+    const size_t raw_floats = (size_t)S.n_h1 * S.n_in + S.n_h1 + (size_t)S.n_h2 * S.n_h1 + S.n_h2 + (size_t)S.n_out * n_last + 2 * (size_t)S.n_out;
+    hipError_t e = hipMalloc((void**)&p->packed, (size_t)S.total * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->raw, raw_floats * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->log_std, DOCKAUV_MAX_U * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(p->log_std, 0, DOCKAUV_MAX_U * sizeof(float));
+    if (e != hipSuccess) {
+        dockauv_policy_destroy(p);
+        return fail(h, DOCKAUV_E_HIP, "policy buffers: %s", hipGetErrorString(e));
+    }
+    if ((rc = upload_policy(p, d, nullptr)) != 0) {
+        dockauv_policy_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dockauv_policy_create(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out) {
+    return create_policy(h, d, out, false, "dockauv_policy_create");
+}
+
+int dockauv_value_create(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out) {
+    return create_policy(h, d, out, true, "dockauv_value_create");
+}
+
+int dockauv_policy_load(dockauv_policy p, const dockauv_policy_desc* d, void* hip_stream) {
+    if (!p) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_load: null policy");
+    if (!d) return fail(p->h, DOCKAUV_E_INVALID, "dockauv_policy_load: null descriptor");
+    int rc = validate_policy_desc(p->h, d, &p->S);
+    if (rc) return rc;
+    HIP_TRY(p->h, hipSetDevice(p->h->device));
+    return upload_policy(p, d, (hipStream_t)hip_stream);
+}
+
+int dockauv_policy_destroy(dockauv_policy p) {
+    if (!p) return 0;
+    if (p->h) (void)hipSetDevice(p->h->device);
+    (void)hipDeviceSynchronize();
+    if (p->packed) (void)hipFree(p->packed);
+    if (p->raw) (void)hipFree(p->raw);
+    if (p->log_std) (void)hipFree(p->log_std);
+    if (p->bwd_partial) (void)hipFree(p->bwd_partial);
+    if (p->head_ws) (void)hipFree(p->head_ws);
+    delete p;
+    return 0;
+}
+
+int dockauv_policy_forward(dockauv_handle h, dockauv_policy p, const float* rows, float* actions, uint64_t t, int stochastic,
+                           void* hip_stream) {
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_forward: null handle");
+    if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward: null policy");
+    if (int rc = check_actor(h, p, "dockauv_policy_forward", false)) return rc;
+    if (!rows || !actions) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward: rows/actions must not be NULL");
+    HIP_TRY(h, hipSetDevice(h->device));
+    return policy_forward(h, p, rows, actions, t, stochastic, (hipStream_t)hip_stream);
+}
+
+int dockauv_policy_forward_logp(dockauv_handle h, dockauv_policy p, const float* rows, float* actions, float* log_prob, uint64_t t,
+                                int stochastic, void* hip_stream) {
+    if (!rows || !actions || !log_prob) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_logp: rows/actions/log_prob must not be NULL");
+    if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_logp: null policy");
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_forward_logp: null handle");
+    if (int rc = check_actor(h, p, "dockauv_policy_forward_logp", true)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return policy_forward(h, p, rows, actions, t, stochastic, (hipStream_t)hip_stream, log_prob);
+}
+
+int dockauv_value_forward(dockauv_handle h, dockauv_policy critic, const float* rows, long long n_rows, float* values, void* hip_stream) {
+    if (!rows || !values) return fail(h, DOCKAUV_E_INVALID, "dockauv_value_forward: rows/values must not be NULL");
+    if (n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_value_forward: n_rows %lld must be >= 1", n_rows);
+    if (!critic) return fail(h, DOCKAUV_E_INVALID, "dockauv_value_forward: null critic");
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_value_forward: null handle");
+    if (int rc = check_critic(h, critic, "dockauv_value_forward")) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return value_forward(h, critic, rows, n_rows, values, (hipStream_t)hip_stream);
+}
+
+int dockauv_policy_forward_rows(dockauv_handle h, dockauv_policy p, const float* rows, const int64_t* row_index, long long n_rows,
+                                float* out, void* hip_stream) {
+    if (!rows || !out) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: rows/out must not be NULL");
+    if (n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: n_rows %lld must be >= 1", n_rows);
+    if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: null policy");
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: null handle");
+    if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: the policy was created for another handle");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = launch_policy_forward_rows(p->S, p->packed, rows, (const long long*)row_index, (long)n_rows, h->n_obs + 2, out,
+                                              (hipStream_t)hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "policy rows kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
+    return 0;
+}
+
+int dockauv_policy_backward(dockauv_handle h, dockauv_policy p, const float* rows, const int64_t* row_index, long long n_rows,
+                            const float* grad_out, const dockauv_policy_grads* grads, void* hip_stream) {
+    if (!rows || !grad_out || !grads) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: rows/grad_out/grads must not be NULL");
+    if (grads->struct_size != sizeof(dockauv_policy_grads))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_grads.struct_size: got %u, library has %zu", grads->struct_size, sizeof(dockauv_policy_grads));
+    if (!grads->dW1 || !grads->db1 || !grads->dW3 || !grads->db3)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_grads: dW1/db1/dW3/db3 must not be NULL");
+    if (n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: n_rows %lld must be >= 1", n_rows);
+    if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: null policy");
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_backward: null handle");
+    if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: the policy was created for another handle");
+    if (p->S.n_h2 > 0 && (!grads->dW2 || !grads->db2))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_grads: dW2/db2 are NULL, the policy has two hidden layers");
+    BackwardLayout L;
+    backward_layout(p->S, L);
+    if (backward_lds_bytes(L) > kPolMaxLds)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: the kernel needs %zu B of LDS for n_in %d, n_hidden %d / %d (weights, one "
+                    "pass's rows, activations and deltas), more than the 160 KiB of a group: narrower layers or observations",
+                    backward_lds_bytes(L), p->S.n_in, p->S.n_h1, p->S.n_h2);
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!p->bwd_partial) HIP_TRY(h, hipMalloc((void**)&p->bwd_partial, (size_t)kBwdMaxGroups * L.n_params * sizeof(float)));
+    const PolicyGrads g{grads->dW1, grads->db1, p->S.n_h2 ? grads->dW2 : nullptr, p->S.n_h2 ? grads->db2 : nullptr, grads->dW3, grads->db3};
+    const int rc = launch_policy_backward(p->S, p->packed, rows, (const long long*)row_index, (long)n_rows, h->n_obs + 2, grad_out,
+                                          p->bwd_partial, g, (hipStream_t)hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "policy backward launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
+    return 0;
+}
+
+int dockauv_ppo_head(dockauv_handle h, dockauv_policy actor, const dockauv_ppo_head_io* io, void* hip_stream) {
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_ppo_head: null handle");
+    if (!actor) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head: null actor");
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head: io is NULL");
+    if (io->struct_size != sizeof(dockauv_ppo_head_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_ppo_head_io));
+    if (int rc = check_actor(h, actor, "dockauv_ppo_head", true)) return rc;
+    if (io->n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.n_rows: %lld must be >= 1", io->n_rows);
+    if (io->normalize_advantage && io->n_rows < 2)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.n_rows: %lld must be >= 2 with normalize_advantage (the unbiased deviation)", io->n_rows);
+    if (!(io->clip_range > 0.0f)) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.clip_range: %g must be > 0", (double)io->clip_range);
+    if (!io->mean) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.mean is NULL");
+    if (!io->actions) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.actions is NULL");
+    if (!io->log_prob_old) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.log_prob_old is NULL");
+    if (!io->advantages) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.advantages is NULL");
+    if (!io->grad_mean) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.grad_mean is NULL");
+    if (!io->grad_log_std) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.grad_log_std is NULL");
+    if (!io->stats) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.stats is NULL");
+    if ((io->v == nullptr) != (io->grad_v == nullptr))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.v / grad_v: both or neither must be NULL (NULL: no critic)");
+    if (io->v && !io->returns) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_head_io.returns is NULL (v is given)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!actor->head_ws) HIP_TRY(h, hipMalloc((void**)&actor->head_ws, kHeadWorkspaceBytes));
+    HeadArgs a{};
+    a.mean = io->mean;
+    a.v = io->v;
+    a.actions = io->actions;
+    a.log_prob_old = io->log_prob_old;
+    a.advantages = io->advantages;
+    a.returns = io->returns;
+    a.row_index = (const long long*)io->row_index;
+    a.log_std = actor->log_std;
+    a.grad_mean = io->grad_mean;
+    a.grad_v = io->grad_v;
+    a.grad_log_std = io->grad_log_std;
+    a.stats = io->stats;
+    a.moments = actor->head_ws;
+    a.partial = actor->head_ws + (size_t)kBwdMaxGroups * kHeadMoments;
+    a.n = (long)io->n_rows;
+    a.n_out = actor->S.n_out;
+    a.normalize = io->normalize_advantage ? 1 : 0;
+    a.clip = io->clip_range;
+    a.vf_coef = io->vf_coef;
+    a.ent_coef = io->ent_coef;
+    const int rc = launch_ppo_head(a, hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "PPO head launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
+    return 0;
+}
+
+int dockauv_gae(dockauv_handle h, const float* rows_out, const float* values, int n_steps, float gamma, float gae_lambda,
+                float* advantages, float* returns, void* hip_stream) {
+    if (!rows_out || !values || !advantages || !returns)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_gae: rows_out/values/advantages/returns must not be NULL");
+    if (n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_gae: n_steps %d must be >= 1", n_steps);
+    if (int rc = check_gae_factors(h, "dockauv_gae", gamma, gae_lambda)) return rc;
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_gae: null handle");
+    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "dockauv_gae: the packed rows are float32; the handle's precision is DOCKAUV_F64");
+    HIP_TRY(h, hipSetDevice(h->device));
+    return gae(h, rows_out, values, n_steps, gamma, gae_lambda, advantages, returns, (hipStream_t)hip_stream);
+}
+
+int dockauv_collect(dockauv_handle h, dockauv_policy actor, dockauv_policy critic, const dockauv_collect_io* io, void* hip_stream) {
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect: io is NULL");
+    if (io->struct_size != sizeof(dockauv_collect_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_collect_io));
+    if (io->n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.n_steps: %d must be >= 1", io->n_steps);
+    if (!io->rows_in || !io->rows_out || !io->actions_out)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: rows_in/rows_out/actions_out must not be NULL");
+    if (critic && (!io->values || !io->advantages || !io->returns))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: values/advantages/returns must not be NULL with a critic");
+    if (!critic && (io->values || io->advantages || io->returns))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: values/advantages/returns must be NULL without a critic");
+    if (critic)
+        if (int rc = check_gae_factors(h, "dockauv_collect_io", io->gamma, io->gae_lambda)) return rc;
+    if (!actor) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect: null actor");
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_collect: null handle");
+    if (int rc = check_actor(h, actor, "dockauv_collect", io->log_prob != nullptr)) return rc;
+    if (critic)
+        if (int rc = check_critic(h, critic, "dockauv_collect")) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int K = io->n_steps;
+    int rc = queue_rollout(h, actor, io->rows_in, io->rows_out, io->actions_out, io->terminal_obs, io->log_prob, K, io->t0,
+                           io->stochastic, stream);
+    if (rc) return rc;
+    if (critic) {
+        const size_t N = (size_t)h->cfg.n_envs;
+        if ((rc = value_forward(h, critic, io->rows_in, (long long)N, io->values, stream)) != 0) return rc;
+        if ((rc = value_forward(h, critic, io->rows_out, (long long)K * (long long)N, io->values + N, stream)) != 0) return rc;
+        if ((rc = gae(h, io->rows_out, io->values, K, io->gamma, io->gae_lambda, io->advantages, io->returns, stream)) != 0) return rc;
+    }
+    return check_status(h);   // (what dockauv_poll_status looks at: no synchronisation)
+}
+
+int dockauv_rollout(dockauv_handle h, dockauv_policy p, const float* rows_in, float* rows_out, float* actions_out,
+                    float* terminal_obs, int n_steps, uint64_t t0, int stochastic, void* hip_stream) {
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_rollout: null handle");
+    if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: null policy");
+    if (int rc = check_actor(h, p, "dockauv_rollout", false)) return rc;
+    if (n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: n_steps %d must be >= 1", n_steps);
+    if (!rows_in || !rows_out || !actions_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: rows_in/rows_out/actions_out must not be NULL");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = queue_rollout(h, p, rows_in, rows_out, actions_out, terminal_obs, nullptr, n_steps, t0, stochastic, (hipStream_t)hip_stream))
+        return rc;
+    return check_status(h);   // (what dockauv_poll_status looks at: no synchronisation)
+}
+
+}  // extern "C"

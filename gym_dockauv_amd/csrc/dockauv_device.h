@@ -223,18 +223,135 @@ inline size_t lds_bytes(int epg, int nt, int max_cap, int max_sph, int n_obs, bo
     return bytes + (size_t)epg * (n_obs + 2) * sizeof(float);   // +2: packed reward | done columns
 }
 
-// launch one step; implemented in dockauv_kernels_f32.hip / _f64.hip.  vk = VehKind, sym = structural fast path
-// (see kinetics_), has_rays = obstacles present.  ev0 / ev1: optional hipEvent_t recorded at the start / end of this
-// very dispatch (hipExtLaunchKernelGGL).  Returns a hipError_t as int.
-int launch_step_f32(const KernelArgs<float, 2>& a, int vk, bool sym, bool has_rays, int threads, void* stream,
-                    void* ev0 = nullptr, void* ev1 = nullptr);
-int launch_step_f64(const KernelArgs<double, 2>& a, int vk, bool sym, bool has_rays, int threads, void* stream,
-                    void* ev0 = nullptr, void* ev1 = nullptr);
+// ------------------------------------------------------------------------------------------ kernel selection (host)
+// Which of the compiled step_kernel / step_ride_kernel / step_seq_kernel instantiations serves a call, and the group shape
+// dockauv_create picks: plain host logic on a handful of integers, written down HERE and nowhere else.  dockauv_capi.hip
+// builds the request (step_request), the launchers of dockauv_step.hip.inc dispatch on the variant;
+// tests/test_kernel_selection_host.py pins the table on a CPU.
+constexpr int ceil_log2(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
 
-// n <= kSeqMax steps of the handle in ONE launch (every group walks its 64 envs through all of them): float32 product
-// kernels of the structural fast path only (dockauv_kernels_seq.hip); hipErrorNotSupported = the caller launches the steps
-// one by one.  a.io: everything but actions / obs, which come from `seq`.
-int launch_sequence_f32(const KernelArgs<float, 2>& a, int vk, bool sym, bool has_rays, int threads, const SeqArgs& seq, void* stream);
+// what a launch is asked for: the handle's constants and what the step's dockauv_step_io wants
+struct StepRequest {
+    bool f64, sym;        // precision; structural fast path (see kinetics_)
+    int vk;               // VehKind
+    bool has_rays;        // obstacles present
+    int threads, n_envs, ray_pad_log2, reset_mode, reward_set;
+    bool extras;          // any optional input / output other than terminal_obs, the episode-storage trace or device noise
+    bool terminal_obs;
+    int pack;             // StepIO::pack
+    bool ride;            // copy groups ride in this launch (RideLaunch::plan)
+};
+
+// the template arguments of the kernel that serves it (RAYS = has_rays, EPG = 64)
+struct StepVariant {
+    int NT;
+    bool LOG, TERM, WB;
+    bool ride;            // step_ride_kernel<..., NT> instead of step_kernel<..., NT, LOG, TERM, WB>
+    bool unsupported;     // no such kernel: hipErrorNotSupported (select_sequence: the caller launches the steps one by one)
+};
+
+// The product instantiations cover what a throughput rollout runs: mandatory outputs only, reward set 1, reset modes
+// NONE (the caller resets) and DEVICE (in-kernel episode generation), fans of 9..16 or 33..64 rays.  Everything else --
+// optional inputs / outputs, logging, reset mode POOL (host-staged next episodes), reward set 2, other fan widths -- is
+// served by the full instantiation (LOG, one group shape each): with those paths behind run-time branches of one kernel,
+// every BASELINE config ran 5-12 % slower.
+inline bool needs_full_kernel(const StepRequest& r) {
+    const bool odd_fan = r.has_rays && !(r.ray_pad_log2 == 6 || r.ray_pad_log2 == 4);
+    return r.extras || r.reset_mode == 1 || r.reward_set == 2 || odd_fan;
+}
+
+// the group shapes that exist: sensor-free kernels of 256 / 128 / 64 threads, ray kernels of 512 / 256 / 64
+inline int group_threads(bool has_rays, int threads) {
+    if (has_rays) return threads >= 512 ? 512 : (threads >= 256 ? 256 : 64);
+    return threads >= 256 ? 256 : (threads >= 128 ? 128 : 64);
+}
+
+// a launch of more than one round of resident groups (config 3: 262 144 envs 34.5 us write-through / 35.6 write-back;
+// 1 048 576: 191 / 165)
+inline bool many_rounds(int n_envs) { return n_envs > 262144; }
+
+inline StepVariant select_step(const StepRequest& r) {
+    const bool fast = !r.f64 && r.sym;   // the float32 kernels of the structural fast path
+    // product kernels that also deliver terminal observations (TERM): float32, structural fast path, packed rows, the two
+    // default group shapes -- what a device-resident learner runs (TorchDocking3d.step(want_terminal_obs=True))
+    const bool term_ok = fast && r.vk != VK_DENSEB;
+    const bool term_product = term_ok && r.terminal_obs && r.pack && !r.ride;
+    StepVariant v{256, false, false, false, false, false};
+    if (needs_full_kernel(r) || (r.terminal_obs && !term_product)) {
+        v.LOG = true;
+        v.unsupported = r.ride;   // (the riding gather is a throughput feature)
+        return v;
+    }
+    if (term_product) {
+        v.TERM = true;
+        if (r.has_rays && r.threads >= 512) v.NT = 512;
+        return v;
+    }
+    // write-through stores while the launch is one round of resident groups, write-back beyond (store_global_): the
+    // sensor-free kernels of one / two waves per group only ever serve batches > 65 536 (choose_threads), the ray kernel of
+    // 256 threads gets a write-back twin for batches > 262 144 (float32 structural fast path).  Copy groups riding in the
+    // launch (lag-1 gather sequences) exist for the write-through float32 instantiations of the structural fast path only;
+    // the caller falls back to a separate gather kernel otherwise.
+    v.NT = group_threads(r.has_rays, r.threads);
+    v.WB = r.has_rays ? (v.NT == 256 && term_ok && many_rounds(r.n_envs) && !r.ride) : (v.NT < 256 && !(fast && r.ride));
+    v.ride = r.ride && fast && !v.WB;
+    v.unsupported = r.ride && !v.ride;
+    return v;
+}
+
+// The resident step sequence (step_seq_kernel): what the plain float32 product kernels of the structural fast path serve,
+// with packed rows; everything else is launched step by step.  Same group shape as select_step picks (`ride` is not read:
+// copy groups never ride in a resident launch).  Stores: a resident launch pays the end-of-kernel write-back of dirty L2
+// lines once per 64 steps, and between its steps every wave waits for its stores to be acknowledged (vmcnt(0) in front of
+// the group's barrier) -- by L2 for plain stores, by memory for write-through ones.  Same-box A/B
+// (profiles/r4/ab_same_box.txt): write-back stores config 2 3.61 -> 3.39 us per step, config 4 8.72 -> 8.52, but config 3
+// 7.05 -> 7.39: the four-wave ray kernels stay written through.
+inline StepVariant select_sequence(const StepRequest& r) {
+    StepVariant v{group_threads(r.has_rays, r.threads), false, false, false, false, false};
+    v.unsupported = r.f64 || !r.sym || r.vk == VK_DENSEB || needs_full_kernel(r) || r.terminal_obs || r.pack == 0;
+    // (the mixed kernel -- two integrating waves writing interleaved lanes of the same lines -- did NOT reproduce the single
+    // launches with write-back stores between resident steps, tests/test_gpu_reset.py: written through like config 3's)
+    v.WB = !r.has_rays || v.NT == 512 || (v.NT == 256 && many_rounds(r.n_envs) && r.vk != VK_MIXED);
+    return v;
+}
+
+// Threads per 64-env group (dockauv_config::threads_per_group == 0: the library's choice): the ray stage spreads over all
+// waves of the group.  Heavy fans on small batches (fewer than ~2 resident waves per SIMD at 256 threads) get 8 waves per
+// group; measured on MI355X: LAUV, 63 rays x 5 capsules, 32 768 envs: 27.5 -> 22.8 us; at 65 536+ envs 256 threads are
+// faster.  Without obstacles extra waves per group (bookkeeper, resetter, second observation wave: the tail of the step cut
+// in two or four) shorten the step while the chip has idle SIMDs; at very large batches one wave per group does the least
+// total work.
+// With obstacles, beyond the batch sizes at which every group is resident at once, ONE wave per group does the least total
+// work and -- since round 4, when its LDS footprint was halved (dockauv_step.hip.inc: SOLO; 16 instead of 8 groups per CU for
+// config 3's fan) -- keeps the most groups in flight.  Same-box measurements (profiles/r4/threads_large.txt), light
+// fan (config 3, 16 beams x 8 spheres) 64 against 256 threads: 131 072 envs 18.4 / 16.7 us, 196 608: 23.0 / 26.0,
+// 262 144: 27.0 / 34.3, 524 288: 50.9 / 69.3, 1 048 576: 117.9 / 175.7; heavy fan (config 4, 63 rays x 5 capsules):
+// 524 288: 115.6 / 113.7, 1 048 576: 236 / 251; mixed vehicles (config 5): 256 threads at every size (229 / 251 at 1 M).
+// One-wave groups of the 63-ray fan against <= 5 capsules keep their completed records in registers (float32:
+// dockauv_step.hip.inc: regrec; 8 -> 16 groups per CU); 64 against 256 threads with that (profiles/r4/threads_large.txt,
+// second table): config 4 163 840 envs 41.4 / 38.2 us, 196 608: 43.1 / 43.8, 262 144: 51.0 / 56.9, 393 216: 69.3 / 82.8,
+// 1 048 576: 154 / 246; config 5 (mixed) 262 144: 53.6 / 50.0, 393 216: 74.5 / 73.9, 524 288: 86.3 / 94.7,
+// 1 048 576: 161 / 215 (vehicle-sorted: 154 / 211).
+inline int choose_threads(bool f64, int n_envs, int n_rays, int max_capsules, int max_spheres, int n_vehicles, int threads_per_group) {
+    if (threads_per_group > 0) return threads_per_group;
+    if (max_capsules + max_spheres == 0) return n_envs <= 65536 ? 256 : (n_envs <= 131072 ? 128 : 64);
+    const bool light = (long)n_rays * (max_capsules + max_spheres) < 256;
+    const bool regrec = !f64 && solo_regrec(max_capsules, max_spheres, ceil_log2(n_rays));
+    if (!light && n_envs <= 32768) return 512;
+    if (light) return n_envs > 163840 ? 64 : 256;
+    if (regrec) return n_envs > (n_vehicles == 1 ? 196608 : 393216) ? 64 : 256;
+    return (n_vehicles == 1 && n_envs > 786432) ? 64 : 256;
+}
+
+// launch one step with the kernel select_step(r) names; implemented in dockauv_kernels_f32.hip / _f64.hip.  ev0 / ev1:
+// optional hipEvent_t recorded at the start / end of this very dispatch (hipExtLaunchKernelGGL).  Returns a hipError_t as int.
+int launch_step_f32(const KernelArgs<float, 2>& a, const StepRequest& r, void* stream, void* ev0 = nullptr, void* ev1 = nullptr);
+int launch_step_f64(const KernelArgs<double, 2>& a, const StepRequest& r, void* stream, void* ev0 = nullptr, void* ev1 = nullptr);
+
+// n <= kSeqMax steps of the handle in ONE launch (every group walks its 64 envs through all of them) with the kernel
+// select_sequence(r) names (dockauv_kernels_seq.hip); hipErrorNotSupported = the caller launches the steps one by one.
+// a.io: everything but actions / obs, which come from `seq`.
+int launch_sequence_f32(const KernelArgs<float, 2>& a, const StepRequest& r, const SeqArgs& seq, void* stream);
 
 #ifdef __HIPCC__
 // Philox4x32-10 (Salmon et al., SC'11): counter-based, integer only -> bit-exact against the NumPy restatement in

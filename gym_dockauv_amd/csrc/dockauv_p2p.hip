@@ -11,11 +11,7 @@
 #include <cstring>
 #include <string>
 
-#include "../../include/dockauv.h"
-
-namespace dockauv {
-extern thread_local std::string g_create_error;   // dockauv_last_error(NULL)
-}
+#include "dockauv_capi.h"
 
 namespace {
 

@@ -27,7 +27,7 @@
 //     out navigation errors and done conditions and shares them through LDS (SHARE_NAV);
 //   * the whole group streams the tile out row-major (what the learner wants) with 16-B coalesced stores.
 // Two instantiations per shape: the PRODUCT kernels (LOG = false) serve the mandatory outputs only; optional inputs /
-// outputs, logging, pool resets, reward set 2 and other fan widths run on the full instantiation (launch_vk).
+// outputs, logging, pool resets, reward set 2 and other fan widths run on the full instantiation (dockauv_device.h: select_step).
 // Numerics: T = float is the product path; T = double instantiates the same code for validation.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -164,8 +164,9 @@ __device__ __forceinline__ P ldgx_(const P* base, long k, long S, unsigned lane)
 // (config 3) spends ~2.5 us there, AFTER its last wave has ended -- a quarter of the event-timed duration
 // (scripts/micro/writeback_cost.hip, profiles/r3/writeback_cost.txt; the `nt` hint changes nothing).  Stores at agent
 // scope (`sc1`) go through to memory while the kernel is still computing and leave nothing to flush: 0.65 us behind the
-// last wave whatever was written.  Every global store of the step kernel's state / outputs is of that kind; nothing
-// written here is read again inside the launch.
+// last wave whatever was written.  Every global store of the step kernel's state / outputs is of that kind.  A single
+// launch reads nothing of what it has written; the resident sequence kernel does, in its next step, and orders the two itself
+// (step_seq_kernel: the inter-step fence, barrier and L1 invalidation).
 #ifndef DOCKAUV_WT_STORES
 #define DOCKAUV_WT_STORES 1
 #endif
@@ -959,7 +960,7 @@ constexpr unsigned kMixedRanks = 0x2310u;
 template <typename T, int NT> constexpr int min_waves_() { return sizeof(T) == 4 ? 4 : 1; }
 
 // LOG = the logging instantiation: state_dot output, episode-storage trace, in-kernel current noise.  Compiled as kernels
-// of their own (launch_vk picks them when a step asks for any of the three): with the same paths behind run-time
+// of their own (select_step picks them when a step asks for any of the three): with the same paths behind run-time
 // branches of the product kernels every BASELINE config lost 5-12 % (same-box A/B, round 2).
 // which kernels run the tail roles in front of the ray-stage barrier (EARLY) and share the integrating wave's navigation
 // errors / done bits through LDS (SHARE_NAV): needed by the kernel body and by the host-side LDS sizing
@@ -980,7 +981,7 @@ constexpr bool share_nav_() {
 // of every env into the tile, and behind the tile's last barrier one wave copies the rows of the finished envs to
 // terminal_obs and zeroes them (the reference's reset observation, Q8) before the tile is streamed out.
 // WB: plain write-back stores (instantiations that serve launches of several rounds of groups only, see store_global_)
-template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool LOG = false, bool TERM = false, bool WB = false, bool SEQ = false>
+template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool LOG = false, bool TERM = false, bool WB = false>
 __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix = threadIdx.x, const unsigned bix = blockIdx.x) {
     DOCKAUV_SPAN(0);   // (diagnostic build: the group's very first instructions)
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -2663,7 +2664,7 @@ __global__ __launch_bounds__(NT, (min_waves_<T, NT>())) void step_seq_kernel(con
         for (unsigned i = 0; i < sizeof(DevArgs) / 8; ++i) Ak.w[i] = src[i];
         Ak.a.io.actions = ka->Q.actions[k];
         Ak.a.io.obs = ka->Q.obs[k];
-        step_body<T, VK, SYM, RAYS, EPG, NT, false, false, WB, true>(Ak.a, tix, bix);
+        step_body<T, VK, SYM, RAYS, EPG, NT, false, false, WB>(Ak.a, tix, bix);
         if (k + 1 < n) {
             // What orders step k + 1 behind step k is the group itself (memory model: workgroup scope; all its waves share one
             // CU and one vector L1): every wave's stores have been performed, the group meets, and the L1 -- only the L1:
@@ -2696,26 +2697,21 @@ static int launch_seq_one(const KernelArgs<T, 2>& a, const SeqArgs& seq, void* s
     return (int)hipGetLastError();
 }
 
-// Same choice of group shape as launch_vk makes for the plain product kernels.  Stores: a resident launch pays the end-of-kernel
-// write-back of dirty L2 lines once per 64 steps, and between its steps every wave waits for its stores to be acknowledged
-// (vmcnt(0) in front of the group's barrier) -- by L2 for plain stores, by memory for write-through ones.  Same-box A/B
-// (profiles/r4/ab_same_box.txt): write-back stores config 2 3.61 -> 3.39 us per step, config 4 8.72 -> 8.52, but config 3
-// 7.05 -> 7.39: the four-wave ray kernels stay written through.
+// the resident instantiations that exist for <float, VK> (select_sequence picks; the mixed kernel's write-back twin of 256
+// threads is compiled and never picked, see there)
 template <typename T, int VK>
-static int launch_seq_vk(const KernelArgs<T, 2>& a, bool has_rays, int threads, const SeqArgs& seq, void* stream) {
-    const bool many_rounds = a.P.E.n_envs > 262144;
-    if (!has_rays) {
-        if (threads >= 256) return launch_seq_one<T, VK, true, false, 64, 256, true>(a, seq, stream);
-        return threads >= 128 ? launch_seq_one<T, VK, true, false, 64, 128, true>(a, seq, stream)
-                              : launch_seq_one<T, VK, true, false, 64, 64, true>(a, seq, stream);
-    }
-    if (threads >= 512) return launch_seq_one<T, VK, true, true, 64, 512, true>(a, seq, stream);
-    if (threads >= 256)
-        // (the mixed kernel -- two integrating waves writing interleaved lanes of the same lines -- did NOT reproduce the single
-        // launches with write-back stores between resident steps, tests/test_gpu_reset.py: written through like config 3's)
-        return (many_rounds && VK != VK_MIXED) ? launch_seq_one<T, VK, true, true, 64, 256, true>(a, seq, stream)
-                                               : launch_seq_one<T, VK, true, true, 64, 256>(a, seq, stream);
-    return launch_seq_one<T, VK, true, true, 64, 64>(a, seq, stream);
+static int launch_seq_vk(const KernelArgs<T, 2>& a, const StepRequest& r, const SeqArgs& seq, void* stream) {
+    const StepVariant v = select_sequence(r);
+    if (v.unsupported) return (int)hipErrorNotSupported;
+    const auto is = [&](bool rays, int nt, bool wb) { return r.has_rays == rays && v.NT == nt && v.WB == wb; };
+    if (is(false, 256, true)) return launch_seq_one<T, VK, true, false, 64, 256, true>(a, seq, stream);
+    if (is(false, 128, true)) return launch_seq_one<T, VK, true, false, 64, 128, true>(a, seq, stream);
+    if (is(false, 64, true)) return launch_seq_one<T, VK, true, false, 64, 64, true>(a, seq, stream);
+    if (is(true, 512, true)) return launch_seq_one<T, VK, true, true, 64, 512, true>(a, seq, stream);
+    if (is(true, 256, true)) return launch_seq_one<T, VK, true, true, 64, 256, true>(a, seq, stream);
+    if (is(true, 256, false)) return launch_seq_one<T, VK, true, true, 64, 256>(a, seq, stream);
+    if (is(true, 64, false)) return launch_seq_one<T, VK, true, true, 64, 64>(a, seq, stream);
+    return (int)hipErrorNotSupported;
 }
 
 // ------------------------------------------------------------------------------------------ launchers
@@ -2769,71 +2765,50 @@ static int launch_one(const KernelArgs<T, 2>& a, void* stream, void* ev0, void* 
     return (int)hipGetLastError();
 }
 
+// the instantiations that exist for <T, VK, SYM> (select_step picks; launch_one takes the ride branch of a plain one)
 template <typename T, int VK, bool SYM>
-static int launch_vk(const KernelArgs<T, 2>& a, bool has_rays, int threads, void* stream, void* ev0, void* ev1) {
-    // The product instantiations cover what a throughput rollout runs: mandatory outputs only, reward set 1, reset modes
-    // NONE (the caller resets) and DEVICE (in-kernel episode generation), fans of 9..16 or 33..64 rays.  Everything else --
-    // optional inputs / outputs, reset mode POOL (host-staged next episodes), reward set 2, other fan widths -- is served by
-    // the full instantiation (one group shape each): with those paths behind run-time branches of one kernel, every
-    // BASELINE config ran 5-12 % slower.
-    const EnvP<T>& E_ = a.P.E;
-    const bool odd_fan = has_rays && !(E_.ray_pad_log2 == 6 || E_.ray_pad_log2 == 4);
-    // product kernels that also deliver terminal observations (TERM): float32, structural fast path, packed rows, the two
-    // default group shapes -- what a device-resident learner runs (TorchDocking3d.step(want_terminal_obs=True))
+static int launch_vk(const KernelArgs<T, 2>& a, const StepRequest& r, void* stream, void* ev0, void* ev1) {
+    const StepVariant v = select_step(r);
+    if (v.unsupported) return (int)hipErrorNotSupported;
+    const auto is = [&](bool rays, int nt, bool log = false, bool term = false, bool wb = false) {
+        return r.has_rays == rays && v.NT == nt && v.LOG == log && v.TERM == term && v.WB == wb;
+    };
     constexpr bool TERM_OK = sizeof(T) == 4 && SYM && VK != VK_DENSEB;
-    const bool term_product = TERM_OK && a.io.terminal_obs && a.io.pack && !a.ride.plan;
-    if (a.io.state_dot || a.io.trace || a.io.device_noise || E_.reset_mode == 1 || E_.reward_set == 2 || odd_fan ||
-        a.io.noise || a.io.reward_terms || a.io.conditions || a.io.nav || a.io.ray_dist || (a.io.terminal_obs && !term_product))
-        return has_rays ? launch_one<T, VK, SYM, true, 64, 256, true>(a, stream, ev0, ev1)
-                        : launch_one<T, VK, SYM, false, 64, 256, true>(a, stream, ev0, ev1);
+    if (is(true, 256, true)) return launch_one<T, VK, SYM, true, 64, 256, true>(a, stream, ev0, ev1);
+    if (is(false, 256, true)) return launch_one<T, VK, SYM, false, 64, 256, true>(a, stream, ev0, ev1);
     if constexpr (TERM_OK) {
-        if (term_product) {
-            if (!has_rays) return launch_one<T, VK, SYM, false, 64, 256, false, true>(a, stream, ev0, ev1);
-            return threads >= 512 ? launch_one<T, VK, SYM, true, 64, 512, false, true>(a, stream, ev0, ev1)
-                                  : launch_one<T, VK, SYM, true, 64, 256, false, true>(a, stream, ev0, ev1);
-        }
+        if (is(false, 256, false, true)) return launch_one<T, VK, SYM, false, 64, 256, false, true>(a, stream, ev0, ev1);
+        if (is(true, 512, false, true)) return launch_one<T, VK, SYM, true, 64, 512, false, true>(a, stream, ev0, ev1);
+        if (is(true, 256, false, true)) return launch_one<T, VK, SYM, true, 64, 256, false, true>(a, stream, ev0, ev1);
+        if (is(true, 256, false, false, true)) return launch_one<T, VK, SYM, true, 64, 256, false, false, true>(a, stream, ev0, ev1);
     }
-    // write-through stores while the launch is one round of resident groups, write-back beyond (store_global_): the
-    // sensor-free kernels of one / two waves per group only ever serve batches > 65 536 (dockauv_create: threads), the ray
-    // kernel of 256 threads gets a write-back twin for batches > 262 144 (float32 structural fast path)
-    const bool many_rounds = E_.n_envs > 262144;   // (config 3: 262 144 envs 34.5 us write-through / 35.6 write-back; 1 048 576: 191 / 165)
-    if (!has_rays) {
-        if (threads >= 256) return launch_one<T, VK, SYM, false, 64, 256>(a, stream, ev0, ev1);
-        if constexpr (sizeof(T) == 4 && SYM) {
-            // copy groups riding in the launch (lag-1 gather sequences) exist for the write-through instantiations only
-            if (a.ride.plan)
-                return threads >= 128 ? launch_one<T, VK, SYM, false, 64, 128>(a, stream, ev0, ev1)
-                                      : launch_one<T, VK, SYM, false, 64, 64>(a, stream, ev0, ev1);
-        }
-        return threads >= 128 ? launch_one<T, VK, SYM, false, 64, 128, false, false, true>(a, stream, ev0, ev1)
-                              : launch_one<T, VK, SYM, false, 64, 64, false, false, true>(a, stream, ev0, ev1);
+    if (is(false, 256)) return launch_one<T, VK, SYM, false, 64, 256>(a, stream, ev0, ev1);
+    if constexpr (sizeof(T) == 4 && SYM) {
+        if (is(false, 128)) return launch_one<T, VK, SYM, false, 64, 128>(a, stream, ev0, ev1);
+        if (is(false, 64)) return launch_one<T, VK, SYM, false, 64, 64>(a, stream, ev0, ev1);
     }
-    if (threads >= 512) return launch_one<T, VK, SYM, true, 64, 512>(a, stream, ev0, ev1);
-    if (threads >= 256) {
-        if constexpr (TERM_OK) {
-            if (many_rounds && !a.ride.plan) return launch_one<T, VK, SYM, true, 64, 256, false, false, true>(a, stream, ev0, ev1);
-        }
-        return launch_one<T, VK, SYM, true, 64, 256>(a, stream, ev0, ev1);
-    }
-    return launch_one<T, VK, SYM, true, 64, 64>(a, stream, ev0, ev1);
+    if (is(false, 128, false, false, true)) return launch_one<T, VK, SYM, false, 64, 128, false, false, true>(a, stream, ev0, ev1);
+    if (is(false, 64, false, false, true)) return launch_one<T, VK, SYM, false, 64, 64, false, false, true>(a, stream, ev0, ev1);
+    if (is(true, 512)) return launch_one<T, VK, SYM, true, 64, 512>(a, stream, ev0, ev1);
+    if (is(true, 256)) return launch_one<T, VK, SYM, true, 64, 256>(a, stream, ev0, ev1);
+    if (is(true, 64)) return launch_one<T, VK, SYM, true, 64, 64>(a, stream, ev0, ev1);
+    return (int)hipErrorNotSupported;
 }
 
 template <typename T, bool SYM>
-static int launch_sym(const KernelArgs<T, 2>& a, int vk, bool has_rays, int threads, void* stream, void* ev0, void* ev1) {
-    switch (vk) {
-        case VK_JOY: return launch_vk<T, VK_JOY, SYM>(a, has_rays, threads, stream, ev0, ev1);
-        case VK_DENSEB: return launch_vk<T, VK_DENSEB, SYM>(a, has_rays, threads, stream, ev0, ev1);
-        case VK_LAUV: return launch_vk<T, VK_LAUV, SYM>(a, has_rays, threads, stream, ev0, ev1);
-        case VK_MIXED: return launch_vk<T, VK_MIXED, SYM>(a, has_rays, threads, stream, ev0, ev1);
+static int launch_sym(const KernelArgs<T, 2>& a, const StepRequest& r, void* stream, void* ev0, void* ev1) {
+    switch (r.vk) {
+        case VK_JOY: return launch_vk<T, VK_JOY, SYM>(a, r, stream, ev0, ev1);
+        case VK_DENSEB: return launch_vk<T, VK_DENSEB, SYM>(a, r, stream, ev0, ev1);
+        case VK_LAUV: return launch_vk<T, VK_LAUV, SYM>(a, r, stream, ev0, ev1);
+        case VK_MIXED: return launch_vk<T, VK_MIXED, SYM>(a, r, stream, ev0, ev1);
     }
     return (int)hipErrorInvalidValue;
 }
 
 template <typename T>
-static int launch_t(const KernelArgs<T, 2>& a, int vk, bool sym, bool has_rays, int threads, void* stream, void* ev0,
-                    void* ev1) {
-    return sym ? launch_sym<T, true>(a, vk, has_rays, threads, stream, ev0, ev1)
-               : launch_sym<T, false>(a, vk, has_rays, threads, stream, ev0, ev1);
+static int launch_t(const KernelArgs<T, 2>& a, const StepRequest& r, void* stream, void* ev0, void* ev1) {
+    return r.sym ? launch_sym<T, true>(a, r, stream, ev0, ev1) : launch_sym<T, false>(a, r, stream, ev0, ev1);
 }
 
 #if defined(DOCKAUV_STAMPS) && defined(DOCKAUV_INSTANTIATE_F32)
@@ -2845,26 +2820,24 @@ int read_span(unsigned long long* out, int groups) {
 }
 #endif
 #ifdef DOCKAUV_INSTANTIATE_F32
-int launch_step_f32(const KernelArgs<float, 2>& a, int vk, bool sym, bool has_rays, int threads, void* stream,
-                    void* ev0, void* ev1) {
-    return launch_t<float>(a, vk, sym, has_rays, threads, stream, ev0, ev1);
+int launch_step_f32(const KernelArgs<float, 2>& a, const StepRequest& r, void* stream, void* ev0, void* ev1) {
+    return launch_t<float>(a, r, stream, ev0, ev1);
 }
 #endif
 #ifdef DOCKAUV_INSTANTIATE_SEQ
-int launch_sequence_f32(const KernelArgs<float, 2>& a, int vk, bool sym, bool has_rays, int threads, const SeqArgs& seq, void* stream) {
-    if (!sym || seq.n < 1 || seq.n > kSeqMax) return (int)hipErrorNotSupported;
-    switch (vk) {
-        case VK_JOY: return launch_seq_vk<float, VK_JOY>(a, has_rays, threads, seq, stream);
-        case VK_LAUV: return launch_seq_vk<float, VK_LAUV>(a, has_rays, threads, seq, stream);
-        case VK_MIXED: return launch_seq_vk<float, VK_MIXED>(a, has_rays, threads, seq, stream);
+int launch_sequence_f32(const KernelArgs<float, 2>& a, const StepRequest& r, const SeqArgs& seq, void* stream) {
+    if (seq.n < 1 || seq.n > kSeqMax) return (int)hipErrorNotSupported;
+    switch (r.vk) {
+        case VK_JOY: return launch_seq_vk<float, VK_JOY>(a, r, seq, stream);
+        case VK_LAUV: return launch_seq_vk<float, VK_LAUV>(a, r, seq, stream);
+        case VK_MIXED: return launch_seq_vk<float, VK_MIXED>(a, r, seq, stream);
     }
     return (int)hipErrorNotSupported;
 }
 #endif
 #ifdef DOCKAUV_INSTANTIATE_F64
-int launch_step_f64(const KernelArgs<double, 2>& a, int vk, bool sym, bool has_rays, int threads, void* stream,
-                    void* ev0, void* ev1) {
-    return launch_t<double>(a, vk, sym, has_rays, threads, stream, ev0, ev1);
+int launch_step_f64(const KernelArgs<double, 2>& a, const StepRequest& r, void* stream, void* ev0, void* ev1) {
+    return launch_t<double>(a, r, stream, ev0, ev1);
 }
 #endif
 

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Which of the compiled kernels does the GPU suite launch?  Writes the record profiles/coverage/kernels.txt.
 
-The library picks its kernel at run time from a family of template instantiations (dockauv_step.hip.inc: launch_vk,
-launch_seq_vk; dockauv_policy.hip: launch_policy_forward), and one instantiation of a correct source can be wrong while its
+The library picks its kernel at run time from a family of template instantiations (dockauv_device.h: select_step,
+select_sequence; dockauv_policy.hip: launch_policy_forward), and one instantiation of a correct source can be wrong while its
 siblings are exact (csrc/build.py: PER_SOURCE_FLAGS; profiles/r4/ab_same_box.txt).  This script joins
 
   * the compiled kernels: the function names in the resource-usage remarks of `python gym_dockauv_amd/csrc/build.py --usage`

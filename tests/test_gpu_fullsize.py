@@ -126,7 +126,7 @@ def test_one_wave_ray_groups_vs_reference(which, precision):
 
 
 def test_group_shape_the_library_picks():
-    """threads_per_group = 0: dockauv_create's choice by workload and batch size (dockauv_capi.hip; the tables behind it:
+    """threads_per_group = 0: dockauv_create's choice by workload and batch size (dockauv_device.h: choose_threads; the tables behind it:
     profiles/r4/threads_large.txt), read back through dockauv_threads_per_group."""
     import sys
     import os
