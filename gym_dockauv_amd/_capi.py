@@ -136,6 +136,25 @@ class PPOHeadIO(C.Structure):
     ]
 
 
+class OptimDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved", C.c_uint32),
+        ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+        ("max_grad_norm", C.c_float), ("reserved1", C.c_float),
+    ]
+
+
+class OptimIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved", C.c_uint32),
+        ("lr", C.c_double),
+        ("actor_params", C.c_void_p * 6), ("log_std", C.c_void_p),
+        ("actor_grads", C.c_void_p * 6), ("grad_log_std", C.c_void_p),
+        ("critic_params", C.c_void_p * 6), ("critic_grads", C.c_void_p * 6),
+        ("stats", C.c_void_p),
+    ]
+
+
 # every symbol include/dockauv.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("dockauv_abi_version", C.c_int, []),
@@ -188,6 +207,11 @@ SYMBOLS = [
     ("dockauv_policy_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
                                           C.POINTER(PolicyGrads), C.c_void_p]),
     ("dockauv_ppo_head", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PPOHeadIO), C.c_void_p]),
+    ("dockauv_optim_create", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(OptimDesc), C.POINTER(C.c_void_p)]),
+    ("dockauv_optim_destroy", C.c_int, [C.c_void_p]),
+    ("dockauv_optim_step", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(OptimIO), C.c_void_p]),
+    ("dockauv_optim_state", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong),
+                                      C.POINTER(C.c_longlong)]),
 ]
 
 _lib: Optional[C.CDLL] = None

@@ -1,5 +1,7 @@
 // dockauv_capi_policy.hip -- C ABI of libdockauv.so (include/dockauv.h), second part: MLP policy and critic, closed-loop
-// rollout, PPO collector, backward and head.  The kernels are in dockauv_policy / _collect / _backward / _head.hip.
+// rollout, PPO collector, backward, head and optimiser.  The kernels are in dockauv_policy / _collect / _backward / _head /
+// _optim.hip.
+#include <cmath>
 #include <cstring>
 
 #include "dockauv_capi.h"
@@ -17,6 +19,17 @@ struct dockauv_policy_s {
     uint64_t seed = 0, env_id_offset = 0;
     float* bwd_partial = nullptr; // dockauv_policy_backward's per-group partial sums, allocated by the first backward
     double* head_ws = nullptr;    // dockauv_ppo_head's moment and row-sum partials (kHeadWorkspaceBytes), allocated by the first head call
+};
+
+struct dockauv_optim_s {
+    dockauv_handle h = nullptr;
+    dockauv_policy actor = nullptr, critic = nullptr;   // critic: nullable
+    double beta1 = 0.9, beta2 = 0.999, eps = 1e-5;
+    float max_grad_norm = 0.0f;
+    long long t = 0;              // steps taken
+    int len[kOptSegments] = {};   // the index space: actor W1 b1 W2 b2 W3 b3, log_std, critic W1 b1 W2 b2 W3 b3
+    int total = 0;
+    float *m = nullptr, *v = nullptr;   // [total] each, one allocation (m first)
 };
 
 namespace {
@@ -197,6 +210,46 @@ int create_policy(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy
     }
     *out = p;
     return 0;
+}
+
+// lengths of W1 b1 W2 b2 W3 b3 of a policy, torch.nn.Linear layout
+void layer_lengths(const PolicyShape& S, int* len) {
+    const int n_last = S.n_h2 ? S.n_h2 : S.n_h1;
+    len[0] = S.n_h1 * S.n_in;
+    len[1] = S.n_h1;
+    len[2] = S.n_h2 * S.n_h1;
+    len[3] = S.n_h2;
+    len[4] = S.n_out * n_last;
+    len[5] = S.n_out;
+}
+
+// one network's six parameter / gradient pointers against its segment lengths; `who`: "actor" / "critic"
+int check_optim_arrays(dockauv_handle h, const char* who, const int* len, float* const* params, const float* const* grads) {
+    static const char* const names[6] = {"W1", "b1", "W2", "b2", "W3", "b3"};
+    for (int i = 0; i < 6; ++i) {
+        if (len[i] > 0 && !params[i]) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.%s_params[%d] (%s) is NULL", who, i, names[i]);
+        if (len[i] > 0 && !grads[i]) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.%s_grads[%d] (%s) is NULL", who, i, names[i]);
+        if (len[i] == 0 && params[i])
+            return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.%s_params[%d] (%s) must be NULL: the optimiser's shapes have no such array", who, i, names[i]);
+        if (len[i] == 0 && grads[i])
+            return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.%s_grads[%d] (%s) must be NULL: the optimiser's shapes have no such array", who, i, names[i]);
+        if (len[i] > 0 && (const float*)params[i] == grads[i])
+            return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.%s_grads[%d] (%s) is the params pointer: gradients are read only, parameters written", who, i, names[i]);
+    }
+    return 0;
+}
+
+// the policy's weights from the six device arrays (and log_std), packed on `stream`: dockauv_policy_load with device pointers,
+// keeping the policy's seed and env id offset
+int repack_policy(dockauv_policy p, float* const* params, const float* log_std, hipStream_t stream) {
+    dockauv_policy_desc d{};
+    d.struct_size = sizeof(dockauv_policy_desc);
+    d.pointers_on_device = 1;
+    d.W1 = params[0]; d.b1 = params[1]; d.W2 = params[2]; d.b2 = params[3]; d.W3 = params[4]; d.b3 = params[5];
+    d.log_std = log_std;
+    d.seed = p->seed;
+    d.env_id_offset = p->env_id_offset;
+    return upload_policy(p, &d, stream);
 }
 
 }  // namespace
@@ -413,6 +466,112 @@ int dockauv_rollout(dockauv_handle h, dockauv_policy p, const float* rows_in, fl
     if (int rc = queue_rollout(h, p, rows_in, rows_out, actions_out, terminal_obs, nullptr, n_steps, t0, stochastic, (hipStream_t)hip_stream))
         return rc;
     return check_status(h);   // (what dockauv_poll_status looks at: no synchronisation)
+}
+
+int dockauv_optim_create(dockauv_handle h, dockauv_policy actor, dockauv_policy critic, const dockauv_optim_desc* d, dockauv_optim* out) {
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_optim_create: null handle");
+    if (!out) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_create: out is NULL");
+    *out = nullptr;
+    if (!actor) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_create: null actor");
+    if (!d) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_create: desc is NULL");
+    if (d->struct_size != sizeof(dockauv_optim_desc))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_desc.struct_size: got %u, library has %zu", d->struct_size, sizeof(dockauv_optim_desc));
+    if (actor->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_create: the actor was created for another handle");
+    if (actor->value_role) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_create: the actor argument is a critic (dockauv_value_create)");
+    if (!actor->has_log_std) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_create: the actor has no log_std (its gradient is part of the index space)");
+    if (critic)
+        if (int rc = check_critic(h, critic, "dockauv_optim_create")) return rc;
+    if (!(d->beta1 >= 0.0 && d->beta1 < 1.0)) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_desc.beta1: %g outside [0, 1)", d->beta1);
+    if (!(d->beta2 >= 0.0 && d->beta2 < 1.0)) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_desc.beta2: %g outside [0, 1)", d->beta2);
+    if (!(d->eps > 0.0) || !std::isfinite(d->eps)) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_desc.eps: %g must be > 0", d->eps);
+    if (std::isnan(d->max_grad_norm)) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_desc.max_grad_norm is NaN");
+    HIP_TRY(h, hipSetDevice(h->device));
+    dockauv_optim o = new dockauv_optim_s();
+    o->h = h;
+    o->actor = actor;
+    o->critic = critic;
+    o->beta1 = d->beta1;
+    o->beta2 = d->beta2;
+    o->eps = d->eps;
+    o->max_grad_norm = d->max_grad_norm;
+    layer_lengths(actor->S, o->len);
+    o->len[6] = actor->S.n_out;
+    if (critic) layer_lengths(critic->S, o->len + 7);
+    for (int s = 0; s < kOptSegments; ++s) o->total += o->len[s];
+    hipError_t e = hipMalloc((void**)&o->m, 2 * (size_t)o->total * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(o->m, 0, 2 * (size_t)o->total * sizeof(float));
+    if (e != hipSuccess) {
+        dockauv_optim_destroy(o);
+        return fail(h, DOCKAUV_E_HIP, "optimiser state: %s", hipGetErrorString(e));
+    }
+    o->v = o->m + o->total;
+    *out = o;
+    return 0;
+}
+
+int dockauv_optim_destroy(dockauv_optim o) {
+    if (!o) return 0;
+    if (o->h) (void)hipSetDevice(o->h->device);
+    (void)hipDeviceSynchronize();
+    if (o->m) (void)hipFree(o->m);
+    delete o;
+    return 0;
+}
+
+int dockauv_optim_state(dockauv_optim o, float** m, float** v, long long* n_elements, long long* steps) {
+    if (!o) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_optim_state: null optimiser");
+    if (m) *m = o->m;
+    if (v) *v = o->v;
+    if (n_elements) *n_elements = o->total;
+    if (steps) *steps = o->t;
+    return 0;
+}
+
+int dockauv_optim_step(dockauv_handle h, dockauv_optim o, const dockauv_optim_io* io, void* hip_stream) {
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_optim_step: null handle");
+    if (!o) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_step: null optimiser");
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_step: io is NULL");
+    if (io->struct_size != sizeof(dockauv_optim_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_optim_io));
+    if (o->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_step: the optimiser was created for another handle");
+    if (!(io->lr >= 0.0) || !std::isfinite(io->lr)) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.lr: %g must be >= 0 and finite", io->lr);
+    if (int rc = check_optim_arrays(h, "actor", o->len, io->actor_params, io->actor_grads)) return rc;
+    if (!io->log_std) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.log_std is NULL");
+    if (!io->grad_log_std) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.grad_log_std is NULL");
+    if ((const float*)io->log_std == io->grad_log_std)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.grad_log_std is the log_std pointer: gradients are read only, parameters written");
+    if (int rc = check_optim_arrays(h, "critic", o->len + 7, io->critic_params, io->critic_grads)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const long long t = ++o->t;
+    AdamArgs a{};
+    for (int i = 0; i < 6; ++i) {
+        a.p[i] = io->actor_params[i];
+        a.g[i] = io->actor_grads[i];
+        a.p[7 + i] = io->critic_params[i];
+        a.g[7 + i] = io->critic_grads[i];
+    }
+    a.p[6] = io->log_std;
+    a.g[6] = io->grad_log_std;
+    for (int s = 0; s < kOptSegments; ++s) a.len[s] = o->len[s];
+    a.m = o->m;
+    a.v = o->v;
+    a.stats = io->stats;
+    a.total = o->total;
+    a.max_grad_norm = o->max_grad_norm;
+    a.c1 = (float)(1.0 - o->beta1);
+    a.c2 = (float)(1.0 - o->beta2);
+    a.b2 = (float)o->beta2;
+    a.step_size = (float)(io->lr / (1.0 - std::pow(o->beta1, (double)t)));
+    a.rsq = (float)(1.0 / std::sqrt(1.0 - std::pow(o->beta2, (double)t)));
+    a.eps = (float)o->eps;
+    const int rc = launch_adam_step(a, stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "optimiser launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = stream;
+    if (int rc2 = repack_policy(o->actor, io->actor_params, io->log_std, stream)) return rc2;
+    if (o->critic)
+        if (int rc2 = repack_policy(o->critic, io->critic_params, nullptr, stream)) return rc2;
+    return 0;
 }
 
 }  // extern "C"

@@ -521,6 +521,28 @@ struct HeadArgs {
 // group order.  Returns a hipError_t as int.
 int launch_ppo_head(const HeadArgs& a, void* stream);
 
+// ------------------------------------------------------------------------------------------ optimiser (dockauv_optim.hip)
+// Gradient-norm clipping and one Adam step (include/dockauv.h: dockauv_optim_step states the arithmetic) over one index space
+// of kOptSegments arrays back to back: actor W1 b1 W2 b2 W3 b3, log_std, critic W1 b1 W2 b2 W3 b3, torch.nn.Linear layout; a
+// segment may be empty (len 0, its pointers unread).  One launch of ceil(total / kOptThreads) groups, no workspace: every group
+// forms the whole norm itself (a lane has kOptChunk loads in flight), then thread i of the grid updates element i.  m, v: the
+// moments, [total] in index-space order.
+constexpr int kOptSegments = 13;
+constexpr int kOptThreads = 1024;
+constexpr int kOptChunk = 4;
+struct AdamArgs {
+    float* p[kOptSegments];               // updated in place
+    const float* g[kOptSegments];         // read only
+    int len[kOptSegments];
+    float *m, *v;                         // [total], updated in place
+    float* stats;                         // nullable [2]: norm before clipping, coef
+    int total;                            // sum of len
+    float max_grad_norm;                  // <= 0: no clipping (coef = 1)
+    float c1, c2, b2, step_size, rsq, eps;   // host scalars of this step (dockauv_optim_step)
+};
+// Returns a hipError_t as int.
+int launch_adam_step(const AdamArgs& a, void* stream);
+
 #ifdef DOCKAUV_STAMPS
 int read_stamps(unsigned long long* out);   // diagnostic build only
 int read_span(unsigned long long* out, int groups);

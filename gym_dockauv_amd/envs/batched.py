@@ -761,6 +761,52 @@ class BatchedDocking3d:
         rc = self._lib.dockauv_ppo_head(self._handle, policy.ptr, C.byref(io), C.c_void_p(stream or None))
         _capi.check(self._lib, self._handle, rc, "dockauv_ppo_head")
 
+    def make_optim(self, policy, value=None, betas=(0.9, 0.999), eps: float = 1e-5, max_grad_norm: float = 0.5):
+        """Adam with gradient-norm clipping for ``policy`` (an actor with a log_std), its log_std and ``value`` (a critic, or
+        None): dockauv_optim_create.  The moments start at zero; ``max_grad_norm`` <= 0: no clipping.  ``close`` destroys it
+        before the policies."""
+        from ..policy import DeviceOptim
+        d = _capi.OptimDesc()
+        d.struct_size = C.sizeof(_capi.OptimDesc)
+        d.beta1, d.beta2, d.eps, d.max_grad_norm = float(betas[0]), float(betas[1]), float(eps), float(max_grad_norm)
+        ptr = C.c_void_p()
+        rc = self._lib.dockauv_optim_create(self._handle, policy.ptr, value.ptr if value is not None else None, C.byref(d), C.byref(ptr))
+        _capi.check(self._lib, self._handle, rc, "dockauv_optim_create")
+        opt = DeviceOptim(ptr, policy, value)
+        self._optims = getattr(self, "_optims", []) + [opt]
+        return opt
+
+    def optim_step_device(self, opt, lr: float, actor_param_ptrs, log_std_ptr: int, actor_grad_ptrs, grad_log_std_ptr: int,
+                          critic_param_ptrs=None, critic_grad_ptrs=None, stats_ptr: int = 0, stream: int = 0) -> None:
+        """One clipped Adam step on device pointers (dockauv_optim_step): ``*_ptrs`` = (W1, b1, W2, b2, W3, b3) addresses of
+        contiguous float32 arrays in torch.nn.Linear layout (W2 / b2 0 with one hidden layer; the critic's None without one),
+        the parameters updated in place, the gradients only read; stats float32 [2] or 0 (norm before clipping, coef).  Both
+        networks hold the new weights afterwards (no ``load_policy`` needed); asynchronous."""
+        io = _capi.OptimIO()
+        io.struct_size = C.sizeof(_capi.OptimIO)
+        io.lr = float(lr)
+        for dst, src in ((io.actor_params, actor_param_ptrs), (io.actor_grads, actor_grad_ptrs),
+                         (io.critic_params, critic_param_ptrs), (io.critic_grads, critic_grad_ptrs)):
+            for i, x in enumerate(src if src is not None else [0] * 6):
+                dst[i] = int(x) or None
+        io.log_std, io.grad_log_std, io.stats = log_std_ptr or None, grad_log_std_ptr or None, stats_ptr or None
+        rc = self._lib.dockauv_optim_step(self._handle, opt.ptr, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_optim_step")
+        opt.policy.has_log_std = True
+
+    def optim_state(self, opt):
+        """(device address of m, of v, number of elements of each, steps taken): dockauv_optim_state.  m and v are float32 in
+        the order actor W1 b1 W2 b2 W3 b3, log_std, critic W1 b1 W2 b2 W3 b3."""
+        m, v, n, t = C.c_void_p(), C.c_void_p(), C.c_longlong(), C.c_longlong()
+        rc = self._lib.dockauv_optim_state(opt.ptr, C.byref(m), C.byref(v), C.byref(n), C.byref(t))
+        _capi.check(self._lib, self._handle, rc, "dockauv_optim_state")
+        return int(m.value or 0), int(v.value or 0), int(n.value), int(t.value)
+
+    def destroy_optim(self, opt) -> None:
+        if opt.ptr is not None and opt.ptr.value:
+            self._lib.dockauv_optim_destroy(opt.ptr)
+            opt.ptr = C.c_void_p()
+
     def destroy_policy(self, policy) -> None:
         if policy.ptr is not None and policy.ptr.value:
             self._lib.dockauv_policy_destroy(policy.ptr)
@@ -791,6 +837,9 @@ class BatchedDocking3d:
     # ------------------------------------------------------------------------------------------ VecEnv odds and ends
     def close(self) -> None:
         if getattr(self, "_handle", None) is not None and self._handle.value:
+            for opt in getattr(self, "_optims", []):     # (an optimiser goes before its policies)
+                self.destroy_optim(opt)
+            self._optims = []
             for pol in getattr(self, "_policies", []):   # (a policy goes before its handle)
                 self.destroy_policy(pol)
             self._policies = []

@@ -243,20 +243,25 @@ class TorchDocking3d:
                                               stream=torch.cuda.current_stream().cuda_stream)
         return out
 
-    def mlp_backward(self, policy, rows, grad_out, index=None):
+    def mlp_backward(self, policy, rows, grad_out, index=None, out=None):
         """The gradients of all weights and biases of ``policy`` for ``grad_out`` [B, n_out] = dL/d(mlp_forward(policy, rows,
         index)): dockauv_policy_backward on the current stream.  Returns fresh tensors (dW1, db1[, dW2, db2], dW3, db3) in
-        torch.nn.Linear layout.  Reproducible bit for bit; no gradient with respect to the rows."""
+        torch.nn.Linear layout, or -- ``out``: such a sequence of contiguous float32 device tensors -- writes into those and
+        returns them.  Reproducible bit for bit; no gradient with respect to the rows."""
         torch = self.torch
         ptr, B = self._mlp_rows(policy, rows, index)
         if grad_out.device != self.device or grad_out.dtype != torch.float32 or not grad_out.is_contiguous() \
                 or tuple(grad_out.shape) != (B, policy.n_out):
             raise ValueError(f"grad_out must be a contiguous float32 [{B}, {policy.n_out}] tensor on {self.device}")
         widths = [policy.n_in] + policy.n_hidden + [policy.n_out]
-        grads = []
-        for i in range(len(widths) - 1):
-            grads += [torch.empty((widths[i + 1], widths[i]), device=self.device, dtype=torch.float32),
-                      torch.empty((widths[i + 1],), device=self.device, dtype=torch.float32)]
+        shapes = [s for i in range(len(widths) - 1) for s in ((widths[i + 1], widths[i]), (widths[i + 1],))]
+        if out is None:
+            grads = [torch.empty(s, device=self.device, dtype=torch.float32) for s in shapes]
+        else:
+            grads = list(out)
+            if len(grads) != len(shapes) or any(g.device != self.device or g.dtype != torch.float32 or not g.is_contiguous()
+                                                or tuple(g.shape) != s for g, s in zip(grads, shapes)):
+                raise ValueError(f"out must be contiguous float32 tensors of shapes {shapes} on {self.device}")
         ptrs = [g.data_ptr() for g in grads]
         if len(ptrs) == 4:
             ptrs[2:2] = [0, 0]
@@ -346,6 +351,79 @@ class TorchDocking3d:
         log_std.grad = grad_log_std
         return stats
 
+    # ------------------------------------------------------------------------------------------ the optimiser and the whole update
+    def make_optimizer(self, policy, value, actor_params, log_std, critic_params, betas=(0.9, 0.999), eps: float = 1e-5,
+                       max_grad_norm: float = 0.5):
+        """Adam with gradient-norm clipping on the device (dockauv_optim_*) for the learner's own tensors: ``actor_params`` /
+        ``critic_params`` = (W1, b1[, W2, b2], W3, b3) and ``log_std``, contiguous float32 tensors on this device (e.g.
+        ``list(net.parameters())``) of the shapes of ``policy`` / ``value``.  The returned ``DeviceAdam`` keeps references to
+        them and updates them IN PLACE (an ``nn.Sequential`` that holds them sees the new weights); it owns gradient buffers of
+        the same shapes (``opt.grads``).  ``value=None`` together with ``critic_params=None``: actor only.  Defaults: SB3's PPO
+        (Adam with eps 1e-5, max_grad_norm 0.5; ``max_grad_norm`` <= 0: no clipping)."""
+        return DeviceAdam(self, policy, value, actor_params, log_std, critic_params, betas, eps, max_grad_norm)
+
+    def ppo_update(self, opt, collected, n_epochs: int, batch_size: int, lr: float, *, clip_range: float, vf_coef: float,
+                   ent_coef: float, normalize_advantage: bool = True, generator=None):
+        """SB3's PPO.train loop on one ``Collected`` (of ``collect`` with the optimiser's actor and critic), queued on the
+        current stream without a host synchronisation: per epoch one ``torch.randperm(K * N, device=..., generator=generator)``
+        split into minibatches of ``batch_size`` rows (the last may be shorter, as in SB3; refused when it would have one row
+        and ``normalize_advantage`` is on); per minibatch ``mlp_forward`` of both networks, the PPO head, ``mlp_backward`` of
+        both into ``opt.grads`` and ``opt.step(lr)``.  The weights are loaded once at the start from the optimiser's tensors
+        (so the call is right even when the caller changed them in between); inside the loop the optimiser's repack is the load,
+        and after the call both networks hold the last step's weights: the next ``collect`` needs no ``load_policy``.  Returns
+        stats [n_epochs, n_minibatches, 10] on the device: the head's eight (``ppo_head``), the gradient norm before clipping
+        and the clipping coefficient.  SB3's ``target_kl`` early stop needs the host and is left to the caller, who can run
+        ``n_epochs=1`` per call and look at column 4 (approx_kl) in between."""
+        torch = self.torch
+        c, policy, value = collected, opt.policy, opt.value
+        n_epochs, batch_size = int(n_epochs), int(batch_size)
+        if n_epochs < 1 or batch_size < 1:
+            raise ValueError("n_epochs and batch_size must be >= 1")
+        if c.log_prob is None or (value is not None and (c.advantages is None or c.returns is None)) or c.advantages is None:
+            raise ValueError("collected must hold log_prob and advantages (and returns with a critic): collect() with a critic")
+        K, N = int(c.actions.shape[0]), int(c.actions.shape[1])
+        M = K * N
+        n_mb = (M + batch_size - 1) // batch_size
+        if normalize_advantage and M - (n_mb - 1) * batch_size == 1:
+            raise ValueError(f"the last minibatch of {M} rows in batches of {batch_size} would have one row: advantage "
+                             "normalisation needs two (another batch_size, or normalize_advantage=False)")
+        rows = c.obs[:K]
+        row_ptr, n_rows = self._mlp_rows(policy, rows, None)
+        if n_rows != M:
+            raise ValueError("collected.obs must be [K + 1, N, n_obs] for actions [K, N, n_u]")
+        flat = {}
+        for name, t, tail in (("actions", c.actions, (policy.n_out,)), ("log_prob", c.log_prob, ()), ("advantages", c.advantages, ()),
+                              ("returns", c.returns, ())):
+            if t is None:
+                flat[name] = None
+                continue
+            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (K, N) + tail:
+                raise ValueError(f"collected.{name} must be a contiguous float32 {(K, N) + tail} tensor on {self.device}")
+            flat[name] = t.view((M,) + tail)
+        stream = torch.cuda.current_stream().cuda_stream
+        opt.load()
+        stats = torch.zeros((n_epochs, n_mb, 10), device=self.device, dtype=torch.float32)
+        for e in range(n_epochs):
+            perm = torch.randperm(M, device=self.device, generator=generator)
+            for j, idx in enumerate(perm.split(batch_size)):
+                B = int(idx.numel())
+                mean = self.mlp_forward(policy, rows, idx)
+                v = self.mlp_forward(value, rows, idx).view(-1) if value is not None else None
+                grad_mean = torch.empty((B, policy.n_out), device=self.device, dtype=torch.float32)
+                grad_v = torch.empty((B,), device=self.device, dtype=torch.float32) if v is not None else None
+                st = stats[e, j]
+                self.batch.ppo_head_device(policy, B, mean.data_ptr(), 0 if v is None else v.data_ptr(), flat["actions"].data_ptr(),
+                                           flat["log_prob"].data_ptr(), flat["advantages"].data_ptr(),
+                                           0 if v is None else flat["returns"].data_ptr(), grad_mean.data_ptr(),
+                                           0 if v is None else grad_v.data_ptr(), opt.grad_log_std.data_ptr(), st.data_ptr(),
+                                           clip_range, vf_coef, ent_coef, normalize_advantage=normalize_advantage,
+                                           index_ptr=idx.data_ptr(), stream=stream)
+                self.mlp_backward(policy, rows, grad_mean, idx, out=opt.actor_grads)
+                if value is not None:
+                    self.mlp_backward(value, rows, grad_v.view(-1, 1), idx, out=opt.critic_grads)
+                opt.step(lr, stats=st[8:])
+        return stats
+
     @property
     def terminal_observation(self):
         return self._terminal
@@ -361,6 +439,81 @@ class TorchDocking3d:
         self.batch.close()
         if err is not None:
             raise err
+
+
+class DeviceAdam:
+    """What ``TorchDocking3d.make_optimizer`` returns: the device optimiser (dockauv_optim) of one actor, its log_std and
+    (optionally) one critic, over the caller's own tensors.  ``actor_params`` / ``log_std`` / ``critic_params``: the caller's
+    tensors (updated in place by ``step``); ``actor_grads`` / ``grad_log_std`` / ``critic_grads``: gradient buffers of the same
+    shapes the optimiser owns, ``grads`` all of them in the optimiser's order (actor, log_std, critic), ``params`` likewise."""
+
+    def __init__(self, env, policy, value, actor_params, log_std, critic_params, betas, eps, max_grad_norm):
+        torch = env.torch
+        if (value is None) != (critic_params is None):
+            raise ValueError("value and critic_params: both or neither (None: actor only)")
+        if log_std is None:
+            raise ValueError("the optimiser needs the actor's log_std tensor")
+
+        def checked(pol, tensors, what):
+            ts = [t.detach() for t in tensors]
+            widths = [pol.n_in] + pol.n_hidden + [pol.n_out]
+            shapes = [s for i in range(len(widths) - 1) for s in ((widths[i + 1], widths[i]), (widths[i + 1],))]
+            if len(ts) != len(shapes) or any(t.device != env.device or t.dtype != torch.float32 or not t.is_contiguous()
+                                             or tuple(t.shape) != s for t, s in zip(ts, shapes)):
+                raise ValueError(f"{what} must be contiguous float32 tensors of shapes {shapes} on {env.device}")
+            return ts
+
+        self.env, self.policy, self.value = env, policy, value
+        self.actor_params = checked(policy, actor_params, "actor_params")
+        self.critic_params = checked(value, critic_params, "critic_params") if value is not None else None
+        self.log_std = log_std.detach()
+        if self.log_std.device != env.device or self.log_std.dtype != torch.float32 or not self.log_std.is_contiguous() \
+                or tuple(self.log_std.shape) != (policy.n_out,):
+            raise ValueError(f"log_std must be a contiguous float32 [{policy.n_out}] tensor on {env.device}")
+        self.actor_grads = [torch.zeros_like(t) for t in self.actor_params]
+        self.grad_log_std = torch.zeros_like(self.log_std)
+        self.critic_grads = [torch.zeros_like(t) for t in self.critic_params] if value is not None else None
+        self.params = self.actor_params + [self.log_std] + (self.critic_params or [])
+        self.grads = self.actor_grads + [self.grad_log_std] + (self.critic_grads or [])
+        self.load()      # (the actor gets its log_std from this tensor before the optimiser is created)
+        self.handle = env.batch.make_optim(policy, value, betas=betas, eps=eps, max_grad_norm=max_grad_norm)
+
+    @staticmethod
+    def _six(tensors):
+        ptrs = [t.data_ptr() for t in tensors]
+        if len(ptrs) == 4:
+            ptrs[2:2] = [0, 0]
+        return ptrs
+
+    def load(self) -> None:
+        """``load_policy`` of both networks from the optimiser's tensors, on the current stream"""
+        self.env.load_policy(self.policy, self.actor_params, log_std=self.log_std)
+        if self.value is not None:
+            self.env.load_policy(self.value, self.critic_params)
+
+    def step(self, lr: float, stats=None) -> None:
+        """One step on ``grads`` (dockauv_optim_step on the current stream): clip by the global norm, Adam, repack of both
+        networks.  ``stats``: None or a contiguous float32 [2] tensor on the device for (norm before clipping, coef).  Does
+        not synchronise."""
+        torch = self.env.torch
+        if stats is not None and (stats.device != self.env.device or stats.dtype != torch.float32 or not stats.is_contiguous()
+                                  or tuple(stats.shape) != (2,)):
+            raise ValueError(f"stats must be a contiguous float32 [2] tensor on {self.env.device}")
+        self.env.batch.optim_step_device(self.handle, lr, self._six(self.actor_params), self.log_std.data_ptr(),
+                                         self._six(self.actor_grads), self.grad_log_std.data_ptr(),
+                                         None if self.value is None else self._six(self.critic_params),
+                                         None if self.value is None else self._six(self.critic_grads),
+                                         stats_ptr=0 if stats is None else stats.data_ptr(),
+                                         stream=torch.cuda.current_stream().cuda_stream)
+
+    def state(self):
+        """(m, v, steps): copies of the two moments as flat float32 device tensors in the order of ``params``, and the number
+        of steps taken (dockauv_optim_state)"""
+        torch = self.env.torch
+        m_ptr, v_ptr, n, t = self.env.batch.optim_state(self.handle)
+        from ..parallel import _DevArray
+        m, v = (torch.as_tensor(_DevArray(ptr, (n,), "<f4"), device=self.env.device).clone() for ptr in (m_ptr, v_ptr))
+        return m, v, t
 
 
 class ShardedTorchDocking3d:

@@ -6,7 +6,8 @@ is SB3's ``MlpPolicy``, which train.py:64 instantiates and train.py:64-71 / 86-1
 ``MLPPolicy`` is a plain host object that holds the arrays; ``BatchedDocking3d.make_policy`` / ``TorchDocking3d.make_policy``
 put it on the device.  An ``MLPPolicy`` with one raw output is a critic (SB3's ``mlp_extractor.value_net`` + ``value_net``;
 ``value_from_torch``, ``make_value``): the PPO collector (dockauv_collect) evaluates it on the rollout's rows.
-``forward_reference``, ``backward_reference``, ``normals_reference``, ``log_prob_reference`` and ``gae_reference`` are float64
+``forward_reference``, ``backward_reference``, ``normals_reference``, ``log_prob_reference``, ``gae_reference``,
+``ppo_head_reference`` and ``adam_reference`` are float64
 NumPy statements of what the kernels compute (for tests and for callers who want to check a port); they are never used as a compute path.
 """
 from __future__ import annotations
@@ -206,6 +207,34 @@ class MLPPolicy:
                           (np.abs(ratio - 1.0) > clip).mean(), m, s], dtype=np.float64)
         return grad_mean, grad_v, grad_log_std, stats
 
+    @staticmethod
+    def adam_reference(params, grads, m, v, t: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-5, max_grad_norm: float = 0.5):
+        """float64 statement of dockauv_optim_step on sequences of arrays of matching shapes: the norm over ALL gradients,
+        coef = min(1, max_grad_norm / (norm + 1e-6)) (1 with max_grad_norm <= 0: torch's clip_grad_norm_), then step ``t`` >= 1
+        of torch.optim.Adam without weight decay or amsgrad on the scaled gradients.  Returns (params, m, v, norm, coef): three
+        lists of new float64 arrays and two floats; nothing is changed in place."""
+        f = lambda xs: [np.asarray(x, dtype=np.float64) for x in xs]
+        params, grads, m, v = f(params), f(grads), f(m), f(v)
+        if not (len(params) == len(grads) == len(m) == len(v)) or any(not (p.shape == g.shape == a.shape == b.shape)
+                                                                      for p, g, a, b in zip(params, grads, m, v)):
+            raise ValueError("params, grads, m, v: sequences of arrays of matching shapes")
+        if int(t) < 1:
+            raise ValueError("t counts the steps from 1")
+        b1, b2 = float(betas[0]), float(betas[1])
+        norm = float(np.sqrt(sum(float((g * g).sum()) for g in grads)))
+        coef = min(1.0, float(max_grad_norm) / (norm + 1e-6)) if max_grad_norm > 0 else 1.0
+        step_size = float(lr) / (1.0 - b1 ** int(t))
+        rsq = 1.0 / np.sqrt(1.0 - b2 ** int(t))
+        new_p, new_m, new_v = [], [], []
+        for p, g, a, b in zip(params, grads, m, v):
+            g = g * coef
+            a = a + (1.0 - b1) * (g - a)
+            b = b2 * b + (1.0 - b2) * g * g
+            new_p.append(p - step_size * (a / (np.sqrt(b) * rsq + float(eps))))
+            new_m.append(a)
+            new_v.append(b)
+        return new_p, new_m, new_v, norm, coef
+
     def forward_reference(self, obs: np.ndarray, z: Optional[np.ndarray] = None) -> np.ndarray:
         """float64 forward of float32 weights: obs [..., n_in] -> [..., n_out]; ``z`` [..., n_out]: exploration normals,
         added as exp(log_std) * z before the output activation."""
@@ -294,3 +323,11 @@ class DevicePolicy:
         self.shape = mlp.shape_desc()
         self.n_in, self.n_hidden, self.n_out = mlp.n_in, mlp.n_hidden, mlp.n_out
         self.has_log_std = mlp.log_std is not None and not self.value_role
+
+
+class DeviceOptim:
+    """A dockauv_optim of one BatchedDocking3d handle (made by ``make_optim``): Adam's moments and step count for one actor,
+    its log_std and (optionally) one critic."""
+
+    def __init__(self, ptr: C.c_void_p, policy: DevicePolicy, value: Optional[DevicePolicy]):
+        self.ptr, self.policy, self.value = ptr, policy, value

@@ -345,8 +345,9 @@ int dockauv_step_gather_sequence(dockauv_handle h, const dockauv_step_io* ios, i
  * update, the library computes the network's share -- the MLP's output on any minibatch of those rows and the gradients of
  * all weights and biases for gradients on that output (dockauv_policy_forward_rows, dockauv_policy_backward, at the end of this
  * header) -- and the PPO head between the two: advantage normalisation, log-probability, ratio and clipping, value loss,
- * entropy, the gradients on both networks' outputs and on log_std, and the statistics SB3 logs (dockauv_ppo_head, the last
- * entry of this header).  Gradient-norm clipping and the optimiser step stay with the learner.
+ * entropy, the gradients on both networks' outputs and on log_std, and the statistics SB3 logs (dockauv_ppo_head) -- and the
+ * tail of the step: gradient-norm clipping and Adam over all parameters in one launch, then the repack of both networks
+ * (dockauv_optim_step, the last entry of this header).
  */
 #define DOCKAUV_ACT_NONE 0       /* output: raw (PPO; the step kernel clips, objects/auvsim.py:74) */
 #define DOCKAUV_ACT_TANH 1       /* hidden: SB3's default; output: SAC-style squashing */
@@ -550,6 +551,79 @@ typedef struct dockauv_ppo_head_io {
     float* stats;                  /* [8]: loss, policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction, adv mean, adv std */
 } dockauv_ppo_head_io;
 int dockauv_ppo_head(dockauv_handle h, dockauv_policy actor, const dockauv_ppo_head_io* io, void* hip_stream);
+
+/*
+ * The optimiser: the tail of a PPO minibatch step (SB3's PPO.train, train.py:64-71: clip_grad_norm_ and Adam.step, SB3's
+ * Adam with eps 1e-5), in one launch over all parameters, followed by the repack of both networks -- so that a learner on the C
+ * ABI needs neither torch nor a dockauv_policy_load between minibatches.  All pointers are device pointers, float32; the step is
+ * asynchronous on the stream and does not synchronise.
+ *
+ * A dockauv_optim belongs to one actor (with a log_std) and, optionally, one critic of the same handle.  It owns the first and
+ * second moments m and v (zero at create) and the step count t (0 at create); everything is allocated at create, a step
+ * allocates nothing.  Destroy it before its policies.
+ *
+ * One step covers one index space: actor W1 b1 W2 b2 W3 b3, log_std, critic W1 b1 W2 b2 W3 b3 (torch.nn.Linear layout, the
+ * shapes of the policies; W2 / b2 are empty with one hidden layer, the critic's arrays without a critic).
+ * The gradient norm: sum = the float64 sum of (double)g * (double)g over the whole index space -- lane t of a group of 1 024
+ * takes the elements t, t + 1 024, .. of each array in turn, the lanes of a wave are added by a fixed tree, the sixteen waves in
+ * order --, then
+ *   norm = (float)sqrt(sum)
+ *   coef = max_grad_norm > 0 ? fminf(1.0f, max_grad_norm / (norm + 1e-6f)) : 1.0f          (torch's clip_grad_norm_)
+ * Every group of the launch forms the whole sum itself, in that order, so every element is scaled by the same coef bit for bit
+ * and no pass between groups is needed.  The host supplies, computed in double from the step count t >= 1 (incremented by the
+ * call before use) and rounded once:
+ *   c1 = (float)(1 - beta1);  c2 = (float)(1 - beta2);  b2 = (float)beta2
+ *   step_size = (float)(lr / (1 - beta1^t));  rsq = (float)(1 / sqrt(1 - beta2^t))
+ * and per element, in exactly this float32 order (the library is built with -ffp-contract=on: only the fmaf written here are
+ * fused):
+ *   g     = grad * coef
+ *   m     = fmaf(c1, g - m, m)
+ *   v     = fmaf(c2 * g, g, b2 * v)
+ *   denom = fmaf(sqrtf(v), rsq, eps)
+ *   p     = p - step_size * (m / denom)
+ * p, m and v are written in place, the gradients are only read.  No weight decay, no amsgrad (torch.optim.Adam's defaults).
+ * stats (nullable [2]): the norm before clipping, coef.
+ * Reproducible: no floating-point atomics; the bits depend on the gradients, the state and the shapes only.
+ *
+ * After the update dockauv_optim_step repacks both networks from the updated arrays (what dockauv_policy_load with
+ * pointers_on_device = 1 does, log_std included): at that point of the stream the actor and the critic hold the new weights,
+ * and the next dockauv_collect / dockauv_policy_forward_rows needs no dockauv_policy_load.  Launches: the step, then per network
+ * the pack (the actor's with the copy of its log_std).
+ * Stream capture: the bias corrections are host scalars of the call, so a captured graph would replay ONE step's corrections (and
+ * the count would not advance): do not capture the step.
+ * Refused before any device call (DOCKAUV_E_INVALID, the message naming the field): a NULL handle, optimiser, desc or io; a wrong
+ * struct_size; a critic as `actor` or an actor as `critic`; policies of another handle; an actor without log_std; beta1 or beta2
+ * outside [0, 1); eps <= 0; lr < 0 or not finite; a NULL among the pointers the shapes require; a non-NULL pointer where the
+ * shapes have none; a grads pointer equal to its params pointer.
+ */
+typedef struct dockauv_optim_s* dockauv_optim;
+typedef struct dockauv_optim_desc {
+    uint32_t struct_size;          /* sizeof(dockauv_optim_desc): ABI check */
+    uint32_t reserved;
+    double beta1, beta2;           /* in [0, 1) */
+    double eps;                    /* > 0 (SB3's PPO: 1e-5) */
+    float max_grad_norm;           /* <= 0: no clipping */
+    float reserved1;
+} dockauv_optim_desc;
+int dockauv_optim_create(dockauv_handle h, dockauv_policy actor, dockauv_policy critic /* nullable */,
+                         const dockauv_optim_desc* d, dockauv_optim* out);
+int dockauv_optim_destroy(dockauv_optim o);   /* NULL: 0 */
+typedef struct dockauv_optim_io {
+    uint32_t struct_size;          /* sizeof(dockauv_optim_io): ABI check */
+    uint32_t reserved;
+    double lr;                     /* >= 0, finite; per call (SB3 schedules it) */
+    float* actor_params[6];        /* W1 b1 W2 b2 W3 b3; index 2, 3 NULL with one hidden layer */
+    float* log_std;                /* [n_out] */
+    const float* actor_grads[6];
+    const float* grad_log_std;
+    float* critic_params[6];       /* all NULL without a critic */
+    const float* critic_grads[6];
+    float* stats;                  /* nullable [2]: gradient norm before clipping, coef */
+} dockauv_optim_io;
+int dockauv_optim_step(dockauv_handle h, dockauv_optim o, const dockauv_optim_io* io, void* hip_stream);
+/* The optimiser's state, for inspection and checkpoints: device pointers to m and v ([*n_elements] each, in index-space order,
+ * owned by the optimiser and valid until dockauv_optim_destroy) and the number of steps taken.  Any output may be NULL. */
+int dockauv_optim_state(dockauv_optim o, float** m, float** v, long long* n_elements, long long* steps);
 
 #ifdef __cplusplus
 }
