@@ -346,11 +346,17 @@ int init_handle(dockauv_handle h, const dockauv_config& c, int device) {
     }
     if (h->f64) {
         fill_env(h->a64.P.E, *h);
-        for (int v = 0; v < c.n_vehicles; ++v) fill_vehicle(h->a64.P.V[v], c.vehicle[v]);
+        for (int v = 0; v < c.n_vehicles; ++v) {
+            fill_vehicle(h->a64.P.V[v], c.vehicle[v]);
+            pack_hot(h->a64.P.H[v], h->a64.P.E, h->a64.P.V[v]);
+        }
         h->a64.B = B;
     } else {
         fill_env(h->a32.P.E, *h);
-        for (int v = 0; v < c.n_vehicles; ++v) fill_vehicle(h->a32.P.V[v], c.vehicle[v]);
+        for (int v = 0; v < c.n_vehicles; ++v) {
+            fill_vehicle(h->a32.P.V[v], c.vehicle[v]);
+            pack_hot(h->a32.P.H[v], h->a32.P.E, h->a32.P.V[v]);
+        }
         h->a32.B = B;
     }
     // the parameter block is read by the kernel from device memory (dockauv_device.h: ParamBlock)

@@ -136,15 +136,55 @@ struct TraceDev {
     uint8_t* cond;        // [..]
 };
 
-// Vehicle / reward / fan parameters (~1.7 KB in f32).  They live in a DEVICE buffer that persists across launches
+// The scalars the integrating wave of the structural (SYM) float kernels reads in front of stage 2 of the integrator,
+// packed in order of first use: COPIES of the EnvP / VehicleP values (pack_hot), so that the wave can request them as one
+// batch of wide scalar loads from six adjacent 64-byte lines (dockauv_step.hip.inc: fetch_hot_).
+constexpr int minv_sym(int k) {   // the entries of M^-1 kinetics_ reads (SYM)
+    const int idx[10] = {0, 4, 7, 9, 14, 19, 21, 24, 28, 35};
+    return idx[k];
+}
+template <typename T>
+struct alignas(64) HotP {
+    // input stage: current filter, low-pass, action penalty, input range
+    T lp_alpha, mu, h;
+    T w_act[kMaxU];
+    T ulo[kMaxU], uhalf[kMaxU];
+    // kinetics
+    T bdiag[6];          // B[i][i] (VK_JOY)
+    T dl[6], dq[6];
+    T kc[10];
+    T minv[10];          // Minv[minv_sym(k)]
+    T gWB, gz;
+    T lauv[L_COUNT];     // (VK_LAUV)
+};
+static_assert(sizeof(HotP<float>) % 64 == 0 && sizeof(HotP<double>) % 64 == 0, "whole 64-byte lines");
+
+template <typename T>
+inline void pack_hot(HotP<T>& H, const EnvP<T>& E, const VehicleP<T>& V) {
+    H = HotP<T>{};
+    H.lp_alpha = E.lp_alpha; H.mu = E.mu; H.h = E.h;
+    for (int i = 0; i < kMaxU; ++i) { H.w_act[i] = E.w_act[i]; H.ulo[i] = V.ulo[i]; H.uhalf[i] = V.uhalf[i]; }
+    for (int i = 0; i < 6; ++i) { H.bdiag[i] = V.B[i * kMaxU + i]; H.dl[i] = V.dl[i]; H.dq[i] = V.dq[i]; }
+    for (int i = 0; i < 10; ++i) { H.kc[i] = V.kc[i]; H.minv[i] = V.Minv[minv_sym(i)]; }
+    H.gWB = V.gWB; H.gz = V.gz;
+    for (int i = 0; i < L_COUNT; ++i) H.lauv[i] = V.lauv[i];
+}
+
+// Vehicle / reward / fan parameters (~2.5 KB in f32).  They live in a DEVICE buffer that persists across launches
 // (uploaded once by dockauv_create) and are read through a constant-address-space pointer: wave-uniform scalar loads
 // (s_load -> SGPR operands) that hit in L2 from the second launch on.  Passing them by value in the kernarg segment
 // made every launch re-fetch 27 fresh cache lines from memory, one exposed miss per first touch (measured: a lone
 // wave spent ~45 % of its life in s_waitcnt).
+// Layout: E and V[] hold every parameter once and serve every kernel; H[v] repeats what the integrating wave of vehicle v
+// needs in front of stage 2, line-aligned (HotP).  The rule for reading the block: ONE batch of scalar loads per wave role,
+// requested where the role waits anyway (behind its row loads, in front of a barrier or a hand-over flag) and pinned
+// (pin_sgpr_), never a load that is awaited where its value is used -- each of those is a scalar-cache round trip on the
+// role's own instruction stream.
 template <typename T, int NV>
 struct ParamBlock {
     EnvP<T> E;
     VehicleP<T> V[NV];
+    HotP<T> H[NV];
 };
 
 // copy groups riding in the launch (dockauv_ride.h); plan == nullptr: none

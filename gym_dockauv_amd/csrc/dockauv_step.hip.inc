@@ -481,13 +481,36 @@ __device__ __forceinline__ void rhs_(const VP& V, const T att[3], const T nu[6],
     ad[2] = sq_cr;
     kinetics_<T, VK, SYM>(V, nu, g, tau_c, u, nd);
 }
+// rhs_ with position of stage 1 in a kernel with a hot block: before_kinetics() stands between the kinematics, which need no
+// parameter, and the kinetics (vehicle_step_ pins its second batch there).  Same expressions as rhs_.
+struct NoFetch { __device__ __forceinline__ void operator()() const {} };
+template <typename T, int VK, bool SYM, typename VP, typename PIN>
+__device__ __forceinline__ void rhs_pinned_(const VP& V, const T att[3], const T nu[6], const T nuc[3], const T tau_c[6],
+                                            const T* u, T pd[3], T ad[3], T nd[6], const PIN& before_kinetics) {
+    const Trig<T> g = trig_(att[0], att[1], att[2]);
+    const T vx = nu[0] + nuc[0], vy = nu[1] + nuc[1], vz = nu[2] + nuc[2];
+    rot_body_to_ned_(g, vx, vy, vz, pd);
+    const T inv_ct = rcp_(g.ct);
+    const T sq_cr = (g.sf * nu[4] + g.cf * nu[5]) * inv_ct;
+    ad[0] = nu[3] + sq_cr * g.st;
+    ad[1] = g.cf * nu[4] - g.sf * nu[5];
+    ad[2] = sq_cr;
+    before_kinetics();
+    kinetics_<T, VK, SYM>(V, nu, g, tau_c, u, nd);
+}
 
 // AUVSim.step: un-normalise, low-pass, Fehlberg 4th-order step, wrap.  objects/auvsim.py:77-108,
 // utils/odesolver45.py:18-27 (stage 6 and the 5th-order result are dead in the reference and not computed).
 // psi_lo (float path): low-order word of the heading, see the end of the function
-template <typename T, int VK, bool SYM, int VOFF, typename VP, typename EP>
+// HOTV: V and E are the register copy of the wave's hot block (HotRegs, fetch_hot_input_: the input stage's part is there);
+// all filtered inputs are computed first and stored then (a store between two inputs kept the parameter reads of the next
+// one from moving above it, which nothing needs once they are in registers), and behind the constant part of the control
+// force request_kinetics() asks for the second batch (request_hot_kinetics_), into the registers the input stage has given
+// back; pin_kinetics() awaits it behind the kinematics of stage 1 (some 30 vector instructions), which cover the round trip.
+template <typename T, int VK, bool SYM, int VOFF, bool HOTV = false, typename VP, typename EP, typename REQ = NoFetch, typename PIN = NoFetch>
 __device__ __forceinline__ void vehicle_step_(const VP& V, const EP& E, T y[9], T dpos[3], T u[kMaxU],
-                                              const T act[kMaxU], const T nuc[3], T* g_u, long S, unsigned ul, T& psi_lo) {
+                                              const T act[kMaxU], const T nuc[3], T* g_u, long S, unsigned ul, T& psi_lo,
+                                              const REQ& request_kinetics = REQ(), const PIN& pin_kinetics = PIN()) {
     const int n_u = (VK == VK_LAUV) ? 3 : (VK == VK_JOY ? 6 : V.n_u);
     const T one_m_alpha = T(1) - E.lp_alpha;
 #pragma unroll
@@ -498,8 +521,13 @@ __device__ __forceinline__ void vehicle_step_(const VP& V, const EP& E, T y[9], 
             u[i] = E.lp_alpha * x + one_m_alpha * u[i];
             // the filtered input is final: it goes back to HBM before the stages (a reset at the end of the step
             // overwrites it with zeros), so that for constant-B vehicles only tau_c stays live through them
-            stgx_<VOFF>(g_u, i, S, ul, u[i]);
+            if (!HOTV) stgx_<VOFF>(g_u, i, S, ul, u[i]);
         }
+    }
+    if (HOTV) {
+#pragma unroll
+        for (int i = 0; i < kMaxU; ++i)
+            if (i < n_u) stgx_<VOFF>(g_u, i, S, ul, u[i]);
     }
     T tau_c[6] = {0, 0, 0, 0, 0, 0};
     if (VK == VK_JOY) {
@@ -517,6 +545,7 @@ __device__ __forceinline__ void vehicle_step_(const VP& V, const EP& E, T y[9], 
     } else if (VK == VK_LAUV) {
         lauv_fin_terms_<T>(V, u, tau_c);
     }
+    if (HOTV) request_kinetics();
     // Fehlberg tableau times h: wave-uniform scalars
     const T h = E.h;
     const T a21 = h * T(1.0 / 4.0);
@@ -529,7 +558,8 @@ __device__ __forceinline__ void vehicle_step_(const VP& V, const EP& E, T y[9], 
     // sum as soon as the stage-5 input exists.  y = (att[3], nu[6]).
     T k1[9], k2[9], k3[9], k4[9], pd[3], ys[9];
     DOCKAUV_STAMP_PIN(16, tau_c, 6);   // inputs filtered
-    rhs_<T, VK, SYM, true>(V, y, y + 3, nuc, tau_c, u, pd, k1, k1 + 3);
+    if (HOTV) rhs_pinned_<T, VK, SYM>(V, y, y + 3, nuc, tau_c, u, pd, k1, k1 + 3, pin_kinetics);
+    else rhs_<T, VK, SYM, true>(V, y, y + 3, nuc, tau_c, u, pd, k1, k1 + 3);
     DOCKAUV_STAMP_PIN(17, k1, 9);
 #pragma unroll
     for (int i = 0; i < 3; ++i) dpos[i] = b1 * pd[i];
@@ -871,6 +901,79 @@ __device__ __forceinline__ V pin_sgpr_(V v) {
     return v;
 }
 
+// The integrating wave's hot block in registers (dockauv_device.h: HotP, the rule at ParamBlock): a VehicleP of which only
+// the fields HotP holds are written -- kinetics_ / tau_minus_damping_ / vehicle_step_ read it like the parameter block's, the
+// rest is never read on this path and does not exist after scalar replacement -- and the input-stage scalars of EnvP.
+template <typename T>
+struct HotRegs {
+    VehicleP<T> V;
+    T lp_alpha, mu, h, w_act[kMaxU];
+};
+// The block arrives in TWO batches, because the wave has no SGPRs for all of it at once (61 scalars for the BlueROV2, 66
+// for the LAUV, next to ~60 of addresses; all at once: 13 -> 57 SGPR spills in config 3's kernel): the input stage's part
+// behind the row loads, whose latency covers it, and the kinetics' part behind the input filter, in the registers the
+// first part has just given back, awaited behind the kinematics of stage 1 (pin_hot_kinetics_).  In each, every load
+// comes first (adjacent words: the compiler merges them into s_load_dwordx2 .. x16), then the pins, which keep the batch
+// where it is requested (pin_sgpr_).
+template <typename T, int VK, bool WACT, typename HP>
+__device__ __forceinline__ void fetch_hot_input_(const HP& H, HotRegs<T>& R) {
+    static_assert(VK == VK_JOY || VK == VK_LAUV, "vehicle kinds with a hot block");
+    constexpr int NU = VK == VK_LAUV ? 3 : 6;
+    R.lp_alpha = H.lp_alpha; R.mu = H.mu; R.h = H.h;
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+        if (WACT) R.w_act[i] = H.w_act[i];
+        R.V.ulo[i] = H.ulo[i]; R.V.uhalf[i] = H.uhalf[i];
+    }
+    // what turns the filtered inputs into the constant part of the control force: dead in front of the stages as well
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+        if (VK == VK_JOY) R.V.B[i * kMaxU + i] = H.bdiag[i];
+#pragma unroll
+    for (int i = L_Y_uudr; i < L_COUNT; ++i)
+        if (VK == VK_LAUV) R.V.lauv[i] = H.lauv[i];
+    R.lp_alpha = pin_sgpr_(R.lp_alpha); R.mu = pin_sgpr_(R.mu); R.h = pin_sgpr_(R.h);
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+        if (WACT) R.w_act[i] = pin_sgpr_(R.w_act[i]);
+        R.V.ulo[i] = pin_sgpr_(R.V.ulo[i]); R.V.uhalf[i] = pin_sgpr_(R.V.uhalf[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+        if (VK == VK_JOY) R.V.B[i * kMaxU + i] = pin_sgpr_(R.V.B[i * kMaxU + i]);
+#pragma unroll
+    for (int i = L_Y_uudr; i < L_COUNT; ++i)
+        if (VK == VK_LAUV) R.V.lauv[i] = pin_sgpr_(R.V.lauv[i]);
+}
+template <typename T, int VK, typename HP>
+__device__ __forceinline__ void request_hot_kinetics_(const HP& H, HotRegs<T>& R) {
+    static_assert(VK == VK_JOY || VK == VK_LAUV, "vehicle kinds with a hot block");
+#pragma unroll
+    for (int i = 0; i < 6; ++i) { R.V.dl[i] = H.dl[i]; R.V.dq[i] = H.dq[i]; }
+#pragma unroll
+    for (int i = 0; i < 10; ++i) { R.V.kc[i] = H.kc[i]; R.V.Minv[minv_sym(i)] = H.minv[i]; }
+    R.V.gWB = H.gWB; R.V.gz = H.gz;
+    if (VK == VK_LAUV) {
+#pragma unroll
+        for (int i = 0; i < L_Y_uudr; ++i) R.V.lauv[i] = H.lauv[i];
+    }
+    // (the loads stay in front of this point: nothing may be scheduled across it)
+    __builtin_amdgcn_sched_barrier(0);
+}
+template <typename T, int VK>
+__device__ __forceinline__ void pin_hot_kinetics_(HotRegs<T>& R) {
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) { R.V.dl[i] = pin_sgpr_(R.V.dl[i]); R.V.dq[i] = pin_sgpr_(R.V.dq[i]); }
+#pragma unroll
+    for (int i = 0; i < 10; ++i) { R.V.kc[i] = pin_sgpr_(R.V.kc[i]); R.V.Minv[minv_sym(i)] = pin_sgpr_(R.V.Minv[minv_sym(i)]); }
+    R.V.gWB = pin_sgpr_(R.V.gWB); R.V.gz = pin_sgpr_(R.V.gz);
+    if (VK == VK_LAUV) {
+#pragma unroll
+        for (int i = 0; i < L_Y_uudr; ++i) R.V.lauv[i] = pin_sgpr_(R.V.lauv[i]);
+    }
+}
+
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the wave's global stores
 // (s_waitcnt vmcnt(0)): every hand-over in this kernel goes through LDS, and the state / input write-backs that are
 // in flight at that point have no reader inside the launch.  A single-wave group needs no s_barrier at all: LDS
@@ -975,13 +1078,32 @@ constexpr bool share_nav_() {
     return early_tail_<VK, RAYS, EPG, NT, LOG>();
 }
 
+// Which kernels fetch the integrating wave's parameters in early batches (fetch_hot_input_ / request_hot_kinetics_): float
+// product kernels of the structural fast path, one vehicle kind per kernel.  KIND: 0 = step_kernel, 1 = step_ride_kernel,
+// 2 = step_seq_kernel.  The batches are pinned, so the register allocator can no longer re-load a parameter where it would
+// otherwise spill one; the instantiations in which that raised the SGPR-spill count (the guard rails of DESIGN.md section 3,
+// profiles/hot_params/kernel_usage.txt) keep the loads at the uses:
+//  * mixed batches: the two integrating waves of a group hold the union of both vehicles' registers (12 -> 50 spills);
+//  * the LAUV's ray kernels and its 256-thread sensor-free kernels (50 kinetics scalars live at once: +2 .. +13 spills);
+//  * of the BlueROV2's: the resident ray kernels of 256 threads, the resident sensor-free kernels of 128 / 256 threads, the
+//    riding one-wave ray kernel (+1 .. +2 spills each).
+template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool LOG, bool TERM, bool WB, int KIND>
+constexpr bool hot_params_() {
+    if (sizeof(T) != 4 || !SYM || LOG) return false;
+    if (VK == VK_LAUV) return !RAYS && NT < 256;
+    if (VK != VK_JOY) return false;
+    if (KIND == 1) return !(RAYS && NT == 64);
+    if (KIND == 2) return RAYS ? NT != 256 : NT == 64;
+    return true;
+}
+
 // TERM (product kernels, packed rows): the terminal observation of the envs that finish in this step is delivered as well
 // (dockauv_step_io::terminal_obs; SB3's infos[i]["terminal_observation"], train.py:64-71 via DummyVecEnv) -- an
 // instantiation of its own, so that the plain product kernels carry none of it: the tail roles write the TRUE observation
 // of every env into the tile, and behind the tile's last barrier one wave copies the rows of the finished envs to
 // terminal_obs and zeroes them (the reference's reset observation, Q8) before the tile is streamed out.
 // WB: plain write-back stores (instantiations that serve launches of several rounds of groups only, see store_global_)
-template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool LOG = false, bool TERM = false, bool WB = false>
+template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool LOG = false, bool TERM = false, bool WB = false, int KIND = 0>
 __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix = threadIdx.x, const unsigned bix = blockIdx.x) {
     DOCKAUV_SPAN(0);   // (diagnostic build: the group's very first instructions)
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -1151,6 +1273,11 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
     T u[kMaxU], act[kMaxU];
     T cdx = T(0), cdy = T(0), cdz = T(0), vmin = T(0), vmax = T(0), w_noise = T(0);
     int vid_l = 0;
+    constexpr bool HOT = hot_params_<T, VK, SYM, RAYS, EPG, NT, LOG, TERM, WB, KIND>();
+    // (ray kernels: the action weights stay with EnvP, one round trip of their own -- six more SGPRs across the row loads
+    // cost config 3's kernel four more spills)
+    constexpr bool HOT_WACT = !RAYS;
+    HotRegs<T> HR;   // (HOT: the integrating wave's parameters, see fetch_hot_input_)
     // episode-storage trace of selected envs (include/dockauv.h: dockauv_trace_*) and its row in the ring for this step
     typedef const __attribute__((address_space(1))) TraceDev GTrace;
     GTrace* const TR = LOG ? (GTrace*)(uintptr_t)IO.trace : nullptr;
@@ -1202,18 +1329,30 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
         }
         if (TR) trace_slot = TR->slot_of_env[env0 + (int)ul];
         DOCKAUV_STAMP(1);   // loads issued
+        // the integrating wave's input-stage parameters: one batch behind the row loads, whose latency (800-1 900 ticks)
+        // covers it
+        if constexpr (HOT) fetch_hot_input_<T, VK, HOT_WACT>(PB->H[0], HR);
     }
-    // The parameter block is read with scalar loads wherever a value is needed; the first touch of each 64-byte line
-    // in a launch goes to L2 (~200 cycles on gfx950, scripts/micro/issue_rate.hip; 56 from the scalar cache, which the
-    // waves of a CU share), and a lone wave pays each of them in full -- eight in the env phase alone.  The group's
-    // last wave (idle until the hand-over) requests one word of every line at once; by the time the integrating wave's
-    // state loads have landed the lines sit in the scalar cache.
+    // The first touch of a 64-byte line of the parameter block in a launch goes to L2 (~200 cycles on gfx950,
+    // scripts/micro/issue_rate.hip; 56 from the scalar cache, which the waves of a CU share), and a lone wave pays each of
+    // them in full.  The group's last wave (idle until the hand-over) requests one word of every line the launch reads at
+    // once -- with a hot block: its lines first, then EnvP's for the batches of the other roles; nobody reads VehicleP then
+    // -- so that they sit in the scalar cache when a role's batch asks for them.
     if (wv == W - 1) {
         typedef const __attribute__((address_space(4))) unsigned CW;
         CW* const pw = (CW*)(uintptr_t)A.params;
         unsigned param_touch = 0;
+        typedef ParamBlock<T, 2> PBlock;
+        if (HOT) {
+            constexpr int h0 = (int)(__builtin_offsetof(PBlock, H) / 4), hw = (int)(sizeof(HotP<T>) / 4);
 #pragma unroll
-        for (int off = 0; off < (int)(sizeof(ParamBlock<T, 2>) / 4); off += 16) param_touch ^= pw[off];
+            for (int off = h0; off < h0 + hw; off += 16) param_touch ^= pw[off];
+#pragma unroll
+            for (int off = 0; off < (int)(sizeof(EnvP<T>) / 4); off += 16) param_touch ^= pw[off];
+        } else {
+#pragma unroll
+            for (int off = 0; off < (int)(__builtin_offsetof(PBlock, H) / 4); off += 16) param_touch ^= pw[off];
+        }
         asm volatile("" ::"s"(param_touch));
     }
     // (after wave 0's loads in program order: wave 0 is the critical path)
@@ -1345,7 +1484,7 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
         // ---------------- 1. Current.sim (objects/current.py:78-96) ----------------
         if (LOG && IO.device_noise && __any(sigma_l != T(0)))
             w_noise = sigma_l * device_normal_<T>(E.seed, env0 + (int)ul, episode_l, t_steps);
-        Vc += (-E.mu * Vc + w_noise) * E.h;
+        if constexpr (HOT) Vc += (-HR.mu * Vc + w_noise) * HR.h; else Vc += (-E.mu * Vc + w_noise) * E.h;
         Vc = clip_(Vc, vmin, vmax);
         // ---------------- 2. nu_c = R(Theta_pre)^T v_c^n (objects/current.py:33-53) ----------------
         nuc[0] = nuc[1] = nuc[2] = T(0);
@@ -1371,11 +1510,15 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
             for (int k = 0; k < kMaxU; ++k) {
                 if (k < n_u_env) {
                     const T a = abs_(act[k]) * inv_nu;   // raw, un-clipped action
-                    act_pen += a * a * E.w_act[k];
+                    if constexpr (HOT && HOT_WACT) act_pen += a * a * HR.w_act[k]; else act_pen += a * a * E.w_act[k];
                 }
             }
         }
-        if (VK == VK_MIXED) {
+        if constexpr (HOT) {
+            vehicle_step_<T, VK, SYM, VOFF, true>(HR.V, HR, st + 3, dpos, u, act, nuc, g_u, S, ul, psi_lo,
+                                                  [&]() { request_hot_kinetics_<T, VK>(PB->H[0], HR); },
+                                                  [&]() { pin_hot_kinetics_<T, VK>(HR); });
+        } else if (VK == VK_MIXED) {
             if (vid == 0) {
                 vehicle_step_<T, VK_JOY, SYM, VOFF>(PB->V[0], E, st + 3, dpos, u, act, nuc, g_u, S, ul, psi_lo);
             } else {
@@ -2627,7 +2770,7 @@ __global__ __launch_bounds__(NT, (min_waves_<T, NT>())) void step_ride_kernel(co
         ride_body<NT>(R, blockIdx.x - groups, gridDim.x - groups, reinterpret_cast<uint32_t*>(smem_raw));
         return;
     }
-    step_body<T, VK, SYM, RAYS, EPG, NT>(A);
+    step_body<T, VK, SYM, RAYS, EPG, NT, false, false, false, 1>(A);
 }
 
 // The RESIDENT step sequence (round 4; dockauv_step_sequence's fast path for open-loop action sequences: the scripted /
@@ -2664,7 +2807,7 @@ __global__ __launch_bounds__(NT, (min_waves_<T, NT>())) void step_seq_kernel(con
         for (unsigned i = 0; i < sizeof(DevArgs) / 8; ++i) Ak.w[i] = src[i];
         Ak.a.io.actions = ka->Q.actions[k];
         Ak.a.io.obs = ka->Q.obs[k];
-        step_body<T, VK, SYM, RAYS, EPG, NT, false, false, WB>(Ak.a, tix, bix);
+        step_body<T, VK, SYM, RAYS, EPG, NT, false, false, WB, 2>(Ak.a, tix, bix);
         if (k + 1 < n) {
             // What orders step k + 1 behind step k is the group itself (memory model: workgroup scope; all its waves share one
             // CU and one vector L1): every wave's stores have been performed, the group meets, and the L1 -- only the L1:
