@@ -155,6 +155,14 @@ class OptimIO(C.Structure):
     ]
 
 
+class MonitorIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_steps", C.c_int32),
+        ("rows_out", C.c_void_p), ("terminal_obs", C.c_void_p), ("values", C.c_void_p), ("returns", C.c_void_p),
+        ("ep_return", C.c_void_p), ("ep_length", C.c_void_p), ("ep_outcome", C.c_void_p), ("stats", C.c_void_p),
+    ]
+
+
 # every symbol include/dockauv.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("dockauv_abi_version", C.c_int, []),
@@ -212,6 +220,11 @@ SYMBOLS = [
     ("dockauv_optim_step", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(OptimIO), C.c_void_p]),
     ("dockauv_optim_state", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong),
                                       C.POINTER(C.c_longlong)]),
+    ("dockauv_monitor_create", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("dockauv_monitor_destroy", C.c_int, [C.c_void_p]),
+    ("dockauv_monitor_sync", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("dockauv_monitor_scan", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MonitorIO), C.c_void_p]),
+    ("dockauv_monitor_carry", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
 ]
 
 _lib: Optional[C.CDLL] = None

@@ -1,6 +1,6 @@
 // dockauv_capi_policy.hip -- C ABI of libdockauv.so (include/dockauv.h), second part: MLP policy and critic, closed-loop
-// rollout, PPO collector, backward, head and optimiser.  The kernels are in dockauv_policy / _collect / _backward / _head /
-// _optim.hip.
+// rollout, PPO collector, backward, head, optimiser and episode monitor.  The kernels are in dockauv_policy / _collect /
+// _backward / _head / _optim / _monitor.hip.
 #include <cmath>
 #include <cstring>
 
@@ -32,7 +32,24 @@ struct dockauv_optim_s {
     float *m = nullptr, *v = nullptr;   // [total] each, one allocation (m first)
 };
 
+struct dockauv_monitor_s {
+    dockauv_handle h = nullptr;
+    float* carry_ret = nullptr;   // [n_envs]: the running return of every env's episode
+    int32_t* carry_len = nullptr; // [n_envs]: its length so far
+    double* ws = nullptr;         // monitor_workspace_doubles(n_envs): the scan's partials, then the explained variance's
+};
+
 namespace {
+
+// the carries <- the handle's own cumulative reward / step counters (float32 handle), ordered on `stream`
+int monitor_sync(dockauv_monitor m, hipStream_t stream) {
+    dockauv_handle h = m->h;
+    const size_t N = (size_t)h->cfg.n_envs;
+    HIP_TRY(h, hipMemcpyAsync(m->carry_ret, h->B.cum_reward, N * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(h, hipMemcpyAsync(m->carry_len, h->B.t_steps, N * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+    h->last_stream = stream;
+    return 0;
+}
 
 // the descriptor's own fields; `like` != nullptr: a reload, shapes and activations must be those of the policy
 int validate_policy_desc(dockauv_handle h, const dockauv_policy_desc* d, const PolicyShape* like) {
@@ -571,6 +588,104 @@ int dockauv_optim_step(dockauv_handle h, dockauv_optim o, const dockauv_optim_io
     if (int rc2 = repack_policy(o->actor, io->actor_params, io->log_std, stream)) return rc2;
     if (o->critic)
         if (int rc2 = repack_policy(o->critic, io->critic_params, nullptr, stream)) return rc2;
+    return 0;
+}
+
+int dockauv_monitor_create(dockauv_handle h, dockauv_monitor* out) {
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_monitor_create: null handle");
+    if (!out) return fail(h, DOCKAUV_E_INVALID, "dockauv_monitor_create: out is NULL");
+    *out = nullptr;
+    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "dockauv_monitor_create: the packed rows are float32; the handle's precision is DOCKAUV_F64");
+    if (h->cfg.reset_mode == DOCKAUV_RESET_NONE)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_monitor_create: the handle's reset_mode is DOCKAUV_RESET_NONE: an episode does not "
+                    "restart at the row after a done");
+    HIP_TRY(h, hipSetDevice(h->device));
+    dockauv_monitor m = new dockauv_monitor_s();
+    m->h = h;
+    const size_t N = (size_t)h->cfg.n_envs;
+    hipError_t e = hipMalloc((void**)&m->carry_ret, N * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&m->carry_len, N * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&m->ws, monitor_workspace_doubles(h->cfg.n_envs) * sizeof(double));
+    if (e != hipSuccess) {
+        dockauv_monitor_destroy(m);
+        return fail(h, DOCKAUV_E_HIP, "monitor buffers: %s", hipGetErrorString(e));
+    }
+    if (int rc = sync_last(h)) {   // (what the handle has queued comes first: the copies below run on the default stream)
+        dockauv_monitor_destroy(m);
+        return rc;
+    }
+    if (int rc = monitor_sync(m, nullptr)) {
+        dockauv_monitor_destroy(m);
+        return rc;
+    }
+    *out = m;
+    return 0;
+}
+
+int dockauv_monitor_destroy(dockauv_monitor m) {
+    if (!m) return 0;
+    if (m->h) (void)hipSetDevice(m->h->device);
+    (void)hipDeviceSynchronize();
+    if (m->carry_ret) (void)hipFree(m->carry_ret);
+    if (m->carry_len) (void)hipFree(m->carry_len);
+    if (m->ws) (void)hipFree(m->ws);
+    delete m;
+    return 0;
+}
+
+int dockauv_monitor_sync(dockauv_monitor m, void* hip_stream) {
+    if (!m) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_monitor_sync: null monitor");
+    HIP_TRY(m->h, hipSetDevice(m->h->device));
+    return monitor_sync(m, (hipStream_t)hip_stream);
+}
+
+int dockauv_monitor_carry(dockauv_monitor m, float** carry_return, int32_t** carry_length) {
+    if (!m) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_monitor_carry: null monitor");
+    if (carry_return) *carry_return = m->carry_ret;
+    if (carry_length) *carry_length = m->carry_len;
+    return 0;
+}
+
+int dockauv_monitor_scan(dockauv_handle h, dockauv_monitor m, const dockauv_monitor_io* io, void* hip_stream) {
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_monitor_scan: null handle");
+    if (!m) return fail(h, DOCKAUV_E_INVALID, "dockauv_monitor_scan: null monitor");
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "dockauv_monitor_scan: io is NULL");
+    if (io->struct_size != sizeof(dockauv_monitor_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_monitor_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_monitor_io));
+    if (io->n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_monitor_io.n_steps: %d must be >= 1", io->n_steps);
+    if (!io->rows_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_monitor_io.rows_out is NULL");
+    if (!io->stats) return fail(h, DOCKAUV_E_INVALID, "dockauv_monitor_io.stats is NULL");
+    if (io->ep_outcome && !io->terminal_obs)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_monitor_io.ep_outcome needs terminal_obs (the outcome is read off the terminal observation)");
+    if ((io->values == nullptr) != (io->returns == nullptr))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_monitor_io.values / returns: both or neither must be NULL (NULL: no explained variance)");
+    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "dockauv_monitor_scan: the packed rows are float32; the handle's precision is DOCKAUV_F64");
+    if (h->cfg.reset_mode == DOCKAUV_RESET_NONE)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_monitor_scan: the handle's reset_mode is DOCKAUV_RESET_NONE: an episode does not "
+                    "restart at the row after a done");
+    if (m->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_monitor_scan: the monitor was created for another handle");
+    HIP_TRY(h, hipSetDevice(h->device));
+    MonitorArgs a{};
+    a.rows = io->rows_out;
+    a.terminal_obs = io->terminal_obs;
+    a.values = io->values;
+    a.returns = io->returns;
+    a.carry_ret = m->carry_ret;
+    a.carry_len = m->carry_len;
+    a.ep_return = io->ep_return;
+    a.ep_length = io->ep_length;
+    a.ep_outcome = io->ep_outcome;
+    a.partial = m->ws;
+    a.ev_partial = m->ws + (size_t)kMonWords * (size_t)monitor_groups(h->cfg.n_envs);
+    a.stats = io->stats;
+    a.n_steps = io->n_steps;
+    a.n_envs = h->cfg.n_envs;
+    a.n_obs = h->n_obs;
+    a.row_stride = h->n_obs + 2;
+    a.max_timesteps = h->cfg.max_timesteps;
+    const int rc = launch_monitor_scan(a, hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "monitor launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
     return 0;
 }
 

@@ -583,6 +583,33 @@ struct AdamArgs {
 // Returns a hipError_t as int.
 int launch_adam_step(const AdamArgs& a, void* stream);
 
+// ------------------------------------------------------------------------------------------ episode monitor (dockauv_monitor.hip)
+// Returns, lengths and outcomes of the episodes that end inside the packed rows of a collection, and the explained variance of
+// its values (include/dockauv.h: dockauv_monitor_scan states the arithmetic).  The scan runs one lane per env in groups of
+// kMonThreads and leaves kMonWords float64 words a group in `partial` ([kMonWords][monitor_groups(n_envs)]); the explained
+// variance takes two passes on at most kEvMaxGroups groups with `ev_partial` ([4][kEvMaxGroups]: sums of pass one, squared sums of
+// pass two); a final launch of one group adds both in a fixed order and writes stats [16].
+constexpr int kMonThreads = 64;           // one wave per group, as the GAE kernel: 65 536 envs are 1 024 groups
+constexpr int kMonWords = 13;
+constexpr int kEvMaxGroups = 256;
+inline int monitor_groups(int n_envs) { return (n_envs + kMonThreads - 1) / kMonThreads; }
+inline size_t monitor_workspace_doubles(int n_envs) { return (size_t)kMonWords * (size_t)monitor_groups(n_envs) + 4 * (size_t)kEvMaxGroups; }
+struct MonitorArgs {
+    const float* rows;                    // [K][N][row_stride]; only the reward and done columns are read
+    const float* terminal_obs;            // nullable [K][N][n_obs]; columns 0, 6, 7 are read where done
+    const float *values, *returns;        // nullable, both or neither: [K + 1][N] (the first K N are read), [K][N]
+    float* carry_ret;                     // [N], read and written back
+    int32_t* carry_len;                   // [N]
+    float* ep_return;                     // nullable [K][N], written where done
+    int32_t* ep_length;                   // nullable [K][N]
+    uint8_t* ep_outcome;                  // nullable [K][N]; null without terminal_obs
+    double *partial, *ev_partial;         // the workspace: monitor_workspace_doubles, ev_partial behind partial
+    double* stats;                        // [16]
+    int n_steps, n_envs, n_obs, row_stride, max_timesteps;
+};
+// Two launches on stream (scan, final sums), four with values / returns.  Returns a hipError_t as int.
+int launch_monitor_scan(const MonitorArgs& a, void* stream);
+
 #ifdef DOCKAUV_STAMPS
 int read_stamps(unsigned long long* out);   // diagnostic build only
 int read_span(unsigned long long* out, int groups);

@@ -802,6 +802,54 @@ class BatchedDocking3d:
         _capi.check(self._lib, self._handle, rc, "dockauv_optim_state")
         return int(m.value or 0), int(v.value or 0), int(n.value), int(t.value)
 
+    # ------------------------------------------------------------------------------------------ episode monitor
+    def make_monitor(self):
+        """An episode monitor of this handle (dockauv_monitor_create): per-env running returns and lengths, started from the
+        handle's own cumulative rewards and step counters, and the reduction workspace.  Needs a float32 handle with an
+        auto-reset mode.  ``close`` destroys it before the handle."""
+        from ..monitor import DeviceMonitor
+        ptr = C.c_void_p()
+        rc = self._lib.dockauv_monitor_create(self._handle, C.byref(ptr))
+        _capi.check(self._lib, self._handle, rc, "dockauv_monitor_create")
+        mon = DeviceMonitor(ptr)
+        self._monitors = getattr(self, "_monitors", []) + [mon]
+        return mon
+
+    def monitor_sync(self, monitor, stream: int = 0) -> None:
+        """The monitor's carries <- the handle's cumulative rewards / step counters at this point of ``stream``
+        (dockauv_monitor_sync): after steps the monitor did not see, ``reset_envs`` or field writes."""
+        rc = self._lib.dockauv_monitor_sync(monitor.ptr, C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_monitor_sync")
+
+    def monitor_scan_device(self, monitor, rows_out_ptr: int, n_steps: int, stats_ptr: int, terminal_obs_ptr: int = 0,
+                            values_ptr: int = 0, returns_ptr: int = 0, ep_return_ptr: int = 0, ep_length_ptr: int = 0,
+                            ep_outcome_ptr: int = 0, stream: int = 0) -> None:
+        """Returns, lengths and outcomes of the episodes that finish inside rows_out [K][N][n_obs + 2], continuing the monitor's
+        carries (dockauv_monitor_scan): stats float64 [16]; terminal_obs [K][N][n_obs] or 0 (no outcomes); values [K + 1][N] and
+        returns [K][N] or both 0 (no explained variance); ep_return float32 / ep_length int32 / ep_outcome uint8 [K][N] or 0,
+        written only where done.  Asynchronous."""
+        io = _capi.MonitorIO()
+        io.struct_size = C.sizeof(_capi.MonitorIO)
+        io.n_steps = int(n_steps)
+        io.rows_out, io.terminal_obs = rows_out_ptr or None, terminal_obs_ptr or None
+        io.values, io.returns = values_ptr or None, returns_ptr or None
+        io.ep_return, io.ep_length, io.ep_outcome = ep_return_ptr or None, ep_length_ptr or None, ep_outcome_ptr or None
+        io.stats = stats_ptr or None
+        rc = self._lib.dockauv_monitor_scan(self._handle, monitor.ptr, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_monitor_scan")
+
+    def monitor_carry(self, monitor):
+        """(device address of the running returns float32 [N], of the running lengths int32 [N]): dockauv_monitor_carry"""
+        r, ln = C.c_void_p(), C.c_void_p()
+        rc = self._lib.dockauv_monitor_carry(monitor.ptr, C.byref(r), C.byref(ln))
+        _capi.check(self._lib, self._handle, rc, "dockauv_monitor_carry")
+        return int(r.value or 0), int(ln.value or 0)
+
+    def destroy_monitor(self, monitor) -> None:
+        if monitor.ptr is not None and monitor.ptr.value:
+            self._lib.dockauv_monitor_destroy(monitor.ptr)
+            monitor.ptr = C.c_void_p()
+
     def destroy_optim(self, opt) -> None:
         if opt.ptr is not None and opt.ptr.value:
             self._lib.dockauv_optim_destroy(opt.ptr)
@@ -840,6 +888,9 @@ class BatchedDocking3d:
             for opt in getattr(self, "_optims", []):     # (an optimiser goes before its policies)
                 self.destroy_optim(opt)
             self._optims = []
+            for mon in getattr(self, "_monitors", []):   # (a monitor goes before its handle)
+                self.destroy_monitor(mon)
+            self._monitors = []
             for pol in getattr(self, "_policies", []):   # (a policy goes before its handle)
                 self.destroy_policy(pol)
             self._policies = []

@@ -625,6 +625,84 @@ int dockauv_optim_step(dockauv_handle h, dockauv_optim o, const dockauv_optim_io
  * owned by the optimiser and valid until dockauv_optim_destroy) and the number of steps taken.  Any output may be NULL. */
 int dockauv_optim_state(dockauv_optim o, float** m, float** v, long long* n_elements, long long* steps);
 
+/*
+ * The episode monitor: what the reference's learner logs about a collection -- rollout/ep_rew_mean, rollout/ep_len_mean and
+ * train/explained_variance through SB3 (train.py:64-71), the success and collision rates debug.py:192-194 forms from the info
+ * dict's cumulative_reward, t_step, goal_reached, collision and conditions_true (docking3d.py:388-400) -- computed on the device
+ * from buffers a collection already writes, by one pass over the reward and done columns AFTER the collection: the step kernels,
+ * dockauv_rollout and dockauv_collect queue exactly what they queue without a monitor.  All pointers are device pointers; the
+ * scan is asynchronous on the stream and does not synchronise.
+ *
+ * A dockauv_monitor belongs to one float32 handle with an auto-reset mode (with DOCKAUV_RESET_NONE an episode does not restart at
+ * the row after a done).  It owns one running return (float32) and one running length (int32) per env -- the carries -- and its
+ * reduction workspace; everything is allocated at create, later calls allocate nothing.  Destroy it before its handle.  The calls
+ * on one monitor must be ordered on one stream (or by events): they share the carries and the workspace.
+ *
+ * Per env, forwards from k = 0, in exactly this order:
+ *   ret = carry_return + reward[k]        (float32, one plain add)
+ *   len = carry_length + 1                (int32)
+ *   if done[k] > 0.5f:  the episode finishes with (ret, len);  carry_return = 0.0f;  carry_length = 0
+ *   else:               carry_return = ret;  carry_length = len
+ * This is the step kernel's own bookkeeping (cumulative reward <- cumulative reward + reward in float32, zero at an in-kernel
+ * reset), so a carry that starts from the handle's DOCKAUV_F_CUM_REWARD / DOCKAUV_F_TSTEPS reproduces them bit for bit, and
+ * after a scan of the rows of the steps since then the carries ARE those two fields.
+ *
+ * The outcome of a finished episode (needs terminal_obs, the last observation where done: dockauv_step_io.terminal_obs,
+ * dockauv_rollout, dockauv_collect_io) is read off the clipped terminal observation t and the length, the lowest index winning
+ * (the conditions of docking3d.py:608-619):
+ *   0 goal reached     t[0] == 0.0f
+ *   1 out of range     t[0] == 1.0f
+ *   2 attitude limit   fabsf(t[6]) == 1.0f || fabsf(t[7]) == 1.0f
+ *   3 time limit       len > max_timesteps  (is_done tests t_steps >= max_timesteps before the increment: max_timesteps + 1 steps)
+ *   4 collision        done and none of the above
+ * Two limits of this rule: it is a float32 test on a clipped value, so a state within one float32 rounding of a threshold can
+ * classify differently from the float64 reference; and a collision that coincides with another condition is reported under the
+ * lower index.  The product kernels do not deliver the true condition bits (dockauv_step_io.conditions selects the full kernel).
+ *
+ * Per-row outputs (each nullable), written ONLY where done -- the semantics of terminal_obs; other entries keep what they held:
+ * ep_return float32, ep_length int32, ep_outcome uint8 (NULL without terminal_obs), all [n_steps][n_envs].
+ *
+ * stats: float64 [16] over the episodes that finished inside the scanned rows (SB3 averages over its last 100 episodes instead):
+ *   0 n_episodes   1 sum of returns   2 sum of returns^2   3 sum of lengths
+ *   4, 5 min, max return   6, 7 min, max length            (NaN when n_episodes == 0)
+ *   8 .. 12 episodes per outcome 0 .. 4   13 episodes classified        (0 without terminal_obs)
+ *   14 explained variance (NaN when values / returns are not given)      15 0 (reserved)
+ * Sums 1 and 2 are float64 sums of (double)ret and (double)ret * (double)ret; the counts are exact.
+ * Explained variance (what SB3 logs after PPO.train) over y = returns[n_steps * n_envs] and e = y - values[0 .. n_steps *
+ * n_envs) (the subtraction in float32): a first pass forms the float64 means m_y and m_e, a second the float64 sums of
+ * (y - m_y)^2 and (e - m_e)^2; ev = 1 - sum (e - m_e)^2 / sum (y - m_y)^2, NaN when the denominator is 0 (np.var gives SB3 that).
+ * Reproducible: no atomics.  A lane per env in groups of 64; the lanes of a group are added by a fixed tree, the groups'
+ * partials -- in the monitor's workspace -- by one final group of 1 024 lanes (lane t the groups t, t + 1 024, .. in order, then
+ * the same tree, then the sixteen waves in order); the explained variance likewise on at most 256 groups of 256 lanes.  The bits
+ * depend on the inputs, n_envs and n_steps only.  Launches: the scan and the final sums; with values / returns two more.
+ *
+ * dockauv_monitor_create: the carries start from the handle's own cum_reward / t_steps arrays (device copies).
+ * dockauv_monitor_sync: re-reads the carries from the handle at this point of the stream -- after steps the monitor did not
+ *   see, after dockauv_reset_envs and dockauv_set_field.
+ * dockauv_monitor_carry: device pointers to the carries ([n_envs] each), owned by the monitor; either output may be NULL.
+ * Refused before any device call (DOCKAUV_E_INVALID, the message naming the field): a NULL handle, monitor, io, rows_out or
+ * stats; a wrong struct_size; n_steps < 1; ep_outcome without terminal_obs; exactly one of values / returns; a float64 handle; a
+ * handle with DOCKAUV_RESET_NONE; a monitor of another handle.
+ */
+typedef struct dockauv_monitor_s* dockauv_monitor;
+typedef struct dockauv_monitor_io {
+    uint32_t struct_size;          /* sizeof(dockauv_monitor_io): ABI check */
+    int32_t n_steps;               /* K >= 1 */
+    const float* rows_out;         /* [K][n_envs][n_obs + 2]: only the reward and done columns are read */
+    const float* terminal_obs;     /* nullable [K][n_envs][n_obs]: columns 0, 6 and 7 are read where done */
+    const float* values;           /* nullable [K + 1][n_envs] (dockauv_collect_io.values; the first K are read) */
+    const float* returns;          /* nullable [K][n_envs]; values and returns: both or neither */
+    float* ep_return;              /* nullable [K][n_envs] */
+    int32_t* ep_length;            /* nullable [K][n_envs] */
+    uint8_t* ep_outcome;           /* nullable [K][n_envs]; must be NULL without terminal_obs */
+    double* stats;                 /* [16] */
+} dockauv_monitor_io;
+int dockauv_monitor_create(dockauv_handle h, dockauv_monitor* out);
+int dockauv_monitor_destroy(dockauv_monitor m);   /* NULL: 0 */
+int dockauv_monitor_sync(dockauv_monitor m, void* hip_stream);
+int dockauv_monitor_scan(dockauv_handle h, dockauv_monitor m, const dockauv_monitor_io* io, void* hip_stream);
+int dockauv_monitor_carry(dockauv_monitor m, float** carry_return, int32_t** carry_length);
+
 #ifdef __cplusplus
 }
 #endif
