@@ -155,6 +155,21 @@ class OptimIO(C.Structure):
     ]
 
 
+class PPOUpdateIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("normalize_advantage", C.c_int32),
+        ("rows", C.c_void_p),
+        ("actions", C.c_void_p), ("log_prob_old", C.c_void_p), ("advantages", C.c_void_p), ("returns", C.c_void_p),
+        ("values_old", C.c_void_p),
+        ("n_rows", C.c_longlong), ("batch_size", C.c_longlong), ("n_epochs", C.c_int32), ("reserved", C.c_int32),
+        ("seed", C.c_uint64), ("first_epoch", C.c_uint64),
+        ("clip_range", C.c_float), ("clip_range_vf", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float),
+        ("target_kl", C.c_float), ("reserved1", C.c_float),
+        ("opt", OptimIO),
+        ("stats", C.c_void_p),
+    ]
+
+
 class MonitorIO(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("n_steps", C.c_int32),
@@ -220,6 +235,8 @@ SYMBOLS = [
     ("dockauv_optim_step", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(OptimIO), C.c_void_p]),
     ("dockauv_optim_state", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong),
                                       C.POINTER(C.c_longlong)]),
+    ("dockauv_permutation", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_longlong, C.c_void_p, C.c_void_p]),
+    ("dockauv_ppo_update", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PPOUpdateIO), C.c_void_p]),
     ("dockauv_monitor_create", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     ("dockauv_monitor_destroy", C.c_int, [C.c_void_p]),
     ("dockauv_monitor_sync", C.c_int, [C.c_void_p, C.c_void_p]),

@@ -1,6 +1,6 @@
 // dockauv_capi_policy.hip -- C ABI of libdockauv.so (include/dockauv.h), second part: MLP policy and critic, closed-loop
 // rollout, PPO collector, backward, head, optimiser and episode monitor.  The kernels are in dockauv_policy / _collect /
-// _backward / _head / _optim / _monitor.hip.
+// _backward / _head / _optim / _monitor / _update.hip.
 #include <cmath>
 #include <cstring>
 
@@ -30,6 +30,14 @@ struct dockauv_optim_s {
     int len[kOptSegments] = {};   // the index space: actor W1 b1 W2 b2 W3 b3, log_std, critic W1 b1 W2 b2 W3 b3
     int total = 0;
     float *m = nullptr, *v = nullptr;   // [total] each, one allocation (m first)
+    // dockauv_ppo_update: allocated by its first call, grown when a later call needs more
+    OptimCtl* ctl = nullptr;      // the control block
+    long long* index = nullptr;   // [index_rows]: an epoch's permutation
+    long long index_rows = 0;
+    float* scratch = nullptr;     // one minibatch of scratch_rows rows: mean and grad_mean [rows][n_out], v and grad_v [rows]
+    long long scratch_rows = 0;
+    bool pending = false;         // t is behind the control block's count (an update with target_kl > 0 is queued)
+    hipStream_t pending_stream = nullptr;
 };
 
 struct dockauv_monitor_s {
@@ -269,6 +277,82 @@ int repack_policy(dockauv_policy p, float* const* params, const float* log_std, 
     return upload_policy(p, &d, stream);
 }
 
+// the head launches' arguments from the io block; the workspace is the actor's
+void head_args(dockauv_policy actor, const dockauv_ppo_head_io* io, HeadArgs& a) {
+    a.mean = io->mean;
+    a.v = io->v;
+    a.actions = io->actions;
+    a.log_prob_old = io->log_prob_old;
+    a.advantages = io->advantages;
+    a.returns = io->returns;
+    a.row_index = (const long long*)io->row_index;
+    a.log_std = actor->log_std;
+    a.grad_mean = io->grad_mean;
+    a.grad_v = io->grad_v;
+    a.grad_log_std = io->grad_log_std;
+    a.stats = io->stats;
+    a.moments = actor->head_ws;
+    a.partial = actor->head_ws + (size_t)kBwdMaxGroups * kHeadMoments;
+    a.n = (long)io->n_rows;
+    a.n_out = actor->S.n_out;
+    a.normalize = io->normalize_advantage ? 1 : 0;
+    a.clip = io->clip_range;
+    a.vf_coef = io->vf_coef;
+    a.ent_coef = io->ent_coef;
+}
+
+// a dockauv_optim_io against the optimiser (dockauv_optim_step, and the `opt` of dockauv_ppo_update)
+int check_optim_io(dockauv_handle h, dockauv_optim o, const dockauv_optim_io* io) {
+    if (!(io->lr >= 0.0) || !std::isfinite(io->lr)) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.lr: %g must be >= 0 and finite", io->lr);
+    if (int rc = check_optim_arrays(h, "actor", o->len, io->actor_params, io->actor_grads)) return rc;
+    if (!io->log_std) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.log_std is NULL");
+    if (!io->grad_log_std) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.grad_log_std is NULL");
+    if ((const float*)io->log_std == io->grad_log_std)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.grad_log_std is the log_std pointer: gradients are read only, parameters written");
+    return check_optim_arrays(h, "critic", o->len + 7, io->critic_params, io->critic_grads);
+}
+
+// the optimiser launch's arguments but the step's two bias corrections
+void adam_args(dockauv_optim o, const dockauv_optim_io* io, float* stats, AdamArgs& a) {
+    for (int i = 0; i < 6; ++i) {
+        a.p[i] = io->actor_params[i];
+        a.g[i] = io->actor_grads[i];
+        a.p[7 + i] = io->critic_params[i];
+        a.g[7 + i] = io->critic_grads[i];
+    }
+    a.p[6] = io->log_std;
+    a.g[6] = io->grad_log_std;
+    for (int s = 0; s < kOptSegments; ++s) a.len[s] = o->len[s];
+    a.m = o->m;
+    a.v = o->v;
+    a.stats = stats;
+    a.total = o->total;
+    a.max_grad_norm = o->max_grad_norm;
+    a.c1 = (float)(1.0 - o->beta1);
+    a.c2 = (float)(1.0 - o->beta2);
+    a.b2 = (float)o->beta2;
+    a.eps = (float)o->eps;
+}
+
+// step t's bias corrections, in double, rounded once (include/dockauv.h: dockauv_optim_step)
+void bias_corrections(dockauv_optim o, double lr, long long t, float& step_size, float& rsq) {
+    step_size = (float)(lr / (1.0 - std::pow(o->beta1, (double)t)));
+    rsq = (float)(1.0 / std::sqrt(1.0 - std::pow(o->beta2, (double)t)));
+}
+
+// o->t <- the control block's count when an update with target_kl > 0 left it pending: waits for that update's stream
+int reconcile_steps(dockauv_optim o) {
+    if (!o->pending) return 0;
+    dockauv_handle h = o->h;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(o->pending_stream));
+    long long t = 0;
+    HIP_TRY(h, hipMemcpy(&t, &o->ctl->t, sizeof(t), hipMemcpyDeviceToHost));
+    o->t = t;
+    o->pending = false;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -401,26 +485,7 @@ int dockauv_ppo_head(dockauv_handle h, dockauv_policy actor, const dockauv_ppo_h
     HIP_TRY(h, hipSetDevice(h->device));
     if (!actor->head_ws) HIP_TRY(h, hipMalloc((void**)&actor->head_ws, kHeadWorkspaceBytes));
     HeadArgs a{};
-    a.mean = io->mean;
-    a.v = io->v;
-    a.actions = io->actions;
-    a.log_prob_old = io->log_prob_old;
-    a.advantages = io->advantages;
-    a.returns = io->returns;
-    a.row_index = (const long long*)io->row_index;
-    a.log_std = actor->log_std;
-    a.grad_mean = io->grad_mean;
-    a.grad_v = io->grad_v;
-    a.grad_log_std = io->grad_log_std;
-    a.stats = io->stats;
-    a.moments = actor->head_ws;
-    a.partial = actor->head_ws + (size_t)kBwdMaxGroups * kHeadMoments;
-    a.n = (long)io->n_rows;
-    a.n_out = actor->S.n_out;
-    a.normalize = io->normalize_advantage ? 1 : 0;
-    a.clip = io->clip_range;
-    a.vf_coef = io->vf_coef;
-    a.ent_coef = io->ent_coef;
+    head_args(actor, io, a);
     const int rc = launch_ppo_head(a, hip_stream);
     if (rc != 0) return fail(h, DOCKAUV_E_HIP, "PPO head launch failed: %s", hipGetErrorString((hipError_t)rc));
     h->last_stream = (hipStream_t)hip_stream;
@@ -531,12 +596,16 @@ int dockauv_optim_destroy(dockauv_optim o) {
     if (o->h) (void)hipSetDevice(o->h->device);
     (void)hipDeviceSynchronize();
     if (o->m) (void)hipFree(o->m);
+    if (o->ctl) (void)hipFree(o->ctl);
+    if (o->index) (void)hipFree(o->index);
+    if (o->scratch) (void)hipFree(o->scratch);
     delete o;
     return 0;
 }
 
 int dockauv_optim_state(dockauv_optim o, float** m, float** v, long long* n_elements, long long* steps) {
     if (!o) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_optim_state: null optimiser");
+    if (int rc = reconcile_steps(o)) return rc;
     if (m) *m = o->m;
     if (v) *v = o->v;
     if (n_elements) *n_elements = o->total;
@@ -551,43 +620,170 @@ int dockauv_optim_step(dockauv_handle h, dockauv_optim o, const dockauv_optim_io
     if (io->struct_size != sizeof(dockauv_optim_io))
         return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_optim_io));
     if (o->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_step: the optimiser was created for another handle");
-    if (!(io->lr >= 0.0) || !std::isfinite(io->lr)) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.lr: %g must be >= 0 and finite", io->lr);
-    if (int rc = check_optim_arrays(h, "actor", o->len, io->actor_params, io->actor_grads)) return rc;
-    if (!io->log_std) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.log_std is NULL");
-    if (!io->grad_log_std) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.grad_log_std is NULL");
-    if ((const float*)io->log_std == io->grad_log_std)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.grad_log_std is the log_std pointer: gradients are read only, parameters written");
-    if (int rc = check_optim_arrays(h, "critic", o->len + 7, io->critic_params, io->critic_grads)) return rc;
+    if (int rc = check_optim_io(h, o, io)) return rc;
+    if (int rc = reconcile_steps(o)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t stream = (hipStream_t)hip_stream;
     const long long t = ++o->t;
     AdamArgs a{};
-    for (int i = 0; i < 6; ++i) {
-        a.p[i] = io->actor_params[i];
-        a.g[i] = io->actor_grads[i];
-        a.p[7 + i] = io->critic_params[i];
-        a.g[7 + i] = io->critic_grads[i];
-    }
-    a.p[6] = io->log_std;
-    a.g[6] = io->grad_log_std;
-    for (int s = 0; s < kOptSegments; ++s) a.len[s] = o->len[s];
-    a.m = o->m;
-    a.v = o->v;
-    a.stats = io->stats;
-    a.total = o->total;
-    a.max_grad_norm = o->max_grad_norm;
-    a.c1 = (float)(1.0 - o->beta1);
-    a.c2 = (float)(1.0 - o->beta2);
-    a.b2 = (float)o->beta2;
-    a.step_size = (float)(io->lr / (1.0 - std::pow(o->beta1, (double)t)));
-    a.rsq = (float)(1.0 / std::sqrt(1.0 - std::pow(o->beta2, (double)t)));
-    a.eps = (float)o->eps;
+    adam_args(o, io, io->stats, a);
+    bias_corrections(o, io->lr, t, a.step_size, a.rsq);
     const int rc = launch_adam_step(a, stream);
     if (rc != 0) return fail(h, DOCKAUV_E_HIP, "optimiser launch failed: %s", hipGetErrorString((hipError_t)rc));
     h->last_stream = stream;
     if (int rc2 = repack_policy(o->actor, io->actor_params, io->log_std, stream)) return rc2;
     if (o->critic)
         if (int rc2 = repack_policy(o->critic, io->critic_params, nullptr, stream)) return rc2;
+    return 0;
+}
+
+int dockauv_permutation(dockauv_handle h, uint64_t seed, uint64_t epoch, long long n, int64_t* out, void* hip_stream) {
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_permutation: null handle");
+    if (!out) return fail(h, DOCKAUV_E_INVALID, "dockauv_permutation: out is NULL");
+    if (n < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_permutation: n %lld must be >= 1", n);
+    if (n > (1ll << 31)) return fail(h, DOCKAUV_E_INVALID, "dockauv_permutation: n %lld must be <= 2^31 (the network works on 32-bit words)", n);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = launch_permutation(seed, epoch, n, (long long*)out, hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "permutation launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
+    return 0;
+}
+
+int dockauv_ppo_update(dockauv_handle h, dockauv_optim o, const dockauv_ppo_update_io* io, void* hip_stream) {
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_ppo_update: null handle");
+    if (!o) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update: null optimiser");
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update: io is NULL");
+    if (io->struct_size != sizeof(dockauv_ppo_update_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_ppo_update_io));
+    if (o->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update: the optimiser was created for another handle");
+    dockauv_policy actor = o->actor, critic = o->critic;
+    if (int rc = check_actor(h, actor, "dockauv_ppo_update", true)) return rc;
+    const long long M = io->n_rows, B = io->batch_size;
+    if (M < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.n_rows: %lld must be >= 1", M);
+    if (M > (1ll << 31)) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.n_rows: %lld must be <= 2^31 (dockauv_permutation)", M);
+    if (B < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.batch_size: %lld must be >= 1", B);
+    if (io->n_epochs < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.n_epochs: %d must be >= 1", io->n_epochs);
+    const long long J = (M + B - 1) / B, last = M - (J - 1) * B;
+    if (io->normalize_advantage && last < 2)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.batch_size: the last minibatch of %lld rows in batches of %lld has one row, "
+                    "normalize_advantage needs two (the unbiased deviation)", M, B);
+    if (!(io->clip_range > 0.0f)) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.clip_range: %g must be > 0", (double)io->clip_range);
+    if (!(io->clip_range_vf >= 0.0f)) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.clip_range_vf: %g must be >= 0 (0 = off)", (double)io->clip_range_vf);
+    if (!(io->target_kl >= 0.0f)) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.target_kl: %g must be >= 0 (0 = off)", (double)io->target_kl);
+    if (!io->rows) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.rows is NULL");
+    if (!io->actions) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.actions is NULL");
+    if (!io->log_prob_old) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.log_prob_old is NULL");
+    if (!io->advantages) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.advantages is NULL");
+    if (critic && !io->returns) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.returns is NULL (the optimiser has a critic)");
+    if (io->clip_range_vf > 0.0f && !critic)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.clip_range_vf: %g, but the optimiser has no critic", (double)io->clip_range_vf);
+    if (io->clip_range_vf > 0.0f && !io->values_old)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.values_old is NULL (clip_range_vf is %g)", (double)io->clip_range_vf);
+    if (!io->stats) return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.stats is NULL");
+    if (io->opt.struct_size != sizeof(dockauv_optim_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_io.struct_size: got %u, library has %zu", io->opt.struct_size, sizeof(dockauv_optim_io));
+    if (int rc = check_optim_io(h, o, &io->opt)) return rc;
+    if (io->opt.stats)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update_io.opt.stats must be NULL: the norm and coef go to columns 8, 9 of dockauv_ppo_update_io.stats");
+    for (dockauv_policy p : {actor, critic}) {
+        if (!p) continue;
+        BackwardLayout L;
+        backward_layout(p->S, L);
+        if (backward_lds_bytes(L) > kPolMaxLds)
+            return fail(h, DOCKAUV_E_INVALID, "dockauv_ppo_update: the backward kernel needs %zu B of LDS for n_in %d, n_hidden %d / %d, more than "
+                        "the 160 KiB of a group (dockauv_policy_backward)", backward_lds_bytes(L), p->S.n_in, p->S.n_h1, p->S.n_h2);
+    }
+    if (int rc = reconcile_steps(o)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+
+    // the optimiser's buffers: allocated here the first time, grown when this call needs more (hipFree waits for the device)
+    const int n_u = actor->S.n_out;
+    const long long rows_mb = B < M ? B : M;
+    if (!o->ctl) HIP_TRY(h, hipMalloc((void**)&o->ctl, sizeof(OptimCtl)));
+    if (o->index_rows < M) {
+        if (o->index) HIP_TRY(h, hipFree(o->index));
+        o->index = nullptr;
+        o->index_rows = 0;
+        HIP_TRY(h, hipMalloc((void**)&o->index, (size_t)M * sizeof(long long)));
+        o->index_rows = M;
+    }
+    if (o->scratch_rows < rows_mb) {
+        if (o->scratch) HIP_TRY(h, hipFree(o->scratch));
+        o->scratch = nullptr;
+        o->scratch_rows = 0;
+        HIP_TRY(h, hipMalloc((void**)&o->scratch, (size_t)rows_mb * (2 * (size_t)n_u + 2) * sizeof(float)));
+        o->scratch_rows = rows_mb;
+    }
+    if (!actor->head_ws) HIP_TRY(h, hipMalloc((void**)&actor->head_ws, kHeadWorkspaceBytes));
+    float* mean = o->scratch;
+    float* grad_mean = mean + (size_t)rows_mb * n_u;
+    float* v = grad_mean + (size_t)rows_mb * n_u;
+    float* grad_v = v + rows_mb;
+
+    const long long t0 = o->t;
+    int rc = launch_update_begin(o->ctl, t0, stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "update control launch failed: %s", hipGetErrorString((hipError_t)rc));
+    dockauv_policy_grads ag{}, cg{};
+    ag.struct_size = cg.struct_size = sizeof(dockauv_policy_grads);
+    float* const* agp = (float* const*)io->opt.actor_grads;     // (the caller's gradient buffers: read by the optimiser, written here)
+    float* const* cgp = (float* const*)io->opt.critic_grads;
+    ag.dW1 = agp[0]; ag.db1 = agp[1]; ag.dW2 = agp[2]; ag.db2 = agp[3]; ag.dW3 = agp[4]; ag.db3 = agp[5];
+    cg.dW1 = cgp[0]; cg.db1 = cgp[1]; cg.dW2 = cgp[2]; cg.db2 = cgp[3]; cg.dW3 = cgp[4]; cg.db3 = cgp[5];
+    long long k = 0;      // minibatches queued by this call
+    for (int e = 0; e < io->n_epochs; ++e) {
+        rc = launch_permutation(io->seed, io->first_epoch + (uint64_t)e, M, o->index, stream);
+        if (rc != 0) return fail(h, DOCKAUV_E_HIP, "permutation launch failed: %s", hipGetErrorString((hipError_t)rc));
+        for (long long j = 0; j < J; ++j, ++k) {
+            const long long n = j + 1 < J ? B : last;
+            const int64_t* idx = (const int64_t*)(o->index + j * B);
+            float* st = io->stats + (size_t)k * 12;
+            if ((rc = dockauv_policy_forward_rows(h, actor, io->rows, idx, n, mean, stream)) != 0) return rc;
+            if (critic && (rc = dockauv_policy_forward_rows(h, critic, io->rows, idx, n, v, stream)) != 0) return rc;
+            dockauv_ppo_head_io hio{};
+            hio.normalize_advantage = io->normalize_advantage;
+            hio.mean = mean;
+            hio.v = critic ? v : nullptr;
+            hio.actions = io->actions;
+            hio.log_prob_old = io->log_prob_old;
+            hio.advantages = io->advantages;
+            hio.returns = critic ? io->returns : nullptr;
+            hio.row_index = idx;
+            hio.n_rows = n;
+            hio.clip_range = io->clip_range;
+            hio.vf_coef = io->vf_coef;
+            hio.ent_coef = io->ent_coef;
+            hio.grad_mean = grad_mean;
+            hio.grad_v = critic ? grad_v : nullptr;
+            hio.grad_log_std = (float*)io->opt.grad_log_std;
+            hio.stats = st;
+            HeadArgs ha{};
+            head_args(actor, &hio, ha);
+            HeadUpdate hu{};
+            hu.v_old = io->clip_range_vf > 0.0f ? io->values_old : nullptr;
+            hu.clip_vf = io->clip_range_vf;
+            hu.ctl = o->ctl;
+            hu.target_kl = io->target_kl;
+            bias_corrections(o, io->opt.lr, t0 + 1 + k, hu.step_size, hu.rsq);
+            rc = launch_ppo_head_update(ha, hu, stream);
+            if (rc != 0) return fail(h, DOCKAUV_E_HIP, "PPO head launch failed: %s", hipGetErrorString((hipError_t)rc));
+            if ((rc = dockauv_policy_backward(h, actor, io->rows, idx, n, grad_mean, &ag, stream)) != 0) return rc;
+            if (critic && (rc = dockauv_policy_backward(h, critic, io->rows, idx, n, grad_v, &cg, stream)) != 0) return rc;
+            AdamArgs aa{};
+            adam_args(o, &io->opt, st + 8, aa);
+            rc = launch_adam_step_ctl(aa, o->ctl, stream);
+            if (rc != 0) return fail(h, DOCKAUV_E_HIP, "optimiser launch failed: %s", hipGetErrorString((hipError_t)rc));
+            if ((rc = repack_policy(actor, io->opt.actor_params, io->opt.log_std, stream)) != 0) return rc;
+            if (critic && (rc = repack_policy(critic, io->opt.critic_params, nullptr, stream)) != 0) return rc;
+        }
+    }
+    h->last_stream = stream;
+    if (io->target_kl > 0.0f) {
+        o->pending = true;
+        o->pending_stream = stream;
+    } else {
+        o->t = t0 + k;
+    }
     return 0;
 }
 

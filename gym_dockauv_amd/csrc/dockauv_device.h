@@ -396,7 +396,7 @@ int launch_sequence_f32(const KernelArgs<float, 2>& a, const StepRequest& r, con
 #ifdef __HIPCC__
 // Philox4x32-10 (Salmon et al., SC'11): counter-based, integer only -> bit-exact against the NumPy restatement in
 // oracle/philox_ref.py.  Counter slot 3 names the stream: 0 = episode generator, 1 = current noise (dockauv_step.hip.inc),
-// 2 = policy exploration noise (dockauv_policy.hip).
+// 2 = policy exploration noise (dockauv_policy.hip), 3 = round keys of the minibatch permutation (dockauv_update.hip).
 __device__ __forceinline__ void philox4x32_10_(uint32_t c[4], uint32_t k0, uint32_t k1) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
@@ -547,6 +547,7 @@ constexpr int kHeadMoments = 4;
 constexpr int kHeadSums = 4 + 8;          // 8 = DOCKAUV_MAX_U
 constexpr size_t kHeadWorkspaceBytes = (size_t)kBwdMaxGroups * (kHeadMoments + kHeadSums) * sizeof(double);
 struct HeadArgs {
+    static constexpr bool kClipVf = false, kGate = false;   // (what the kernels are instantiated on: dockauv_ppo_head's own)
     const float *mean, *v;                // [n][n_out]; [n] or null (no critic)
     const float *actions, *log_prob_old, *advantages, *returns;   // row arrays, read at row_index[r]
     const long long* row_index;           // nullable [n]
@@ -561,6 +562,35 @@ struct HeadArgs {
 // group order.  Returns a hipError_t as int.
 int launch_ppo_head(const HeadArgs& a, void* stream);
 
+// The optimiser's control block in device memory (dockauv_ppo_update): written by ONE thread -- update_begin_kernel at the start
+// of a call, then the gated final-sums kernel of every minibatch -- and read by every thread of the controlled Adam kernel.
+struct OptimCtl {
+    long long t;                          // Adam steps applied so far (what the host reads back when the count is pending)
+    int stop, reserved;                   // sticky for the rest of the call: SB3's target_kl rule tripped
+    float step_size, rsq;                 // the bias corrections of step t (the host's double arithmetic, rounded once)
+};
+// The head inside dockauv_ppo_update: the same kernels instantiated on these argument blocks.
+struct HeadArgsVf : HeadArgs {            // rows kernel with clip_range_vf > 0
+    static constexpr bool kClipVf = true;
+    const float* v_old;                   // [M], read at row_index[r]
+    float clip_vf;
+};
+struct HeadArgsGate : HeadArgs {          // final-sums kernel that decides whether the minibatch is applied
+    static constexpr bool kGate = true;
+    OptimCtl* ctl;
+    float target_kl;                      // 0: no early stop
+    float step_size, rsq;                 // of step ctl->t + 1, copied into the block when the minibatch is applied
+};
+struct HeadUpdate {
+    const float* v_old;                   // null: clip_vf unused
+    float clip_vf;                        // 0: the shipped rows kernel
+    OptimCtl* ctl;
+    float target_kl, step_size, rsq;
+};
+// launch_ppo_head with the gated final sums (stats: [12], columns 8..11 written too) and, with u.clip_vf > 0, the clipped value
+// loss.  Returns a hipError_t as int.
+int launch_ppo_head_update(const HeadArgs& a, const HeadUpdate& u, void* stream);
+
 // ------------------------------------------------------------------------------------------ optimiser (dockauv_optim.hip)
 // Gradient-norm clipping and one Adam step (include/dockauv.h: dockauv_optim_step states the arithmetic) over one index space
 // of kOptSegments arrays back to back: actor W1 b1 W2 b2 W3 b3, log_std, critic W1 b1 W2 b2 W3 b3, torch.nn.Linear layout; a
@@ -571,6 +601,7 @@ constexpr int kOptSegments = 13;
 constexpr int kOptThreads = 1024;
 constexpr int kOptChunk = 4;
 struct AdamArgs {
+    static constexpr bool kCtl = false;   // (what the kernel is instantiated on: dockauv_optim_step's own)
     float* p[kOptSegments];               // updated in place
     const float* g[kOptSegments];         // read only
     int len[kOptSegments];
@@ -582,6 +613,22 @@ struct AdamArgs {
 };
 // Returns a hipError_t as int.
 int launch_adam_step(const AdamArgs& a, void* stream);
+// The same kernel instantiated for dockauv_ppo_update: step_size and rsq come from the control block, not from the arguments, and
+// with its stop flag set the launch leaves p, m, v and stats untouched.  Returns a hipError_t as int.
+struct AdamArgsCtl : AdamArgs {
+    static constexpr bool kCtl = true;
+    const OptimCtl* ctl;
+};
+int launch_adam_step_ctl(const AdamArgs& a, const OptimCtl* ctl, void* stream);
+
+// ------------------------------------------------------------------------------------------ whole update (dockauv_update.hip)
+// out[i] = P_{seed, epoch}(i), i < n <= 2^31: the keyed bijection include/dockauv.h states (dockauv_permutation), one lane per
+// output, no workspace.  Philox counter slot 3 of its round keys:
+constexpr uint32_t kPermStream = 3u;
+constexpr int kPermThreads = 256;
+int launch_permutation(unsigned long long seed, unsigned long long epoch, long long n, long long* out, void* stream);
+// ctl <- {t0, no stop}: the first launch of a dockauv_ppo_update.  Returns a hipError_t as int.
+int launch_update_begin(OptimCtl* ctl, long long t0, void* stream);
 
 // ------------------------------------------------------------------------------------------ episode monitor (dockauv_monitor.hip)
 // Returns, lengths and outcomes of the episodes that end inside the packed rows of a collection, and the explained variance of

@@ -102,7 +102,10 @@ __global__ __launch_bounds__(kHeadThreads) void ppo_head_moments_kernel(const He
     }
 }
 
-__global__ __launch_bounds__(kHeadThreads) void ppo_head_rows_kernel(const HeadArgs a) {
+// Args: HeadArgs (dockauv_ppo_head) or HeadArgsVf (dockauv_ppo_update with clip_range_vf > 0: the value error is taken at the
+// value clipped to v_old +- clip_vf, include/dockauv.h: dockauv_ppo_update)
+template <class Args>
+__global__ __launch_bounds__(kHeadThreads) void ppo_head_rows_kernel(const Args a) {
     __shared__ double red[kHeadThreads / 64][kHeadSums];
     __shared__ double mom[kBwdMaxGroups * kHeadMoments];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -137,6 +140,7 @@ __global__ __launch_bounds__(kHeadThreads) void ppo_head_rows_kernel(const HeadA
     for (long b = blockIdx.x; b < passes; b += gridDim.x) {
         long pos[kHeadChunk], at[kHeadChunk];
         float adv[kHeadChunk], lpo[kHeadChunk], ret[kHeadChunk], val[kHeadChunk], act[kHeadChunk][DOCKAUV_MAX_U], mu[kHeadChunk][DOCKAUV_MAX_U];
+        float vold[kHeadChunk];
 #pragma unroll
         for (int c = 0; c < kHeadChunk; ++c) {
             const long r = head_row_(b, c, tid);
@@ -149,6 +153,7 @@ __global__ __launch_bounds__(kHeadThreads) void ppo_head_rows_kernel(const HeadA
             lpo[c] = a.log_prob_old[at[c]];
             ret[c] = ret_src[at[c]];
             val[c] = v_src[pos[c]];
+            if constexpr (Args::kClipVf) vold[c] = a.v_old[at[c]];
 #pragma unroll
             for (int j = 0; j < DOCKAUV_MAX_U; ++j) {
                 const int jc = j < n_u ? j : n_u - 1;   // (behind n_out: the last action again, dropped below)
@@ -176,7 +181,14 @@ __global__ __launch_bounds__(kHeadThreads) void ppo_head_rows_kernel(const HeadA
             const float clamped = fminf(fmaxf(ratio, lo), hi);
             const float surrogate = fminf(ratio * A, clamped * A);
             const float g = live ? -(A * ratio) / nf : 0.0f;
-            const float dv = critic ? val[c] - ret[c] : 0.0f;
+            [[maybe_unused]] float vc = 0.0f;
+            [[maybe_unused]] bool vlive = true;
+            if constexpr (Args::kClipVf) {
+                const float d = val[c] - vold[c];
+                vc = vold[c] + fminf(fmaxf(d, -a.clip_vf), a.clip_vf);
+                vlive = fabsf(d) <= a.clip_vf;      // (the inclusive edge: torch.clamp's backward)
+            }
+            const float dv = critic ? (Args::kClipVf ? vc : val[c]) - ret[c] : 0.0f;
             acc[0] += (double)surrogate;
             acc[1] += (double)(dv * dv);
             acc[2] += (double)((ratio - 1.0f) - lr);
@@ -189,7 +201,7 @@ __global__ __launch_bounds__(kHeadThreads) void ppo_head_rows_kernel(const HeadA
                     acc[4 + j] += (double)(g * fmaf(z[j], z[j], -1.0f));
                 }
             }
-            if (critic) a.grad_v[pos[c]] = (two_vf * dv) / nf;
+            if (critic) a.grad_v[pos[c]] = (Args::kClipVf && !vlive) ? 0.0f : (two_vf * dv) / nf;
         }
     }
 
@@ -203,7 +215,9 @@ __global__ __launch_bounds__(kHeadThreads) void ppo_head_rows_kernel(const HeadA
 }
 
 // sum k = partial[0][k] + partial[1][k] + ... in group order, rounded to float32 once
-__global__ __launch_bounds__(64) void ppo_head_final_kernel(const HeadArgs a, int groups) {
+// Args: HeadArgs, or HeadArgsGate (dockauv_ppo_update): thread 0 then decides whether the optimiser applies this minibatch
+template <class Args>
+__global__ __launch_bounds__(64) void ppo_head_final_kernel(const Args a, int groups) {
     __shared__ double total[kHeadSums];
     const int tid = threadIdx.x;
     if (tid < kHeadSums) {
@@ -225,6 +239,26 @@ __global__ __launch_bounds__(64) void ppo_head_final_kernel(const HeadArgs a, in
         a.stats[3] = entropy_loss;
         a.stats[4] = (float)(total[2] / n);
         a.stats[5] = (float)(total[3] / n);
+        if constexpr (Args::kGate) {
+            // SB3's rule on the stored statistic, in float32; once stopped, stopped for the rest of the call
+            const float approx_kl = (float)(total[2] / n);
+            const bool stop = a.ctl->stop != 0 || (a.target_kl > 0.0f && approx_kl > 1.5f * a.target_kl);
+            float applied = 0.0f, step = 0.0f;
+            if (stop) {
+                a.ctl->stop = 1;
+            } else {
+                const long long t = a.ctl->t + 1;
+                a.ctl->t = t;
+                a.ctl->step_size = a.step_size;
+                a.ctl->rsq = a.rsq;
+                applied = 1.0f;
+                step = (float)t;
+            }
+            a.stats[8] = 0.0f;      // (norm and coef: the optimiser's launch, when it applies the step)
+            a.stats[9] = 0.0f;
+            a.stats[10] = applied;
+            a.stats[11] = step;
+        }
     }
 }
 
@@ -236,8 +270,34 @@ int launch_ppo_head(const HeadArgs& a, void* stream) {
     const unsigned groups = (unsigned)(passes < kBwdMaxGroups ? passes : kBwdMaxGroups);
     hipStream_t st = (hipStream_t)stream;
     if (a.normalize) hipLaunchKernelGGL(ppo_head_moments_kernel, dim3(groups), dim3(kHeadThreads), 0, st, a);
-    hipLaunchKernelGGL(ppo_head_rows_kernel, dim3(groups), dim3(kHeadThreads), 0, st, a);
-    hipLaunchKernelGGL(ppo_head_final_kernel, dim3(1), dim3(64), 0, st, a, (int)groups);
+    hipLaunchKernelGGL(ppo_head_rows_kernel<HeadArgs>, dim3(groups), dim3(kHeadThreads), 0, st, a);
+    hipLaunchKernelGGL(ppo_head_final_kernel<HeadArgs>, dim3(1), dim3(64), 0, st, a, (int)groups);
+    return (int)hipGetLastError();
+}
+
+int launch_ppo_head_update(const HeadArgs& a, const HeadUpdate& u, void* stream) {
+    if (a.n < 1 || (a.normalize && a.n < 2) || a.n_out < 1 || a.n_out > DOCKAUV_MAX_U || !u.ctl) return (int)hipErrorInvalidValue;
+    if (u.clip_vf > 0.0f && (!u.v_old || !a.v)) return (int)hipErrorInvalidValue;
+    const long passes = (a.n + kHeadPassRows - 1) / kHeadPassRows;
+    const unsigned groups = (unsigned)(passes < kBwdMaxGroups ? passes : kBwdMaxGroups);
+    hipStream_t st = (hipStream_t)stream;
+    if (a.normalize) hipLaunchKernelGGL(ppo_head_moments_kernel, dim3(groups), dim3(kHeadThreads), 0, st, a);
+    if (u.clip_vf > 0.0f) {
+        HeadArgsVf x;
+        static_cast<HeadArgs&>(x) = a;
+        x.v_old = u.v_old;
+        x.clip_vf = u.clip_vf;
+        hipLaunchKernelGGL(ppo_head_rows_kernel<HeadArgsVf>, dim3(groups), dim3(kHeadThreads), 0, st, x);
+    } else {
+        hipLaunchKernelGGL(ppo_head_rows_kernel<HeadArgs>, dim3(groups), dim3(kHeadThreads), 0, st, a);
+    }
+    HeadArgsGate g;
+    static_cast<HeadArgs&>(g) = a;
+    g.ctl = u.ctl;
+    g.target_kl = u.target_kl;
+    g.step_size = u.step_size;
+    g.rsq = u.rsq;
+    hipLaunchKernelGGL(ppo_head_final_kernel<HeadArgsGate>, dim3(1), dim3(64), 0, st, g, (int)groups);
     return (int)hipGetLastError();
 }
 

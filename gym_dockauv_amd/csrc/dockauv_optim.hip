@@ -29,9 +29,18 @@ __device__ __forceinline__ double wave_sum_(double v) {
     return v;
 }
 
-__global__ __launch_bounds__(kOptThreads) void adam_step_kernel(const AdamArgs a) {
+// A: AdamArgs (dockauv_optim_step), or AdamArgsCtl (dockauv_ppo_update): the step's two bias corrections come from the
+// optimiser's control block, and a launch that finds its stop flag set changes nothing
+template <class A>
+__global__ __launch_bounds__(kOptThreads) void adam_step_kernel(const A a) {
     __shared__ double red[kOptThreads / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    [[maybe_unused]] float ctl_step_size = 0.0f, ctl_rsq = 0.0f;
+    if constexpr (A::kCtl) {
+        if (a.ctl->stop != 0) return;       // (the same in every thread of the grid)
+        ctl_step_size = a.ctl->step_size;
+        ctl_rsq = a.ctl->rsq;
+    }
 
     // the thread's own element: segment s, offset k in it (at most one segment holds i)
     const int i = (int)blockIdx.x * kOptThreads + tid;
@@ -92,8 +101,8 @@ __global__ __launch_bounds__(kOptThreads) void adam_step_kernel(const AdamArgs a
         m = fmaf(a.c1, g - m, m);
         const float bv = a.b2 * v;
         v = fmaf(a.c2 * g, g, bv);
-        const float denom = fmaf(sqrtf(v), a.rsq, a.eps);
-        const float upd = a.step_size * (m / denom);
+        const float denom = fmaf(sqrtf(v), A::kCtl ? ctl_rsq : a.rsq, a.eps);
+        const float upd = (A::kCtl ? ctl_step_size : a.step_size) * (m / denom);
         *pp = p - upd;
         a.m[i] = m;
         a.v[i] = v;
@@ -102,15 +111,35 @@ __global__ __launch_bounds__(kOptThreads) void adam_step_kernel(const AdamArgs a
 
 }  // namespace
 
-int launch_adam_step(const AdamArgs& a, void* stream) {
+namespace {
+
+// groups of the launch, 0: the arguments do not describe one index space
+unsigned adam_groups(const AdamArgs& a) {
     long total = 0;
     for (int s = 0; s < kOptSegments; ++s) {
-        if (a.len[s] < 0 || (a.len[s] > 0 && (!a.p[s] || !a.g[s]))) return (int)hipErrorInvalidValue;
+        if (a.len[s] < 0 || (a.len[s] > 0 && (!a.p[s] || !a.g[s]))) return 0;
         total += a.len[s];
     }
-    if (total < 1 || total != (long)a.total || !a.m || !a.v) return (int)hipErrorInvalidValue;
-    const unsigned groups = (unsigned)((total + kOptThreads - 1) / kOptThreads);
-    hipLaunchKernelGGL(adam_step_kernel, dim3(groups), dim3(kOptThreads), 0, (hipStream_t)stream, a);
+    if (total < 1 || total != (long)a.total || !a.m || !a.v) return 0;
+    return (unsigned)((total + kOptThreads - 1) / kOptThreads);
+}
+
+}  // namespace
+
+int launch_adam_step(const AdamArgs& a, void* stream) {
+    const unsigned groups = adam_groups(a);
+    if (!groups) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(adam_step_kernel<AdamArgs>, dim3(groups), dim3(kOptThreads), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+int launch_adam_step_ctl(const AdamArgs& a, const OptimCtl* ctl, void* stream) {
+    const unsigned groups = adam_groups(a);
+    if (!groups || !ctl) return (int)hipErrorInvalidValue;
+    AdamArgsCtl x;
+    static_cast<AdamArgs&>(x) = a;
+    x.ctl = ctl;
+    hipLaunchKernelGGL(adam_step_kernel<AdamArgsCtl>, dim3(groups), dim3(kOptThreads), 0, (hipStream_t)stream, x);
     return (int)hipGetLastError();
 }
 

@@ -802,6 +802,46 @@ class BatchedDocking3d:
         _capi.check(self._lib, self._handle, rc, "dockauv_optim_state")
         return int(m.value or 0), int(v.value or 0), int(n.value), int(t.value)
 
+    def permutation_device(self, seed: int, epoch: int, n: int, out_ptr: int, stream: int = 0) -> None:
+        """out int64 [n] <- the keyed permutation P_{seed, epoch} of 0 .. n - 1 (dockauv_permutation, stated exactly by
+        ``MLPPolicy.permutation_reference``); asynchronous."""
+        rc = self._lib.dockauv_permutation(self._handle, int(seed) & (2 ** 64 - 1), int(epoch) & (2 ** 64 - 1), int(n),
+                                           C.c_void_p(out_ptr or None), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_permutation")
+
+    def ppo_update_device(self, opt, rows_ptr: int, n_rows: int, batch_size: int, n_epochs: int, lr: float, actions_ptr: int,
+                          log_prob_old_ptr: int, advantages_ptr: int, returns_ptr: int, stats_ptr: int, actor_param_ptrs,
+                          log_std_ptr: int, actor_grad_ptrs, grad_log_std_ptr: int, critic_param_ptrs=None, critic_grad_ptrs=None, *,
+                          clip_range: float, vf_coef: float, ent_coef: float, normalize_advantage: bool = True,
+                          clip_range_vf: float = 0.0, values_old_ptr: int = 0, target_kl: float = 0.0, seed: int = 0,
+                          first_epoch: int = 0, stream: int = 0) -> None:
+        """SB3's PPO.train loop queued by one host call (dockauv_ppo_update): ``n_epochs`` passes over the ``n_rows`` packed rows
+        at ``rows_ptr`` in minibatches of ``batch_size`` shuffled by ``permutation_device(seed, first_epoch + e, n_rows)``; the
+        row arrays are float32 [n_rows][n_u] / [n_rows]; the parameter and gradient pointers as in ``optim_step_device``; stats
+        float32 [n_epochs][n_minibatches][12].  ``clip_range_vf`` / ``target_kl`` 0: off.  Asynchronous; with ``target_kl`` the
+        optimiser's step count is read back by the next call that needs it."""
+        io = _capi.PPOUpdateIO()
+        io.struct_size = C.sizeof(_capi.PPOUpdateIO)
+        io.normalize_advantage = 1 if normalize_advantage else 0
+        io.rows = rows_ptr or None
+        io.actions, io.log_prob_old = actions_ptr or None, log_prob_old_ptr or None
+        io.advantages, io.returns, io.values_old = advantages_ptr or None, returns_ptr or None, values_old_ptr or None
+        io.n_rows, io.batch_size, io.n_epochs = int(n_rows), int(batch_size), int(n_epochs)
+        io.seed, io.first_epoch = int(seed) & (2 ** 64 - 1), int(first_epoch) & (2 ** 64 - 1)
+        io.clip_range, io.clip_range_vf, io.vf_coef, io.ent_coef = float(clip_range), float(clip_range_vf), float(vf_coef), float(ent_coef)
+        io.target_kl = float(target_kl)
+        io.opt.struct_size = C.sizeof(_capi.OptimIO)
+        io.opt.lr = float(lr)
+        for dst, src in ((io.opt.actor_params, actor_param_ptrs), (io.opt.actor_grads, actor_grad_ptrs),
+                         (io.opt.critic_params, critic_param_ptrs), (io.opt.critic_grads, critic_grad_ptrs)):
+            for i, x in enumerate(src if src is not None else [0] * 6):
+                dst[i] = int(x) or None
+        io.opt.log_std, io.opt.grad_log_std = log_std_ptr or None, grad_log_std_ptr or None
+        io.stats = stats_ptr or None
+        rc = self._lib.dockauv_ppo_update(self._handle, opt.ptr, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_ppo_update")
+        opt.policy.has_log_std = True
+
     # ------------------------------------------------------------------------------------------ episode monitor
     def make_monitor(self):
         """An episode monitor of this handle (dockauv_monitor_create): per-env running returns and lengths, started from the

@@ -462,6 +462,81 @@ class TorchDocking3d:
                 opt.step(lr, stats=st[8:])
         return stats
 
+    def permutation(self, seed: int, epoch: int, n: int):
+        """A fresh int64 [n] device tensor: the keyed permutation P_{seed, epoch} of 0 .. n - 1 (dockauv_permutation on the
+        current stream; ``MLPPolicy.permutation_reference`` states it exactly).  The shuffle of ``ppo_train``."""
+        torch = self.torch
+        n = int(n)
+        if n < 1 or n > 1 << 31:
+            raise ValueError("n must be in 1 .. 2^31")
+        out = torch.empty((n,), device=self.device, dtype=torch.int64)
+        self.batch.permutation_device(seed, epoch, n, out.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+        return out
+
+    def ppo_train(self, opt, collected, n_epochs: int, batch_size: int, lr: float, *, clip_range: float, vf_coef: float,
+                  ent_coef: float, normalize_advantage: bool = True, clip_range_vf=None, target_kl=None, seed: int = 0,
+                  first_epoch: int = 0):
+        """``ppo_update`` queued by ONE host call (dockauv_ppo_update on the current stream), with the two hyper-parameters
+        that one leaves out.  Minibatch j of epoch e is ``permutation(seed, first_epoch + e, K * N)[j * batch_size : ...]``
+        (pass a ``first_epoch`` that advances by ``n_epochs`` per call); per minibatch the library queues what ``ppo_update``
+        queues -- both forwards, the head, both backwards into ``opt.grads``, the optimiser step with its repack -- on its own
+        scratch: no torch allocation, no host synchronisation.  ``clip_range_vf`` (None / 0: off) clips the value to
+        ``collected.values`` +- clip_range_vf as SB3 does.  ``target_kl`` (None / 0: off): the first minibatch whose approx_kl
+        exceeds 1.5 target_kl is not applied and neither is any after it (SB3's early stop, decided on the device); the
+        remaining minibatches still run on the frozen weights, and ``opt.steps()`` afterwards waits for the update and reads
+        how many were applied.  The weights are loaded once at the start from the optimiser's tensors, as in ``ppo_update``.
+        Returns stats [n_epochs, n_minibatches, 12] on the device: the head's eight, the gradient norm before clipping and
+        the clipping coefficient, applied (1 / 0), the Adam step number; columns 8..11 are 0 where nothing was applied."""
+        torch = self.torch
+        c, policy, value = collected, opt.policy, opt.value
+        n_epochs, batch_size = int(n_epochs), int(batch_size)
+        if n_epochs < 1 or batch_size < 1:
+            raise ValueError("n_epochs and batch_size must be >= 1")
+        if c.log_prob is None or (value is not None and (c.advantages is None or c.returns is None)) or c.advantages is None:
+            raise ValueError("collected must hold log_prob and advantages (and returns with a critic): collect() with a critic")
+        clip_range_vf, target_kl = float(clip_range_vf or 0.0), float(target_kl or 0.0)
+        if clip_range_vf < 0.0 or target_kl < 0.0:
+            raise ValueError("clip_range_vf and target_kl must be >= 0 (None or 0: off)")
+        if clip_range_vf > 0.0 and (value is None or c.values is None):
+            raise ValueError("clip_range_vf needs a critic and collected.values")
+        K, N = int(c.actions.shape[0]), int(c.actions.shape[1])
+        M = K * N
+        n_mb = (M + batch_size - 1) // batch_size
+        if normalize_advantage and M - (n_mb - 1) * batch_size == 1:
+            raise ValueError(f"the last minibatch of {M} rows in batches of {batch_size} would have one row: advantage "
+                             "normalisation needs two (another batch_size, or normalize_advantage=False)")
+        row_ptr, n_rows = self._mlp_rows(policy, c.obs[:K], None)
+        if n_rows != M:
+            raise ValueError("collected.obs must be [K + 1, N, n_obs] for actions [K, N, n_u]")
+        ptr = {}
+        for name, t, tail in (("actions", c.actions, (policy.n_out,)), ("log_prob", c.log_prob, ()), ("advantages", c.advantages, ()),
+                              ("returns", c.returns, ())):
+            if t is None:
+                ptr[name] = 0
+                continue
+            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (K, N) + tail:
+                raise ValueError(f"collected.{name} must be a contiguous float32 {(K, N) + tail} tensor on {self.device}")
+            ptr[name] = t.data_ptr()
+        ptr["values"] = 0
+        if clip_range_vf > 0.0:
+            t = c.values
+            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (K + 1, N):
+                raise ValueError(f"collected.values must be a contiguous float32 {(K + 1, N)} tensor on {self.device}")
+            ptr["values"] = t.data_ptr()
+        opt.load()
+        stats = torch.zeros((n_epochs, n_mb, 12), device=self.device, dtype=torch.float32)
+        self.batch.ppo_update_device(opt.handle, row_ptr, M, batch_size, n_epochs, lr, ptr["actions"], ptr["log_prob"],
+                                     ptr["advantages"], ptr["returns"] if value is not None else 0, stats.data_ptr(),
+                                     opt._six(opt.actor_params), opt.log_std.data_ptr(), opt._six(opt.actor_grads),
+                                     opt.grad_log_std.data_ptr(),
+                                     None if value is None else opt._six(opt.critic_params),
+                                     None if value is None else opt._six(opt.critic_grads),
+                                     clip_range=clip_range, vf_coef=vf_coef, ent_coef=ent_coef,
+                                     normalize_advantage=normalize_advantage, clip_range_vf=clip_range_vf,
+                                     values_old_ptr=ptr["values"], target_kl=target_kl, seed=seed, first_epoch=first_epoch,
+                                     stream=torch.cuda.current_stream().cuda_stream)
+        return stats
+
     @property
     def terminal_observation(self):
         return self._terminal
@@ -552,6 +627,11 @@ class DeviceAdam:
         from ..parallel import _DevArray
         m, v = (torch.as_tensor(_DevArray(ptr, (n,), "<f4"), device=self.env.device).clone() for ptr in (m_ptr, v_ptr))
         return m, v, t
+
+    def steps(self) -> int:
+        """The number of Adam steps taken (dockauv_optim_state).  After a ``ppo_train`` with ``target_kl`` the count is known
+        to the device only: the call then waits for that update's stream and reads it back (8 bytes)."""
+        return self.env.batch.optim_state(self.handle)[3]
 
 
 class ShardedTorchDocking3d:

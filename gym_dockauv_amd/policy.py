@@ -7,7 +7,7 @@ is SB3's ``MlpPolicy``, which train.py:64 instantiates and train.py:64-71 / 86-1
 put it on the device.  An ``MLPPolicy`` with one raw output is a critic (SB3's ``mlp_extractor.value_net`` + ``value_net``;
 ``value_from_torch``, ``make_value``): the PPO collector (dockauv_collect) evaluates it on the rollout's rows.
 ``forward_reference``, ``backward_reference``, ``normals_reference``, ``log_prob_reference``, ``gae_reference``,
-``ppo_head_reference`` and ``adam_reference`` are float64
+``ppo_head_reference``, ``adam_reference`` and ``permutation_reference`` (exact integers) are float64
 NumPy statements of what the kernels compute (for tests and for callers who want to check a port); they are never used as a compute path.
 """
 from __future__ import annotations
@@ -166,14 +166,17 @@ class MLPPolicy:
 
     @staticmethod
     def ppo_head_reference(mean, v, actions, log_prob_old, advantages, returns, log_std, clip_range: float, vf_coef: float,
-                           ent_coef: float, normalize_advantage: bool = True):
+                           ent_coef: float, normalize_advantage: bool = True, clip_range_vf=None, values_old=None):
         """float64 statement of dockauv_ppo_head on one minibatch, every array already gathered: mean, actions [B, n_out];
         v (None: no critic), log_prob_old, advantages, returns [B]; log_std [n_out].  The loss is SB3's: the clipped surrogate
         on advantages normalised with the unbiased standard deviation, vf_coef x the squared value error, ent_coef x the
         negative Gaussian entropy.  Returns (grad_mean [B, n_out], grad_v [B] or None, grad_log_std [n_out], stats [8]):
         d loss / d mean, d loss / d v, d loss / d log_std and (loss, policy_loss, value_loss, entropy_loss, approx_kl,
         clip_fraction, advantage mean, advantage std -- 0 and 1 without normalisation).  Where the two surrogates tie (inside
-        the clip range, and on its edges) the gradient is the unclipped one, as torch.min and clamp give it."""
+        the clip range, and on its edges) the gradient is the unclipped one, as torch.min and clamp give it.
+        ``clip_range_vf`` > 0 with ``values_old`` [B] (dockauv_ppo_update): the value error is taken at v_old + clamp(v - v_old,
+        -c, c), whose gradient with respect to v is 1 for |v - v_old| <= c (the edges included, as torch.clamp's backward
+        gives it) and 0 beyond.  None / 0: the plain squared error."""
         f = lambda x: np.asarray(x, dtype=np.float64)
         mean, a, lpo, adv, ls = f(mean), f(actions), f(log_prob_old).reshape(-1), f(advantages).reshape(-1), f(log_std).reshape(-1)
         B, n_out = mean.shape
@@ -200,8 +203,17 @@ class MLPPolicy:
             v, ret = f(v).reshape(-1), f(returns).reshape(-1)
             if v.shape != (B,) or ret.shape != (B,):
                 raise ValueError("v, returns: [B]")
-            value_loss = float(((ret - v) ** 2).mean())
-            grad_v = 2.0 * vf_coef * (v - ret) / B
+            dv, inside = v - ret, 1.0
+            if clip_range_vf is not None and float(clip_range_vf) > 0.0:
+                if values_old is None:
+                    raise ValueError("clip_range_vf needs values_old")
+                c, vo = float(clip_range_vf), f(values_old).reshape(-1)
+                if vo.shape != (B,):
+                    raise ValueError("values_old: [B]")
+                d = v - vo
+                dv, inside = (vo + np.clip(d, -c, c)) - ret, (np.abs(d) <= c).astype(np.float64)
+            value_loss = float((dv ** 2).mean())
+            grad_v = 2.0 * vf_coef * dv * inside / B
         loss = policy_loss + ent_coef * entropy_loss + vf_coef * value_loss
         stats = np.array([loss, policy_loss, value_loss, entropy_loss, ((ratio - 1.0) - lr).mean(),
                           (np.abs(ratio - 1.0) > clip).mean(), m, s], dtype=np.float64)
@@ -288,6 +300,42 @@ class MLPPolicy:
         u1 = ((x[..., 0] >> np.uint64(8)).astype(np.float64) + 0.5) / 16777216.0
         u2 = (x[..., 1] >> np.uint64(8)).astype(np.float64) / 16777216.0
         return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+
+    @staticmethod
+    def permutation_reference(seed: int, epoch: int, n: int) -> np.ndarray:
+        """The exact statement of dockauv_permutation: int64 [n], out[i] = P(i) for the keyed bijection P of [0, n) -- an
+        eight-round Feistel network on b = max(2, bit_length(n - 1)) bits (left half: the high b // 2 bits) whose round keys
+        are the eight words of the Philox4x32-10 blocks of counters (q, epoch mod 2^32, 0, 3), q = 0, 1, key = seed, applied
+        again while the result is >= n (cycle-walking: the walk stays on the cycle through i < n, so it ends).  Round r with
+        left width w: t = ((R + k_r) mod 2^32) * 0xD2511F53; f = hi32(t) ^ lo32(t); f = (f ^ (f >> 15)) & (2^w - 1);
+        (L, R) = (R, L ^ f), and the widths swap.  Integer arithmetic only: the kernel gives the same bits."""
+        n = int(n)
+        if n < 1 or n > 1 << 31:
+            raise ValueError("n must be in 1 .. 2^31")
+        ctr = np.zeros((2, 4), dtype=np.uint64)
+        ctr[:, 0] = (0, 1)
+        ctr[:, 1] = np.uint64(int(epoch) & 0xFFFFFFFF)
+        ctr[:, 3] = np.uint64(3)
+        keys = _philox4x32_10(ctr, (int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)).reshape(8)
+        b = max(2, (n - 1).bit_length())
+        wl, wr = b // 2, b - b // 2
+
+        def network(x):
+            L, R = x >> np.uint64(wr), x & np.uint64((1 << wr) - 1)
+            w = [wl, wr]
+            for r in range(8):
+                t = ((R + keys[r]) & _MASK) * _M0
+                f = (t >> _S32) ^ (t & _MASK)
+                f = (f ^ (f >> np.uint64(15))) & np.uint64((1 << w[r & 1]) - 1)
+                L, R = R, L ^ f
+            return (L << np.uint64(wr)) | R
+
+        out = network(np.arange(n, dtype=np.uint64))
+        while True:
+            walk = np.nonzero(out >= np.uint64(n))[0]
+            if walk.size == 0:
+                return out.astype(np.int64)
+            out[walk] = network(out[walk])
 
     # ------------------------------------------------------------------------------------------ C ABI
     def shape_desc(self) -> _capi.PolicyDesc:

@@ -591,6 +591,8 @@ int dockauv_ppo_head(dockauv_handle h, dockauv_policy actor, const dockauv_ppo_h
  * the pack (the actor's with the copy of its log_std).
  * Stream capture: the bias corrections are host scalars of the call, so a captured graph would replay ONE step's corrections (and
  * the count would not advance): do not capture the step.
+ * After a dockauv_ppo_update with target_kl > 0 on this optimiser the count is pending (how many of its steps were applied is
+ * known to the device only): the step then first synchronises the stream that update ran on and reads the count back.
  * Refused before any device call (DOCKAUV_E_INVALID, the message naming the field): a NULL handle, optimiser, desc or io; a wrong
  * struct_size; a critic as `actor` or an actor as `critic`; policies of another handle; an actor without log_std; beta1 or beta2
  * outside [0, 1); eps <= 0; lr < 0 or not finite; a NULL among the pointers the shapes require; a non-NULL pointer where the
@@ -622,8 +624,108 @@ typedef struct dockauv_optim_io {
 } dockauv_optim_io;
 int dockauv_optim_step(dockauv_handle h, dockauv_optim o, const dockauv_optim_io* io, void* hip_stream);
 /* The optimiser's state, for inspection and checkpoints: device pointers to m and v ([*n_elements] each, in index-space order,
- * owned by the optimiser and valid until dockauv_optim_destroy) and the number of steps taken.  Any output may be NULL. */
+ * owned by the optimiser and valid until dockauv_optim_destroy) and the number of steps taken.  Any output may be NULL.
+ * While the count is pending (after a dockauv_ppo_update with target_kl > 0) the call first synchronises the stream that update
+ * ran on and reads the count back from the device. */
 int dockauv_optim_state(dockauv_optim o, float** m, float** v, long long* n_elements, long long* steps);
+
+/*
+ * A keyed pseudo-random permutation of 0 .. n - 1 on the device, the shuffle of dockauv_ppo_update (the reference's counterpart:
+ * the np.random.permutation of SB3's RolloutBuffer.get): out[i] = P(i), int64 [n] in device memory, P a bijection of [0, n) that
+ * is a function of (seed, epoch, n) alone.  One launch, one lane per output, no sort and no workspace; asynchronous on the stream.
+ * The construction is the bijective shuffle of Mitchell, Stokes, Frank and Holmes, "Bandwidth-optimal random shuffling for GPUs"
+ * (2022) -- a Feistel network on b bits with cycle-walking --, in exact unsigned integer arithmetic:
+ *   b  = max(2, bit_length(n - 1));  wl = b / 2 (the left half: the HIGH bits);  wr = b - wl
+ *   k_0 .. k_3, k_4 .. k_7 = the words of the Philox4x32-10 blocks of counter (q, epoch mod 2^32, 0, 3), q = 0, 1, key = (seed mod
+ *     2^32, seed >> 32).  Counter word 3 names the stream: the episode generator uses 0, the current's noise 1, the policy's
+ *     exploration noise 2, this permutation 3.
+ *   N(x), x < 2^b:  L = x >> wr;  R = x mod 2^wr;  then eight rounds r = 0 .. 7, w = the width of L (wl in the even rounds, wr in
+ *     the odd ones: the two widths swap with the halves):
+ *       t = ((R + k_r) mod 2^32) * 0xD2511F53            (a 64-bit product)
+ *       f = (t >> 32) ^ (t mod 2^32);  f = (f ^ (f >> 15)) mod 2^w
+ *       (L, R) = (R, L ^ f)
+ *     N(x) = L * 2^wr + R.  Every round is invertible (L ^ f is undone by the same f of R), so N is a bijection of [0, 2^b).
+ *   P(i) = N(i), and while the result is >= n, N of the result again (cycle-walking).
+ * The walk follows the cycle of N that contains i; that cycle returns to i < n, so the loop ends -- a theorem, not a
+ * probability: it has no bound and cannot hang.  2^b < 2 n for n > 2, so a lane applies N fewer than two times on average; the
+ * lanes of a wave walk different lengths and diverge there (the longest walk seen for n <= 100 000: 14 applications, at
+ * n = 4 097).
+ * Refused before any device call, the message naming the field: a NULL handle or out; n < 1; n > 2^31.
+ */
+int dockauv_permutation(dockauv_handle h, uint64_t seed, uint64_t epoch, long long n, int64_t* out, void* hip_stream);
+
+/*
+ * The whole update of a PPO iteration -- SB3's PPO.train (train.py:64-71): n_epochs passes over the collection in shuffled
+ * minibatches -- queued by ONE host call, with no host synchronisation and, after the first call, no allocation.  All pointers
+ * are device pointers, float32; asynchronous on the stream.  M = n_rows, B = batch_size, J = ceil(M / B) minibatches an epoch,
+ * the last one of M - (J - 1) B rows (shorter, as in SB3).
+ *
+ * What one call queues: one launch that starts the optimiser's control block; per epoch e one dockauv_permutation(seed,
+ * first_epoch + e, M) into the optimiser's index buffer; per minibatch j, with row_index = that buffer + j B: the actor's and
+ * the critic's dockauv_policy_forward_rows, the head (dockauv_ppo_head's launches on the same inputs, stats -> columns 0..7),
+ * the actor's and the critic's dockauv_policy_backward into opt.actor_grads / opt.critic_grads (grad_log_std: the head), the
+ * optimiser's launch and the repack of both networks (dockauv_optim_step).  Without target_kl and clip_range_vf every bit is
+ * that of the same calls issued one by one.  The weights the first forward uses are the ones the policies hold at that point of
+ * the stream (dockauv_policy_load, or an earlier step's repack), as for the pieces.
+ *
+ * clip_range_vf > 0 (needs values_old and a critic): the head's rows launch is the same kernel instantiated with the clipped
+ * value loss; for row r, v_old = values_old_i read at the row index, in this float32 order, c = clip_range_vf:
+ *   d = v_r - v_old;  vc = v_old + fminf(fmaxf(d, -c), c);  dv = vc - ret_i
+ *   value_loss = (sum dv * dv) / B
+ *   grad_v[r] = (fabsf(d) <= c) ? ((2.0f * vf_coef) * dv) / (float)B : 0.0f        (the edge included: torch.clamp's backward)
+ * Everything else is dockauv_ppo_head's arithmetic; with clip_range_vf == 0 so is this.
+ *
+ * Adam's count lives on the device for the length of the call: the optimiser owns a control block {t, stop, step_size, rsq},
+ * written by one thread and read by everyone.  The host computes (step_size, rsq) of the steps t0 + 1 .. t0 + n_epochs J in
+ * double exactly as dockauv_optim_step does, t0 the count at the call; the pair of step t0 + 1 + k travels in the kernel
+ * arguments of the k-th minibatch's final-sums launch (applied steps are a prefix of the minibatches, so the k-th minibatch is
+ * either step t0 + 1 + k or not applied; kernel arguments are copied at the call, so two updates queued back to back on one
+ * stream cannot overwrite each other's values).  That launch -- the head's final-sums kernel instantiated for this call --,
+ * after writing approx_kl:
+ *   stop = already stopped || (target_kl > 0 && approx_kl > 1.5f * target_kl)        (float32, the stored statistic: SB3's rule)
+ *   stop:  the flag is set and stays set for the rest of the call
+ *   else:  t = t + 1;  the block's (step_size, rsq) = the launch's pair
+ * and the optimiser's launch -- dockauv_optim_step's kernel instantiated for this call -- takes step_size and rsq from the block
+ * and, with the flag set, leaves p, m and v untouched (the repack after it then packs the same weights again).  So a minibatch
+ * that trips the rule is not applied and neither is anything after it, in this epoch or a later one of the call: SB3's break in
+ * front of optimizer.step() and out of the epochs.  The remaining forwards, heads and backwards still run, on the frozen
+ * weights: that wasted device work is the price of having no host round trip per minibatch.
+ *
+ * The host's count: with target_kl == 0 the call adds n_epochs J to it.  With target_kl > 0 the count is PENDING after the call:
+ * the next dockauv_optim_step, dockauv_optim_state or dockauv_ppo_update on this optimiser first synchronises the stream the
+ * update ran on and reads t back (8 bytes); SB3 synchronises once per minibatch there.
+ *
+ * stats [n_epochs][J][12], per minibatch: columns 0..7 dockauv_ppo_head's statistics (also for the minibatches after a stop; the
+ * one that tripped the rule shows the approx_kl that tripped it, as SB3 logs it); 8, 9: the gradient norm before clipping and
+ * coef (dockauv_optim_step); 10: applied, 1.0f or 0.0f; 11: the Adam step number used, as a float.  Columns 8..11 are 0 where the
+ * minibatch was not applied.
+ *
+ * The optimiser owns the index buffer (int64 [M]), the head's inputs and outputs (mean, v, grad_mean, grad_v of one minibatch)
+ * and the control block: allocated by the first call and grown when a later call needs more (hipMalloc synchronises the device:
+ * make the first call outside a stream capture, as for dockauv_ppo_head, whose workspace rules hold here too).  The bias
+ * corrections are host scalars of the call: do not capture it (dockauv_optim_step).
+ * Refused before any device call, the message naming the field: what dockauv_ppo_head refuses for normalize_advantage, rows,
+ * actions, log_prob_old, advantages, returns, clip_range and the actor, and dockauv_optim_step for opt; n_rows < 1 or > 2^31;
+ * batch_size < 1; n_epochs < 1; a last minibatch of one row with normalize_advantage; clip_range_vf < 0; target_kl < 0;
+ * clip_range_vf > 0 with values_old NULL or without a critic; opt.stats != NULL; a NULL stats; networks whose backward does
+ * not fit a group's LDS (dockauv_policy_backward).
+ */
+typedef struct dockauv_ppo_update_io {
+    uint32_t struct_size;          /* sizeof(dockauv_ppo_update_io): ABI check */
+    int32_t normalize_advantage;
+    const float* rows;             /* packed rows [M][n_obs + 2]: what the actor saw */
+    const float *actions, *log_prob_old, *advantages, *returns, *values_old;   /* [M][n_out], [M] ..; returns NULL without a
+                                      critic; values_old nullable (clip_range_vf) */
+    long long n_rows;              /* M, 1 .. 2^31 */
+    long long batch_size;          /* B >= 1 */
+    int32_t n_epochs;              /* >= 1 */
+    int32_t reserved;
+    uint64_t seed, first_epoch;    /* minibatch j of epoch e: P_{seed, first_epoch + e}[j B .. j B + B) */
+    float clip_range, clip_range_vf, vf_coef, ent_coef, target_kl, reserved1;   /* clip_range > 0; clip_range_vf, target_kl: 0 = off */
+    dockauv_optim_io opt;          /* params, grads (the caller's buffers, as in dockauv_optim_step), lr; stats must be NULL */
+    float* stats;                  /* [n_epochs][J][12] */
+} dockauv_ppo_update_io;
+int dockauv_ppo_update(dockauv_handle h, dockauv_optim o, const dockauv_ppo_update_io* io, void* hip_stream);
 
 /*
  * The episode monitor: what the reference's learner logs about a collection -- rollout/ep_rew_mean, rollout/ep_len_mean and
