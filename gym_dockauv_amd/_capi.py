@@ -118,6 +118,16 @@ class CollectIO(C.Structure):
     ]
 
 
+class TruncationIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_steps", C.c_int32), ("n_slots", C.c_int32),
+        ("gamma", C.c_float), ("gae_lambda", C.c_float), ("reserved", C.c_int32),
+        ("rows_out", C.c_void_p), ("terminal_obs", C.c_void_p), ("values", C.c_void_p),
+        ("length_carry", C.c_void_p), ("trunc_step", C.c_void_p), ("trunc_row", C.c_void_p), ("v_terminal", C.c_void_p),
+        ("advantages", C.c_void_p), ("returns", C.c_void_p),
+    ]
+
+
 class PolicyGrads(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("reserved", C.c_uint32),
@@ -226,6 +236,11 @@ SYMBOLS = [
     ("dockauv_gae", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                               C.c_void_p]),
     ("dockauv_collect", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CollectIO), C.c_void_p]),
+    ("dockauv_truncation_slots", C.c_int, [C.c_void_p, C.c_int]),
+    ("dockauv_truncation_scan", C.c_int, [C.c_void_p, C.POINTER(TruncationIO), C.c_void_p]),
+    ("dockauv_gae_truncated", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(TruncationIO), C.c_void_p]),
+    ("dockauv_collect_truncated", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CollectIO), C.POINTER(TruncationIO),
+                                            C.c_void_p]),
     ("dockauv_policy_forward_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
     ("dockauv_policy_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
                                           C.POINTER(PolicyGrads), C.c_void_p]),

@@ -189,6 +189,69 @@ int gae(dockauv_handle h, const float* rows_out, const float* values, int n_step
     return 0;
 }
 
+// a dockauv_truncation_io against the handle, before any device call; `full`: also what the value launch and GAE touch
+int check_truncation(dockauv_handle h, const dockauv_truncation_io* io, const char* fn, bool full) {
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "%s: io is NULL", fn);
+    if (io->struct_size != sizeof(dockauv_truncation_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_truncation_io));
+    if (io->n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.n_steps: %d must be >= 1", io->n_steps);
+    if (h->cfg.max_timesteps < 1) return fail(h, DOCKAUV_E_INVALID, "%s: the handle's max_timesteps %d must be >= 1", fn, h->cfg.max_timesteps);
+    const int need = truncation_slots(io->n_steps, h->cfg.max_timesteps);
+    if (io->n_slots < need)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.n_slots: %d, dockauv_truncation_slots gives %d for %d steps", io->n_slots, need, io->n_steps);
+    if (!io->rows_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.rows_out is NULL");
+    if (!io->terminal_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.terminal_obs is NULL");
+    if (!io->length_carry) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.length_carry is NULL");
+    if (!io->trunc_step) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.trunc_step is NULL");
+    if (!io->trunc_row) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.trunc_row is NULL");
+    if (full) {
+        if (!io->values) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.values is NULL");
+        if (!io->v_terminal) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.v_terminal is NULL");
+        if (!io->advantages) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.advantages is NULL");
+        if (!io->returns) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.returns is NULL");
+        if (int rc = check_gae_factors(h, "dockauv_truncation_io", io->gamma, io->gae_lambda)) return rc;
+    }
+    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "%s: the packed rows are float32; the handle's precision is DOCKAUV_F64", fn);
+    if (h->cfg.reset_mode == DOCKAUV_RESET_NONE)
+        return fail(h, DOCKAUV_E_INVALID, "%s: the handle's reset_mode is DOCKAUV_RESET_NONE: an episode does not restart at the row "
+                    "after a done", fn);
+    return 0;
+}
+
+int truncation_scan(dockauv_handle h, const dockauv_truncation_io* io, hipStream_t stream) {
+    TruncArgs a{};
+    a.rows = io->rows_out;
+    a.terminal_obs = io->terminal_obs;
+    a.carry_len = io->length_carry;
+    a.trunc_step = io->trunc_step;
+    a.trunc_row = (long long*)io->trunc_row;
+    a.n_steps = io->n_steps;
+    a.n_envs = h->cfg.n_envs;
+    a.n_obs = h->n_obs;
+    a.row_stride = h->n_obs + 2;
+    a.max_timesteps = h->cfg.max_timesteps;
+    a.n_slots = io->n_slots;
+    const int rc = launch_truncation_scan(a, stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "truncation scan launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = stream;
+    return 0;
+}
+
+// the three launches of dockauv_gae_truncated: the scan, V of the slots' terminal observations, GAE with the bootstrap
+int gae_truncated(dockauv_handle h, dockauv_policy critic, const dockauv_truncation_io* io, hipStream_t stream) {
+    if (int rc = truncation_scan(h, io, stream)) return rc;
+    const long n = (long)io->n_slots * (long)h->cfg.n_envs;
+    int rc = launch_policy_forward_rows(critic->S, critic->packed, io->terminal_obs, (const long long*)io->trunc_row, n, h->n_obs,
+                                        io->v_terminal, stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "value kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    rc = launch_gae_truncated(io->rows_out, io->values, io->advantages, io->returns, io->trunc_step, io->v_terminal, io->n_slots,
+                              io->n_steps, h->cfg.n_envs, h->n_obs, io->gamma, io->gae_lambda, stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "GAE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = stream;
+    return 0;
+}
+
 // actor (dockauv_policy_create) or critic (dockauv_value_create): `fn` names the entry point in the messages
 int create_policy(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out, bool value_role, const char* fn) {
     if (!d || !out) return fail(h, DOCKAUV_E_INVALID, "%s: null argument", fn);
@@ -534,6 +597,72 @@ int dockauv_collect(dockauv_handle h, dockauv_policy actor, dockauv_policy criti
         if ((rc = value_forward(h, critic, io->rows_out, (long long)K * (long long)N, io->values + N, stream)) != 0) return rc;
         if ((rc = gae(h, io->rows_out, io->values, K, io->gamma, io->gae_lambda, io->advantages, io->returns, stream)) != 0) return rc;
     }
+    return check_status(h);   // (what dockauv_poll_status looks at: no synchronisation)
+}
+
+int dockauv_truncation_slots(dockauv_handle h, int n_steps) {
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_truncation_slots: null handle");
+    if (n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_slots: n_steps %d must be >= 1", n_steps);
+    if (h->cfg.max_timesteps < 1)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_slots: the handle's max_timesteps %d must be >= 1", h->cfg.max_timesteps);
+    return truncation_slots(n_steps, h->cfg.max_timesteps);
+}
+
+int dockauv_truncation_scan(dockauv_handle h, const dockauv_truncation_io* io, void* hip_stream) {
+    if (int rc = check_truncation(h, io, "dockauv_truncation_scan", false)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return truncation_scan(h, io, (hipStream_t)hip_stream);
+}
+
+int dockauv_gae_truncated(dockauv_handle h, dockauv_policy critic, const dockauv_truncation_io* io, void* hip_stream) {
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_gae_truncated: null handle");
+    if (!critic) return fail(h, DOCKAUV_E_INVALID, "dockauv_gae_truncated: null critic");
+    if (int rc = check_truncation(h, io, "dockauv_gae_truncated", true)) return rc;
+    if (int rc = check_critic(h, critic, "dockauv_gae_truncated")) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return gae_truncated(h, critic, io, (hipStream_t)hip_stream);
+}
+
+int dockauv_collect_truncated(dockauv_handle h, dockauv_policy actor, dockauv_policy critic, const dockauv_collect_io* cio,
+                              const dockauv_truncation_io* tio, void* hip_stream) {
+    const char* fn = "dockauv_collect_truncated";
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
+    if (!actor) return fail(h, DOCKAUV_E_INVALID, "%s: null actor", fn);
+    if (!critic) return fail(h, DOCKAUV_E_INVALID, "%s: null critic (the bootstrap is the critic's value)", fn);
+    if (!cio) return fail(h, DOCKAUV_E_INVALID, "%s: cio is NULL", fn);
+    if (cio->struct_size != sizeof(dockauv_collect_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.struct_size: got %u, library has %zu", cio->struct_size, sizeof(dockauv_collect_io));
+    if (cio->n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.n_steps: %d must be >= 1", cio->n_steps);
+    if (!cio->rows_in || !cio->rows_out || !cio->actions_out)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: rows_in/rows_out/actions_out must not be NULL");
+    if (!cio->terminal_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.terminal_obs is NULL (%s reads it)", fn);
+    if (!cio->values || !cio->advantages || !cio->returns)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: values/advantages/returns must not be NULL with a critic");
+    if (int rc = check_truncation(h, tio, fn, true)) return rc;
+    if (tio->n_steps != cio->n_steps) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.n_steps: %d, dockauv_collect_io's is %d", tio->n_steps, cio->n_steps);
+    if (tio->rows_out != cio->rows_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.rows_out is not dockauv_collect_io's");
+    if (tio->terminal_obs != cio->terminal_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.terminal_obs is not dockauv_collect_io's");
+    if (tio->values != cio->values) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.values is not dockauv_collect_io's");
+    if (tio->advantages != cio->advantages) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.advantages is not dockauv_collect_io's");
+    if (tio->returns != cio->returns) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.returns is not dockauv_collect_io's");
+    if (tio->gamma != cio->gamma) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.gamma: %g, dockauv_collect_io's is %g", (double)tio->gamma, (double)cio->gamma);
+    if (tio->gae_lambda != cio->gae_lambda)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.gae_lambda: %g, dockauv_collect_io's is %g", (double)tio->gae_lambda, (double)cio->gae_lambda);
+    if (int rc = check_actor(h, actor, fn, cio->log_prob != nullptr)) return rc;
+    if (int rc = check_critic(h, critic, fn)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int K = cio->n_steps;
+    const size_t N = (size_t)h->cfg.n_envs;
+    // the steps of every env's episode before step 0: the handle's own counters at this point of the stream (monitor_sync)
+    HIP_TRY(h, hipMemcpyAsync(tio->length_carry, h->B.t_steps, N * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+    h->last_stream = stream;
+    int rc = queue_rollout(h, actor, cio->rows_in, cio->rows_out, cio->actions_out, cio->terminal_obs, cio->log_prob, K, cio->t0,
+                           cio->stochastic, stream);
+    if (rc) return rc;
+    if ((rc = value_forward(h, critic, cio->rows_in, (long long)N, cio->values, stream)) != 0) return rc;
+    if ((rc = value_forward(h, critic, cio->rows_out, (long long)K * (long long)N, cio->values + N, stream)) != 0) return rc;
+    if ((rc = gae_truncated(h, critic, tio, stream)) != 0) return rc;
     return check_status(h);   // (what dockauv_poll_status looks at: no synchronisation)
 }
 

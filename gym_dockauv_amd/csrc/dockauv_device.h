@@ -534,6 +534,30 @@ int launch_policy_backward(const PolicyShape& s, const float* packed, const floa
 int launch_gae(const float* rows, const float* values, float* advantages, float* returns, int n_steps, int n_envs, int n_obs,
                float gamma, float gae_lambda, void* stream);
 
+// ------------------------------------------------------------------------------------------ truncation bootstrap (dockauv_collect.hip)
+// SB3's rewards[idx] += gamma * V(terminal_observation) for the dones that are time limits (include/dockauv.h:
+// dockauv_gae_truncated states the rule and the arithmetic).  The scan finds them -- one lane per env walks k = 0 .. K - 1 with an
+// int32 length carry -- and leaves env's s-th truncated step in slot s of two [n_slots][n_envs] tables: trunc_step (the step, -1
+// in unused slots) and trunc_row (k n_envs + env: the row of terminal_obs, what launch_policy_forward_rows takes as an index; env
+// in unused slots, a row that exists).  A truncated episode has max_timesteps + 1 steps and the carry before step 0 is at most
+// max_timesteps, so an env truncates at most (K - 1) / (max_timesteps + 1) + 1 times in K steps: the slots are the compaction.
+inline int truncation_slots(int n_steps, int max_timesteps) { return n_steps / (max_timesteps + 1) + 1; }
+struct TruncArgs {
+    const float* rows;                    // [K][N][row_stride]; only the done column is read
+    const float* terminal_obs;            // [K][N][n_obs]; columns 0, 6, 7 are read where a done is a time limit by its length
+    int32_t* carry_len;                   // [N], read and written back
+    int32_t* trunc_step;                  // [n_slots][N]
+    long long* trunc_row;                 // [n_slots][N]
+    int n_steps, n_envs, n_obs, row_stride, max_timesteps, n_slots;
+};
+// One launch.  Returns a hipError_t as int.
+int launch_truncation_scan(const TruncArgs& a, void* stream);
+// launch_gae with the bootstrap: at step trunc_step[s][env] the reward is fmaf(gamma, v_terminal[s][env], reward).  The same
+// kernel instantiated on the two tables; without a used slot the bits are launch_gae's.  Returns a hipError_t as int.
+int launch_gae_truncated(const float* rows, const float* values, float* advantages, float* returns, const int32_t* trunc_step,
+                         const float* v_terminal, int n_slots, int n_steps, int n_envs, int n_obs, float gamma, float gae_lambda,
+                         void* stream);
+
 // ------------------------------------------------------------------------------------------ PPO head (dockauv_head.hip)
 // Loss terms, statistics and the gradients on the networks' raw outputs and on log_std for one minibatch (include/dockauv.h:
 // dockauv_ppo_head states the arithmetic).  Groups of kHeadThreads lanes on the backward's bounded grid (kBwdMaxGroups); a lane

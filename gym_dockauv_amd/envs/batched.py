@@ -720,6 +720,68 @@ class BatchedDocking3d:
                                        C.c_void_p(stream or None))
         _capi.check(self._lib, self._handle, rc, "dockauv_collect")
 
+    def truncation_slots(self, n_steps: int) -> int:
+        """Slots per env that hold every time-limit truncation of ``n_steps`` steps (dockauv_truncation_slots):
+        n_steps // (max_timesteps + 1) + 1."""
+        n = self._lib.dockauv_truncation_slots(self._handle, int(n_steps))
+        if n < 1:
+            _capi.check(self._lib, self._handle, n, "dockauv_truncation_slots")
+        return int(n)
+
+    def _truncation_io(self, n_steps: int, n_slots: int, rows_out_ptr: int, terminal_obs_ptr: int, length_carry_ptr: int,
+                       trunc_step_ptr: int, trunc_row_ptr: int, values_ptr: int = 0, v_terminal_ptr: int = 0,
+                       advantages_ptr: int = 0, returns_ptr: int = 0, gamma: float = 0.0, gae_lambda: float = 0.0):
+        io = _capi.TruncationIO()
+        io.struct_size = C.sizeof(_capi.TruncationIO)
+        io.n_steps, io.n_slots = int(n_steps), int(n_slots)
+        io.gamma, io.gae_lambda = float(gamma), float(gae_lambda)
+        io.rows_out, io.terminal_obs, io.values = rows_out_ptr or None, terminal_obs_ptr or None, values_ptr or None
+        io.length_carry, io.trunc_step, io.trunc_row = length_carry_ptr or None, trunc_step_ptr or None, trunc_row_ptr or None
+        io.v_terminal, io.advantages, io.returns = v_terminal_ptr or None, advantages_ptr or None, returns_ptr or None
+        return io
+
+    def truncation_scan_device(self, rows_out_ptr: int, terminal_obs_ptr: int, n_steps: int, n_slots: int, length_carry_ptr: int,
+                               trunc_step_ptr: int, trunc_row_ptr: int, stream: int = 0) -> None:
+        """The time-limit truncations inside rows_out [K][N][n_obs + 2] (dockauv_truncation_scan): env's s-th truncated step ->
+        trunc_step int32 [n_slots][N] (-1: unused) and its terminal_obs row -> trunc_row int64 [n_slots][N]; length_carry int32
+        [N] is read (steps of every env's episode before step 0) and written back.  Asynchronous."""
+        io = self._truncation_io(n_steps, n_slots, rows_out_ptr, terminal_obs_ptr, length_carry_ptr, trunc_step_ptr, trunc_row_ptr)
+        rc = self._lib.dockauv_truncation_scan(self._handle, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_truncation_scan")
+
+    def gae_truncated_device(self, value, rows_out_ptr: int, terminal_obs_ptr: int, values_ptr: int, n_steps: int, n_slots: int,
+                             gamma: float, gae_lambda: float, length_carry_ptr: int, trunc_step_ptr: int, trunc_row_ptr: int,
+                             v_terminal_ptr: int, advantages_ptr: int, returns_ptr: int, stream: int = 0) -> None:
+        """``gae_device`` with SB3's truncation bootstrap (dockauv_gae_truncated): the scan of ``truncation_scan_device``, V of
+        the truncated steps' terminal observations -> v_terminal float32 [n_slots][N], then GAE with reward + gamma *
+        v_terminal at those steps.  Asynchronous."""
+        io = self._truncation_io(n_steps, n_slots, rows_out_ptr, terminal_obs_ptr, length_carry_ptr, trunc_step_ptr, trunc_row_ptr,
+                                 values_ptr, v_terminal_ptr, advantages_ptr, returns_ptr, gamma, gae_lambda)
+        rc = self._lib.dockauv_gae_truncated(self._handle, value.ptr, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_gae_truncated")
+
+    def collect_truncated_device(self, policy, value, rows_in_ptr: int, rows_out_ptr: int, actions_out_ptr: int, n_steps: int,
+                                 n_slots: int, terminal_obs_ptr: int, values_ptr: int, advantages_ptr: int, returns_ptr: int,
+                                 length_carry_ptr: int, trunc_step_ptr: int, trunc_row_ptr: int, v_terminal_ptr: int,
+                                 gamma: float = 0.99, gae_lambda: float = 0.95, t0: int = 0, stochastic: bool = True,
+                                 stream: int = 0, log_prob_ptr: int = 0) -> None:
+        """``collect_device`` with the truncation bootstrap (dockauv_collect_truncated): length_carry <- the handle's step
+        counters, the rollout, the two value launches, then ``gae_truncated_device``'s three launches in place of the GAE
+        launch.  Needs a critic and terminal_obs.  Asynchronous; raises like poll_status()."""
+        cio = _capi.CollectIO()
+        cio.struct_size = C.sizeof(_capi.CollectIO)
+        cio.n_steps = int(n_steps)
+        cio.rows_in, cio.rows_out, cio.actions_out = rows_in_ptr or None, rows_out_ptr or None, actions_out_ptr or None
+        cio.terminal_obs, cio.log_prob = terminal_obs_ptr or None, log_prob_ptr or None
+        cio.values, cio.advantages, cio.returns = values_ptr or None, advantages_ptr or None, returns_ptr or None
+        cio.t0, cio.stochastic = int(t0), 1 if stochastic else 0
+        cio.gamma, cio.gae_lambda = float(gamma), float(gae_lambda)
+        tio = self._truncation_io(n_steps, n_slots, rows_out_ptr, terminal_obs_ptr, length_carry_ptr, trunc_step_ptr, trunc_row_ptr,
+                                  values_ptr, v_terminal_ptr, advantages_ptr, returns_ptr, gamma, gae_lambda)
+        rc = self._lib.dockauv_collect_truncated(self._handle, policy.ptr, value.ptr if value is not None else None, C.byref(cio),
+                                                 C.byref(tio), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_collect_truncated")
+
     def policy_forward_rows_device(self, policy, rows_ptr: int, n_rows: int, out_ptr: int, index_ptr: int = 0, stream: int = 0) -> None:
         """The MLP's output before its output activation, without noise, for any rows (dockauv_policy_forward_rows; an actor or
         a critic): rows float32 packed rows [n_obs + 2], index int64 [n_rows] or 0 (row r is rows[index[r]]), out float32

@@ -199,7 +199,7 @@ class TorchDocking3d:
         return rows[:, :, : self.n_obs], acts, rows[:, :, self.n_obs], rows[:, :, self.n_obs + 1] > 0.5
 
     def collect(self, policy, value, n_steps: int, gamma: float, gae_lambda: float, stochastic: bool = True,
-                want_terminal_obs: bool = False, monitor=None):
+                want_terminal_obs: bool = False, monitor=None, bootstrap_truncated: bool = False):
         """One PPO iteration's collection queued by ONE host call (dockauv_collect) on the current stream: ``rollout`` plus
         log pi(a|s), V(s) of the K + 1 observation sets and GAE.  Continues the trajectory exactly as ``rollout`` does.  Returns
         a ``Collected`` named tuple of views of buffers the env owns (reused by the next ``collect`` of the same K):
@@ -209,11 +209,20 @@ class TorchDocking3d:
         ``value`` None: rollout and log-probabilities only).
         ``monitor`` (``make_monitor``): forces ``want_terminal_obs`` and queues the episode scan of these K steps -- with the
         explained variance of ``values`` / ``returns`` when there is a critic -- behind the collection on the same stream;
-        ``monitor.stats`` holds the result.  Without it no launch is added and none is changed."""
+        ``monitor.stats`` holds the result.  Without it no launch is added and none is changed.
+        ``bootstrap_truncated``: SB3's truncation bootstrap (dockauv_collect_truncated) -- where an episode ends on the time
+        limit and on nothing else (the monitor's outcome 3), advantages and returns are those of reward + gamma *
+        V(terminal observation) at that step; reward, values and log_prob are what they are without it.  Forces
+        ``want_terminal_obs`` and needs a critic; the tuple keeps its fields.  With the default not one launch is added or
+        changed."""
         torch = self.torch
         K = int(n_steps)
         if K < 1:
             raise ValueError("n_steps must be >= 1")
+        if bootstrap_truncated:
+            if value is None:
+                raise ValueError("bootstrap_truncated needs a critic: the bootstrap is its value of the terminal observation")
+            want_terminal_obs = True
         if monitor is not None:
             want_terminal_obs = True
             self._monitor_before(monitor)
@@ -232,12 +241,27 @@ class TorchDocking3d:
         has_v = value is not None
         values, adv, ret = (bufs["values"], bufs["adv"], bufs["ret"]) if has_v else (None, None, None)
         logp = bufs["logp"] if (policy.has_log_std and policy.shape.out_act == _capi.ACT_NONE) else None
-        self.batch.collect_device(policy, value, rows[0].data_ptr(), rows[1].data_ptr(), bufs["acts"].data_ptr(), K, gamma=gamma,
-                                  gae_lambda=gae_lambda, t0=self._t, stochastic=stochastic,
-                                  stream=torch.cuda.current_stream().cuda_stream,
-                                  terminal_obs_ptr=term.data_ptr() if term is not None else 0, log_prob_ptr=0 if logp is None else logp.data_ptr(),
-                                  values_ptr=values.data_ptr() if has_v else 0, advantages_ptr=adv.data_ptr() if has_v else 0,
-                                  returns_ptr=ret.data_ptr() if has_v else 0)
+        if bootstrap_truncated:
+            ws = bufs.get("trunc")
+            if ws is None:      # the four workspaces of dockauv_truncation_io, once per K
+                S = self.batch.truncation_slots(K)
+                ws = bufs["trunc"] = dict(slots=S, carry=torch.zeros((N,), device=self.device, dtype=torch.int32),
+                                          step=torch.zeros((S, N), device=self.device, dtype=torch.int32),
+                                          row=torch.zeros((S, N), device=self.device, dtype=torch.int64),
+                                          v=torch.zeros((S, N), device=self.device, dtype=torch.float32))
+            self.batch.collect_truncated_device(policy, value, rows[0].data_ptr(), rows[1].data_ptr(), bufs["acts"].data_ptr(), K,
+                                                ws["slots"], term.data_ptr(), values.data_ptr(), adv.data_ptr(), ret.data_ptr(),
+                                                ws["carry"].data_ptr(), ws["step"].data_ptr(), ws["row"].data_ptr(),
+                                                ws["v"].data_ptr(), gamma=gamma, gae_lambda=gae_lambda, t0=self._t,
+                                                stochastic=stochastic, stream=torch.cuda.current_stream().cuda_stream,
+                                                log_prob_ptr=0 if logp is None else logp.data_ptr())
+        else:
+            self.batch.collect_device(policy, value, rows[0].data_ptr(), rows[1].data_ptr(), bufs["acts"].data_ptr(), K, gamma=gamma,
+                                      gae_lambda=gae_lambda, t0=self._t, stochastic=stochastic,
+                                      stream=torch.cuda.current_stream().cuda_stream,
+                                      terminal_obs_ptr=term.data_ptr() if term is not None else 0, log_prob_ptr=0 if logp is None else logp.data_ptr(),
+                                      values_ptr=values.data_ptr() if has_v else 0, advantages_ptr=adv.data_ptr() if has_v else 0,
+                                      returns_ptr=ret.data_ptr() if has_v else 0)
         self._t += K
         self._gen += 1
         self._last_rows = rows[K]

@@ -87,6 +87,47 @@ def episode_scan_reference(rows_reward, rows_done, carry_return, carry_length, m
                 stats=stats)
 
 
+def truncation_slots(n_steps: int, max_timesteps: int) -> int:
+    """dockauv_truncation_slots: slots per env that hold every truncated step of ``n_steps`` steps.  A truncated episode has
+    exactly max_timesteps + 1 steps and the carry before step 0 is at most max_timesteps, so an env truncates at most
+    (n_steps - 1) // (max_timesteps + 1) + 1 times; the bound returned is n_steps // (max_timesteps + 1) + 1, never less."""
+    if int(n_steps) < 1 or int(max_timesteps) < 1:
+        raise ValueError("n_steps and max_timesteps must be >= 1")
+    return int(n_steps) // (int(max_timesteps) + 1) + 1
+
+
+def truncation_scan_reference(rows_done, carry_length, max_timesteps, terminal_obs, n_slots=None):
+    """NumPy statement of dockauv_truncation_scan, defined through ``episode_scan_reference`` so that the rule stays in one place:
+    a step is truncated iff its ``ep_outcome`` is 3 -- a time limit with no lower bit set, so a goal reached or an attitude
+    limit hit on the last allowed step is terminal.  rows_done [K, N]; carry_length int32 [N] (each at most max_timesteps);
+    terminal_obs [K, N, n_obs]; n_slots: None = ``truncation_slots(K, max_timesteps)``.
+
+    Returns a dict: ``truncated`` bool [K, N]; ``trunc_step`` int32 [n_slots, N], env's truncated steps in order, padded with
+    -1; ``trunc_row`` int64 [n_slots, N], k * N + env of those steps (the row of terminal_obs), env in unused slots;
+    ``carry_length`` int32 [N], the new carry."""
+    d = np.asarray(rows_done) > 0.5
+    if d.ndim != 2:
+        raise ValueError("rows_done: [K, N]")
+    K, N = d.shape
+    need = truncation_slots(K, max_timesteps)
+    n_slots = need if n_slots is None else int(n_slots)
+    if n_slots < need:
+        raise ValueError(f"n_slots {n_slots} is below truncation_slots = {need}")
+    res = episode_scan_reference(np.zeros((K, N), np.float32), d, np.zeros(N, np.float32), carry_length, max_timesteps,
+                                 terminal_obs=terminal_obs)
+    truncated = d & (res["ep_outcome"] == 3)
+    count = truncated.sum(axis=0)
+    if np.all(np.asarray(carry_length).reshape(-1) <= int(max_timesteps)):
+        assert int(count.max(initial=0)) <= (K - 1) // (int(max_timesteps) + 1) + 1 <= need, "the slot bound does not hold"
+    step = np.full((n_slots, N), -1, dtype=np.int32)
+    row = np.tile(np.arange(N, dtype=np.int64), (n_slots, 1))
+    for env in range(N):
+        ks = np.flatnonzero(truncated[:, env])[:n_slots]
+        step[: ks.size, env] = ks
+        row[: ks.size, env] = ks.astype(np.int64) * N + env
+    return dict(truncated=truncated, trunc_step=step, trunc_row=row, carry_length=res["carry_length"])
+
+
 def explained_variance_reference(values, returns) -> float:
     """SB3's explained_variance on a collection, as dockauv_monitor_scan forms it: y = returns [K, N], e = y - values[:K] (the
     subtraction in float32), 1 - var(e) / var(y) in float64; NaN when var(y) is 0."""

@@ -146,16 +146,29 @@ class MLPPolicy:
         return (-0.5 * z * z - ls - 0.5 * np.log(2.0 * np.pi)).sum(axis=-1)
 
     @staticmethod
-    def gae_reference(reward, done, values, gamma: float, gae_lambda: float):
+    def gae_reference(reward, done, values, gamma: float, gae_lambda: float, truncated=None, v_terminal=None):
         """SB3's RolloutBuffer.compute_returns_and_advantage in float64: reward, done [K, N]; values [K + 1, N] with values[k] =
         V of the observation step k acted on and values[K] = V of the last one; every done is terminal.  Returns
-        (advantages [K, N], returns [K, N])."""
+        (advantages [K, N], returns [K, N]).
+        ``truncated`` bool [K, N] with ``v_terminal`` [K, N] (both or neither; dockauv_gae_truncated): where a step is done and
+        truncated its reward is reward + gamma * v_terminal, as SB3's collect_rollouts adds gamma * V(terminal_observation) for
+        ``TimeLimit.truncated``; the done stays a done (the advantage does not cross the reset).  ``v_terminal`` is read nowhere
+        else."""
         r = np.asarray(reward, dtype=np.float64)
         nt = 1.0 - (np.asarray(done) > 0.5).astype(np.float64)
         v = np.asarray(values, dtype=np.float64)
         K = r.shape[0]
         if v.shape[0] != K + 1 or nt.shape != r.shape or v.shape[1:] != r.shape[1:]:
             raise ValueError("reward, done: [K, N]; values: [K + 1, N]")
+        if (truncated is None) != (v_terminal is None):
+            raise ValueError("truncated and v_terminal: both or neither")
+        if truncated is not None:
+            tr = np.asarray(truncated).astype(bool) & (nt == 0.0)
+            vt = np.asarray(v_terminal, dtype=np.float64)
+            if tr.shape != r.shape or vt.shape != r.shape:
+                raise ValueError("truncated, v_terminal: [K, N]")
+            r = r.copy()
+            r[tr] = r[tr] + gamma * vt[tr]
         adv = np.zeros_like(r)
         gae = np.zeros(r.shape[1:], dtype=np.float64)
         for k in range(K - 1, -1, -1):

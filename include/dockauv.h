@@ -431,7 +431,8 @@ int dockauv_policy_forward_logp(dockauv_handle h, dockauv_policy p, const float*
  *   gae   = fmaf((gamma * gae_lambda) * nt, gae, delta)
  *   advantages[k] = gae;  returns[k] = gae + values[k]
  * Every done is terminal: the reference's env reports no truncation flag (docking3d.py:630), and the row after a done holds the
- * reset observation, whose value is masked out by nt.  gamma and gae_lambda must lie in [0, 1]. */
+ * reset observation, whose value is masked out by nt (dockauv_gae_truncated, below, bootstraps the dones that are time limits).
+ * gamma and gae_lambda must lie in [0, 1]. */
 int dockauv_gae(dockauv_handle h, const float* rows_out, const float* values, int n_steps, float gamma, float gae_lambda,
                 float* advantages, float* returns, void* hip_stream);
 /* One PPO iteration's collection. */
@@ -457,6 +458,72 @@ typedef struct dockauv_collect_io {
  * what dockauv_poll_status returns, looked at once after queueing. */
 int dockauv_collect(dockauv_handle h, dockauv_policy actor, dockauv_policy critic, const dockauv_collect_io* io,
                     void* hip_stream);
+
+/*
+ * The truncation bootstrap of SB3's collect_rollouts: where an episode ends on the time limit and on nothing else
+ * (infos[idx]["TimeLimit.truncated"]), rewards[idx] += gamma * V(terminal_observation).  The reference's env has no such flag
+ * (docking3d.py:630) and dockauv_gae treats every done as terminal; in this env time is not part of the observation, so that
+ * teaches the critic that a state is worth nothing whenever the clock runs out.  These calls are the opt-in alternative, computed
+ * on the device from what a collection already holds; without them every call queues exactly what it queued before.
+ *
+ * A done at step k is TRUNCATED iff the episode monitor gives it outcome 3 (dockauv_monitor_scan: the same float32 comparisons on
+ * the clipped terminal observation t, the same length carry):
+ *   len > max_timesteps  and not  (t[0] == 0.0f || t[0] == 1.0f || fabsf(t[6]) == 1.0f || fabsf(t[7]) == 1.0f)
+ * so a goal reached or an attitude limit hit on the last allowed step is terminal, and the two limits of the monitor's rule hold
+ * here too.  len is the monitor's: length_carry + the steps so far, zero after every done.
+ *
+ * Slots.  A truncated episode has exactly max_timesteps + 1 steps and the carry before step 0 is at most max_timesteps, so an
+ * env truncates at most (K - 1) / (max_timesteps + 1) + 1 times in K steps.  dockauv_truncation_slots returns
+ * n_slots = K / (max_timesteps + 1) + 1 (never less; 1 at the default 1000 for K = 128; -1 for a NULL handle or K < 1).  The scan
+ * writes env's s-th truncated step, in step order, to slot s of two tables laid out [n_slots][n_envs]:
+ *   trunc_step[s][env] = k                      (-1 in unused slots)
+ *   trunc_row[s][env]  = k * n_envs + env       (the row of terminal_obs; env in unused slots: a row that exists)
+ * and writes the new length carry back.  No atomics and no compaction pass: the per-env slots are the compaction.
+ *
+ * dockauv_truncation_scan: that scan alone, one launch.  Needs rows_out, terminal_obs, length_carry, trunc_step, trunc_row.
+ * dockauv_gae_truncated: three launches -- the scan; the critic on the n_slots * n_envs rows terminal_obs[trunc_row[.]] ->
+ *   v_terminal [n_slots][n_envs] (the kernel of dockauv_policy_forward_rows with a row stride of n_obs: a row's value is a
+ *   function of the row and the weights only, bit for bit dockauv_value_forward on the same observation; values of unused slots
+ *   are unspecified and never used); GAE with the bootstrap.  Per env, backwards as dockauv_gae, in exactly this float32 order:
+ *     nt    = done[k] > 0.5f ? 0.0f : 1.0f
+ *     gnt   = gamma * nt
+ *     rb    = k == trunc_step[s][env] for a slot s ? fmaf(gamma, v_terminal[s][env], reward[k]) : reward[k]
+ *     delta = fmaf(gnt, values[k + 1], rb) - values[k]          (nt = 0 there, as for any done: gae does not cross the reset)
+ *     gae   = fmaf((gamma * gae_lambda) * nt, gae, delta)
+ *     advantages[k] = gae;  returns[k] = gae + values[k]
+ *   Without a truncated step the bits are dockauv_gae's.  The reward columns, values and log-probabilities are not touched (the
+ *   monitor's returns stay sums of raw rewards, as SB3's Monitor wrapper sees them).
+ * dockauv_collect_truncated: dockauv_collect with dockauv_gae_truncated's three launches in place of the GAE launch; in front of
+ *   the rollout, on the stream, length_carry <- the handle's own step counters (DOCKAUV_F_TSTEPS; a device-to-device copy, as
+ *   dockauv_monitor_sync reads them).  The critic and cio->terminal_obs are required; n_steps, rows_out, terminal_obs, values,
+ *   advantages, returns, gamma and gae_lambda of the two blocks must agree.
+ * All pointers are device pointers, the workspaces belong to the caller, no call allocates, every call is asynchronous on the
+ * stream.  Refused before any device call (DOCKAUV_E_INVALID, the message naming the field): a NULL handle, critic, io or required
+ * pointer; a wrong struct_size; n_steps < 1; n_slots below dockauv_truncation_slots; a handle whose max_timesteps is < 1; gamma
+ * or gae_lambda outside [0, 1]; a float64 handle; a handle with DOCKAUV_RESET_NONE (an episode does not restart at the row after
+ * a done); an actor passed as critic.
+ */
+typedef struct dockauv_truncation_io {
+    uint32_t struct_size;          /* sizeof(dockauv_truncation_io): ABI check */
+    int32_t n_steps;               /* K >= 1 */
+    int32_t n_slots;               /* >= dockauv_truncation_slots(h, K) */
+    float gamma, gae_lambda;       /* in [0, 1] */
+    int32_t reserved;
+    const float* rows_out;         /* [K][n_envs][n_obs + 2]: the reward and done columns are read */
+    const float* terminal_obs;     /* [K][n_envs][n_obs]: read where done (the scan: columns 0, 6, 7; the critic: all) */
+    const float* values;           /* [K + 1][n_envs] (dockauv_gae) */
+    int32_t* length_carry;         /* [n_envs] workspace: steps of every env's episode before step 0; the scan writes it back */
+    int32_t* trunc_step;           /* [n_slots][n_envs] workspace */
+    int64_t* trunc_row;            /* [n_slots][n_envs] workspace */
+    float* v_terminal;             /* [n_slots][n_envs] workspace */
+    float* advantages;             /* [K][n_envs] */
+    float* returns;                /* [K][n_envs] */
+} dockauv_truncation_io;
+int dockauv_truncation_slots(dockauv_handle h, int n_steps);
+int dockauv_truncation_scan(dockauv_handle h, const dockauv_truncation_io* io, void* hip_stream);
+int dockauv_gae_truncated(dockauv_handle h, dockauv_policy critic, const dockauv_truncation_io* io, void* hip_stream);
+int dockauv_collect_truncated(dockauv_handle h, dockauv_policy actor, dockauv_policy critic, const dockauv_collect_io* cio,
+                              const dockauv_truncation_io* tio, void* hip_stream);
 
 /*
  * The network's share of the update (PPO.train of train.py:64-71: the MlpPolicy forward on a minibatch and autograd's backward

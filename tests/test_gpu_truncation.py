@@ -1,0 +1,444 @@
+"""The truncation bootstrap on a real MI355X (include/dockauv.h: dockauv_truncation_scan, dockauv_gae_truncated,
+dockauv_collect_truncated; TorchDocking3d.collect(bootstrap_truncated=True)).  Crafted inputs without stepping (the table of
+tests/test_truncation_host.py: crafted): the slots and the carry exactly, the values of the truncated terminal observations bit
+for bit dockauv_value_forward's, advantages against float64 under the bound of the GAE tests, bit for bit dockauv_gae where
+nothing truncates, and which advantages a terminal observation reaches.  A real collection against its twin and against the call
+issued by hand.  Refusals on a live handle.  Every batch is closed in `finally`."""
+import copy
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+MT = 9
+GAMMA_LAMBDA = [(0.99, 0.95), (1.0, 1.0), (0.99, 0.0)]
+
+
+def Cc():
+    """the helpers of the collector tests: P (make_mlp, env_for, FANS), make_critic, gae_float32_numpy, bits, stream_of, SENTINEL"""
+    from tests import test_gpu_collect
+    return test_gpu_collect
+
+
+def Hh():
+    """the crafted table of the host tests"""
+    from tests import test_truncation_host
+    return test_truncation_host
+
+
+def trunc_env(n_obs, n_envs, max_timesteps=MT):
+    """fan_env of the policy tests (n_u = 6) with a time limit of `max_timesteps`"""
+    from gym_dockauv_amd.config.env_config import BASE_CONFIG
+    from gym_dockauv_amd.envs.batched import BatchedDocking3d
+    cfg = copy.deepcopy(BASE_CONFIG)
+    cfg["radar"].update(Cc().P().FANS[n_obs])
+    cfg["max_timesteps"] = max_timesteps
+    env = BatchedDocking3d(cfg, num_envs=n_envs, scenario="ObstaclesDocking3d", device=0, precision="f32", reset_mode="device",
+                           device_seed=7, rng="batched")
+    assert (env.n_observations, env.n_u) == (n_obs, 6)
+    return env
+
+
+def inputs(K, N, n_obs, seed, max_timesteps=MT):
+    """crafted dones / carries / terminal observations plus rewards U(-1, 1), values U(-2, 2) and rows whose observation columns
+    are NaN"""
+    done, carry, term = Hh().crafted(K, N, n_obs, seed, max_timesteps)
+    rng = np.random.default_rng(seed + 1)
+    reward = rng.uniform(-1, 1, (K, N)).astype(np.float32)
+    values = rng.uniform(-2, 2, (K + 1, N)).astype(np.float32)
+    rows = np.full((K, N, n_obs + 2), np.nan, dtype=np.float32)
+    rows[:, :, n_obs] = reward
+    rows[:, :, n_obs + 1] = done
+    return dict(K=K, N=N, n_obs=n_obs, done=done, carry=carry, term=term, reward=reward, values=values, rows=rows)
+
+
+def run(torch, env, val, x, gamma, lam, n_slots=None, scan_only=False):
+    """dockauv_gae_truncated (or the scan alone) with one sentinel row behind every output and workspace; the rows must stay"""
+    c = Cc()
+    K, N = x["K"], x["N"]
+    S = env.truncation_slots(K) if n_slots is None else n_slots
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    rows, term, values = dev(x["rows"]), dev(x["term"]), dev(x["values"])
+    carry = torch.full((2 * N,), -7, device="cuda", dtype=torch.int32)
+    carry[:N] = dev(x["carry"])
+    step = torch.full((S + 1, N), -7, device="cuda", dtype=torch.int32)
+    row = torch.full((S + 1, N), -7, device="cuda", dtype=torch.int64)
+    vt = torch.full((S + 1, N), c.SENTINEL, device="cuda")
+    adv = torch.full((K + 1, N), c.SENTINEL, device="cuda")
+    ret = torch.full((K + 1, N), c.SENTINEL, device="cuda")
+    if scan_only:
+        env.truncation_scan_device(rows.data_ptr(), term.data_ptr(), K, S, carry.data_ptr(), step.data_ptr(), row.data_ptr(),
+                                   stream=c.stream_of(torch))
+    else:
+        env.gae_truncated_device(val, rows.data_ptr(), term.data_ptr(), values.data_ptr(), K, S, gamma, lam, carry.data_ptr(),
+                                 step.data_ptr(), row.data_ptr(), vt.data_ptr(), adv.data_ptr(), ret.data_ptr(),
+                                 stream=c.stream_of(torch))
+    torch.cuda.synchronize()
+    assert bool((carry[N:] == -7).all()) and bool((step[S] == -7).all()) and bool((row[S] == -7).all()), "a workspace's guard row changed"
+    if scan_only:
+        assert bool((vt == c.SENTINEL).all()) and bool((adv == c.SENTINEL).all()) and bool((ret == c.SENTINEL).all())
+    else:
+        assert bool((vt[S] == c.SENTINEL).all()) and bool((adv[K] == c.SENTINEL).all()) and bool((ret[K] == c.SENTINEL).all())
+    return dict(S=S, carry=carry[:N].cpu().numpy(), step=step[:S].cpu().numpy(), row=row[:S].cpu().numpy(), vt=vt[:S].cpu().numpy(),
+                adv=adv[:K].cpu().numpy(), ret=ret[:K].cpu().numpy(), term_dev=term)
+
+
+def scatter_v_terminal(out, K, N):
+    """(truncated bool [K, N], v_terminal float32 [K, N]: the device's values at the used slots, NaN elsewhere)"""
+    truncated = np.zeros((K, N), dtype=bool)
+    vt = np.full((K, N), np.nan, dtype=np.float32)
+    s, env = np.nonzero(out["step"] >= 0)
+    truncated[out["step"][s, env], env] = True
+    vt[out["step"][s, env], env] = out["vt"][s, env]
+    return truncated, vt
+
+
+def reference_and_bound(x, truncated, vt, gamma, lam):
+    """(float64 advantages, bound): 8 x the error of the plain-float32 NumPy restatement -- gae_float32_numpy on the rewards with
+    the one extra multiply-add --, floor 4 ulp of max |advantage|: gae_reference_and_bound of the collector tests"""
+    from gym_dockauv_amd.policy import MLPPolicy
+    ref, _ = MLPPolicy.gae_reference(x["reward"], x["done"], x["values"], gamma, lam, truncated=truncated, v_terminal=vt)
+    rb = x["reward"].copy()
+    rb[truncated] = x["reward"][truncated] + np.float32(gamma) * vt[truncated]
+    assert rb.dtype == np.float32
+    f32, _ = Cc().gae_float32_numpy(rb, x["done"], x["values"], gamma, lam)
+    floor = 4.0 * float(np.spacing(np.float32(np.abs(ref).max())))
+    return ref, max(8.0 * float(np.abs(f32.astype(np.float64) - ref).max()), floor)
+
+
+@pytest.mark.parametrize("N", [1, 63, 257])
+@pytest.mark.parametrize("n_obs", [20, 25], ids=["n_obs20-8byte", "n_obs25-4byte"])
+def test_scan_values_and_gae_on_crafted_inputs(n_obs, N):
+    """K in {1, 2, 67} (67: no multiple of the chunk of 8, more than one, 7 slots); env 0 fills every slot, env 1 never truncates"""
+    import torch
+    from gym_dockauv_amd.monitor import truncation_scan_reference
+    c = Cc()
+    critic = c.make_critic(n_obs, (64, 64))
+    env = trunc_env(n_obs, N)
+    try:
+        val = env.make_value(critic)
+        for K in (1, 2, 67):
+            x = inputs(K, N, n_obs, seed=100 * K + N)
+            want = truncation_scan_reference(x["done"], x["carry"], MT, x["term"])
+            assert want["trunc_step"].shape[0] == env.truncation_slots(K) == K // (MT + 1) + 1
+            assert (want["trunc_step"][:, 0] >= 0).all() and (N < 2 or (want["trunc_step"][:, 1] == -1).all())
+            alone = run(torch, env, val, x, 0.99, 0.95, scan_only=True)
+            packed_values = None
+            for gamma, lam in GAMMA_LAMBDA:
+                out = run(torch, env, val, x, gamma, lam)
+                for o in (alone, out):
+                    assert np.array_equal(o["step"], want["trunc_step"]), (K, "trunc_step")
+                    assert np.array_equal(o["row"], want["trunc_row"]), (K, "trunc_row")
+                    assert np.array_equal(o["carry"], want["carry_length"]), (K, "carry")
+                truncated, vt = scatter_v_terminal(out, K, N)
+                assert np.array_equal(truncated, want["truncated"])
+                n_used = int(truncated.sum())
+                if packed_values is None and n_used:
+                    # the same terminal observations as packed rows (reward / done columns NaN) through dockauv_value_forward
+                    ks, es = np.nonzero(truncated)
+                    packed = torch.full((n_used, n_obs + 2), float("nan"), device="cuda")
+                    packed[:, :n_obs] = out["term_dev"][torch.from_numpy(ks).cuda(), torch.from_numpy(es).cuda()]
+                    packed_values = c.values_of(torch, env, val, packed).cpu().numpy()
+                if n_used:
+                    assert not np.isnan(vt[truncated]).any()
+                    assert np.array_equal(vt[truncated].view(np.int32), packed_values.view(np.int32)), "v_terminal is not dockauv_value_forward's"
+                adv, ret = out["adv"], out["ret"]
+                assert not np.isnan(adv).any() and not np.isnan(ret).any(), "NaN: an unused slot or a row that is not done got in"
+                assert np.array_equal(ret.view(np.int32), (adv + x["values"][:K]).view(np.int32))
+                ref, bound = reference_and_bound(x, truncated, vt, gamma, lam)
+                err = float(np.abs(adv.astype(np.float64) - ref).max())
+                print(f"gae_truncated n_obs {n_obs} N {N} K {K} gamma {gamma} lambda {lam}: {n_used} truncations, device {err:.3e}, "
+                      f"bound {bound:.3e}")
+                assert err <= bound, (K, gamma, lam, err, bound)
+    finally:
+        env.close()
+
+
+@pytest.mark.parametrize("n_obs", [20, 25])
+def test_without_a_truncation_the_bits_are_dockauv_gaes(n_obs):
+    """the same rows on a handle whose time limit (1000) no episode reaches: every slot unused, advantages and returns bit for
+    bit those of dockauv_gae"""
+    import torch
+    c = Cc()
+    N = 257
+    env = trunc_env(n_obs, N, max_timesteps=1000)
+    try:
+        val = env.make_value(c.make_critic(n_obs, (64, 64)))
+        for K in (2, 67):
+            x = inputs(K, N, n_obs, seed=7 * K)
+            assert env.truncation_slots(K) == 1 and int(x["done"].sum()) > (N if K == 67 else 0)
+            for gamma, lam in GAMMA_LAMBDA:
+                out = run(torch, env, val, x, gamma, lam)
+                assert (out["step"] == -1).all() and np.array_equal(out["row"][0], np.arange(N))
+                adv, ret = c.run_gae(torch, env, x["rows"], x["values"], K, N, gamma, lam)
+                assert np.array_equal(out["adv"].view(np.int32), adv.view(np.int32))
+                assert np.array_equal(out["ret"].view(np.int32), ret.view(np.int32))
+            # more slots than the bound asks for change nothing
+            wide = run(torch, env, val, x, 0.99, 0.95, n_slots=3)
+            narrow = run(torch, env, val, x, 0.99, 0.95)
+            assert np.array_equal(wide["adv"].view(np.int32), narrow["adv"].view(np.int32)) and (wide["step"] == -1).all()
+    finally:
+        env.close()
+
+
+def test_a_terminal_observation_reaches_its_own_segment_only():
+    """Another terminal observation (the words of the rule kept) at the truncated steps changes the advantages of exactly the
+    steps of the episode segments that end there, inside the window; at the dones that are not truncated it changes no bit."""
+    import torch
+    c = Cc()
+    K, N, n_obs, gamma, lam = 67, 257, 20, 0.99, 0.95
+    env = trunc_env(n_obs, N)
+    try:
+        val = env.make_value(c.make_critic(n_obs, (64, 64)))
+        x = inputs(K, N, n_obs, seed=3)
+        base = run(torch, env, val, x, gamma, lam)
+        truncated, _ = scatter_v_terminal(base, K, N)
+        other = x["done"] & ~truncated
+        assert int(truncated.sum()) > N and int(other.sum()) > N
+        rng = np.random.default_rng(8)
+
+        def redrawn(where):
+            y = dict(x)
+            t = x["term"].copy()
+            fresh = rng.uniform(-0.9, 0.9, (int(where.sum()), n_obs)).astype(np.float32)
+            fresh[:, [0, 6, 7]] = t[where][:, [0, 6, 7]]
+            t[where] = fresh
+            y["term"] = t
+            return y
+        # the steps of the segments that end at a truncated step: walk back from it to the step after the previous done
+        reached = np.zeros((K, N), dtype=bool)
+        for k, e in zip(*np.nonzero(truncated)):
+            j = k
+            while j >= 0 and (j == k or not x["done"][j, e]):
+                reached[j, e] = True
+                j -= 1
+        a = run(torch, env, val, redrawn(truncated), gamma, lam)
+        changed = a["adv"].view(np.int32) != base["adv"].view(np.int32)
+        assert np.array_equal(changed, reached), (int(changed.sum()), int(reached.sum()))
+        assert np.array_equal(a["step"], base["step"])
+        b = run(torch, env, val, redrawn(other), gamma, lam)
+        assert np.array_equal(b["adv"].view(np.int32), base["adv"].view(np.int32))
+        assert np.array_equal(b["ret"].view(np.int32), base["ret"].view(np.int32))
+        assert np.array_equal(b["vt"].view(np.int32)[base["step"] >= 0], base["vt"].view(np.int32)[base["step"] >= 0])
+    finally:
+        env.close()
+
+
+# ------------------------------------------------------------------------------------------------------- a real collection
+def test_collect_with_the_bootstrap_against_its_twin():
+    """Config 3, 64 + 6 envs, max_timesteps 9, K = 35 (4 slots), two envs built alike.  The test relies on -- and asserts -- at
+    least N truncated episodes per collection and an env with two or more: within 10 steps of 0.1 s hardly any episode of this
+    scenario ends on anything but the clock."""
+    import torch
+    import bench
+    from gym_dockauv_amd import _capi
+    from gym_dockauv_amd.envs.torch_env import TorchDocking3d
+    from gym_dockauv_amd.monitor import truncation_scan_reference
+    from tests import test_gpu_update as U
+    c = Cc()
+    N, K, gamma, lam = 64 + 6, 35, 0.99, 0.95
+    wl = bench.workload(3, N)
+    cfg = copy.deepcopy(wl["cfg"])
+    cfg["max_timesteps"] = MT
+    actor_mlp, critic_mlp = U.mlps()
+
+    def make():
+        env = TorchDocking3d(cfg, num_envs=N, scenario=wl["scenario"], device_seed=9)
+        env.batch._gen = np.random.default_rng(5)
+        env.reset()
+        return env
+    ea, eb = make(), make()
+    try:
+        pa, pb = [e.make_policy(actor_mlp, seed=3) for e in (ea, eb)]
+        va, vb = [e.make_value(critic_mlp) for e in (ea, eb)]
+        S = eb.batch.truncation_slots(K)
+        assert S == 4
+        with pytest.raises(ValueError, match="critic"):
+            ea.collect(pa, None, K, gamma, lam, bootstrap_truncated=True)
+        total = 0
+        for it in range(2):
+            carry = eb.batch.get_field(_capi.F_TSTEPS).reshape(-1).astype(np.int32)   # (synchronises: before the collect)
+            assert np.array_equal(carry, ea.batch.get_field(_capi.F_TSTEPS).reshape(-1).astype(np.int32))
+            ca = ea.collect(pa, va, K, gamma, lam, bootstrap_truncated=True)
+            cb = eb.collect(pb, vb, K, gamma, lam, want_terminal_obs=True)
+            torch.cuda.synchronize()
+            for name in ("obs", "actions", "reward", "log_prob", "values"):
+                assert torch.equal(c.bits(getattr(ca, name)), c.bits(getattr(cb, name))), (it, name)
+            assert torch.equal(ca.done, cb.done)
+            ta, tb = ea.rollout_terminal_observation, eb.rollout_terminal_observation
+            assert torch.equal(c.bits(ta)[ca.done], c.bits(tb)[cb.done])
+            # dockauv_gae_truncated by hand on the plain collection's buffers
+            rows = eb._collect_bufs[K]["rows"]
+            d_carry = torch.from_numpy(carry).cuda()
+            step = torch.zeros((S, N), device="cuda", dtype=torch.int32)
+            row = torch.zeros((S, N), device="cuda", dtype=torch.int64)
+            vt, adv, ret = torch.zeros((S, N), device="cuda"), torch.zeros((K, N), device="cuda"), torch.zeros((K, N), device="cuda")
+            eb.batch.gae_truncated_device(vb, rows[1].data_ptr(), tb.data_ptr(), cb.values.data_ptr(), K, S, gamma, lam,
+                                          d_carry.data_ptr(), step.data_ptr(), row.data_ptr(), vt.data_ptr(), adv.data_ptr(),
+                                          ret.data_ptr(), stream=c.stream_of(torch))
+            torch.cuda.synchronize()
+            assert torch.equal(c.bits(ca.advantages), c.bits(adv)) and torch.equal(c.bits(ca.returns), c.bits(ret)), it
+            assert not torch.equal(c.bits(ca.advantages), c.bits(cb.advantages))
+            ws = ea._collect_bufs[K]["trunc"]
+            assert torch.equal(ws["step"], step) and torch.equal(ws["row"], row) and torch.equal(ws["carry"], d_carry)
+            # the carries after the scan are the handle's counters: the next collect continues them
+            assert np.array_equal(d_carry.cpu().numpy(), eb.batch.get_field(_capi.F_TSTEPS).reshape(-1).astype(np.int32))
+            want = truncation_scan_reference(cb.done.cpu().numpy(), carry, MT, tb.cpu().numpy())
+            assert np.array_equal(step.cpu().numpy(), want["trunc_step"])
+            count = (want["trunc_step"] >= 0).sum(axis=0)
+            assert int(count.sum()) >= N and int(count.max()) >= 2, (it, int(count.sum()), int(count.max()))
+            total += int(count.sum())
+            if it == 1:
+                # an episode that began in the first collection and ends on the clock in the second: at step max_timesteps - carry
+                spans = (carry > 0) & (want["trunc_step"][0] == MT - carry)
+                first_done = cb.done.cpu().numpy().argmax(axis=0)
+                assert int(spans.sum()) >= 1 and np.array_equal(first_done[spans], (MT - carry)[spans])
+        assert total >= 2 * N
+        # the result feeds the update unchanged
+        nets = U.learner(torch, actor_mlp, critic_mlp)
+        opt = U.optimizer(ea, pa, va, nets)
+        stats = ea.ppo_train(opt, ca, 1, 512, 3e-4, seed=1, **U.KW)
+        torch.cuda.synchronize()
+        assert not torch.isnan(stats[..., :8]).any() and opt.steps() == (K * N + 511) // 512
+    finally:
+        ea.close()
+        eb.close()
+
+
+def test_collect_with_the_bootstrap_and_a_monitor():
+    """monitor= keeps working: its scan runs behind the collection, sees raw rewards, and its explained variance is that of the
+    bootstrapped returns"""
+    import torch
+    import bench
+    from gym_dockauv_amd.envs.torch_env import TorchDocking3d
+    from gym_dockauv_amd.monitor import explained_variance_reference
+    from tests import test_gpu_update as U
+    N, K = 70, 35
+    wl = bench.workload(3, N)
+    cfg = copy.deepcopy(wl["cfg"])
+    cfg["max_timesteps"] = MT
+    actor_mlp, critic_mlp = U.mlps()
+    env = TorchDocking3d(cfg, num_envs=N, scenario=wl["scenario"], device_seed=9)
+    try:
+        env.batch._gen = np.random.default_rng(5)
+        env.reset()
+        pol, val = env.make_policy(actor_mlp, seed=3), env.make_value(critic_mlp)
+        mon = env.make_monitor()
+        col = env.collect(pol, val, K, 0.99, 0.95, monitor=mon, bootstrap_truncated=True)
+        s = mon.summary()
+        assert s["n_episodes"] >= N and s["time_limit_rate"] > 0.5
+        want = explained_variance_reference(col.values.cpu().numpy(), col.returns.cpu().numpy())
+        assert abs(s["train/explained_variance"] - want) <= 1e-9 * max(1.0, abs(want))
+    finally:
+        env.close()
+
+
+# ------------------------------------------------------------------------------------------------------- refusals
+def test_refusals_on_a_live_handle():
+    import torch
+    import bench
+    from gym_dockauv_amd import _capi
+    from gym_dockauv_amd.envs.batched import BatchedDocking3d
+    lib = _capi.load_library()
+    c = Cc()
+    p = c.P()
+    K, N = 12, 64
+    z = lambda *shape, dtype=torch.float32: torch.zeros(shape, device="cuda", dtype=dtype)
+
+    def tio_for(env, **over):
+        S = 2
+        keep = [z(K, N, 22), z(K, N, 20), z(K + 1, N), z(N, dtype=torch.int32), z(S, N, dtype=torch.int32), z(S, N, dtype=torch.int64),
+                z(S, N), z(K, N), z(K, N)]
+        io = _capi.TruncationIO()
+        io.struct_size = C.sizeof(_capi.TruncationIO)
+        io.n_steps, io.n_slots, io.gamma, io.gae_lambda = K, S, 0.99, 0.95
+        for name, t in zip(("rows_out", "terminal_obs", "values", "length_carry", "trunc_step", "trunc_row", "v_terminal", "advantages",
+                            "returns"), keep):
+            setattr(io, name, t.data_ptr())
+        for k, v in over.items():
+            setattr(io, k, v)
+        io._keep = keep
+        return io
+
+    critic = c.make_critic(20, (64, 64))
+    mlp = p.make_mlp((20, (64, 64), 6, "tanh", "none"), seed=1, log_std=np.full(6, -0.5))
+    wl = bench.workload(3, N)
+    # a float64 handle, DOCKAUV_RESET_NONE, max_timesteps 0: the handle's own properties
+    e64 = p.env_for(20, 6, N, max_timesteps=MT, precision="f64")
+    none = BatchedDocking3d(copy.deepcopy(wl["cfg"]), num_envs=N, scenario=wl["scenario"], device=0, precision="f32", reset_mode="none",
+                            rng="batched")
+    zero = p.env_for(20, 6, N, max_timesteps=0)
+    try:
+        fake = C.c_void_p(8)   # never dereferenced: the calls are refused first
+        for env, needle in ((e64, b"DOCKAUV_F64"), (none, b"DOCKAUV_RESET_NONE"), (zero, b"max_timesteps")):
+            io = tio_for(env, n_slots=K + 1)
+            assert lib.dockauv_truncation_scan(env._handle, C.byref(io), None) == -1 and needle in lib.dockauv_last_error(env._handle), needle
+            assert lib.dockauv_gae_truncated(env._handle, fake, C.byref(io), None) == -1 and needle in lib.dockauv_last_error(env._handle), needle
+        assert lib.dockauv_truncation_slots(zero._handle, K) == -1 and b"max_timesteps" in lib.dockauv_last_error(zero._handle)
+    finally:
+        e64.close()
+        none.close()
+        zero.close()
+    env = p.env_for(20, 6, N, max_timesteps=MT)
+    try:
+        pol, val = env.make_policy(mlp), env.make_value(critic)
+        h = env._handle
+        err = lambda: lib.dockauv_last_error(h)
+        assert lib.dockauv_truncation_slots(h, K) == 2 and lib.dockauv_truncation_slots(h, 9) == 1 and lib.dockauv_truncation_slots(h, 10) == 2
+        assert lib.dockauv_truncation_slots(h, 0) == -1 and b"n_steps" in err()
+        scan = lambda io: lib.dockauv_truncation_scan(h, C.byref(io) if io is not None else None, None)
+        full = lambda io, crit=val: lib.dockauv_gae_truncated(h, crit.ptr if crit is not None else None, C.byref(io) if io is not None else None, None)
+        assert scan(None) == -1 and b"io is NULL" in err()
+        assert full(None) == -1 and b"io is NULL" in err()
+        assert full(tio_for(env), None) == -1 and b"null critic" in err()
+        assert full(tio_for(env), pol) == -1 and b"not a critic" in err()
+        assert scan(tio_for(env, struct_size=8)) == -1 and b"dockauv_truncation_io.struct_size" in err()
+        assert scan(tio_for(env, n_steps=0)) == -1 and b"dockauv_truncation_io.n_steps" in err()
+        assert scan(tio_for(env, n_slots=1)) == -1 and b"dockauv_truncation_io.n_slots" in err()
+        for name in ("rows_out", "terminal_obs", "length_carry", "trunc_step", "trunc_row"):
+            assert scan(tio_for(env, **{name: None})) == -1 and f"dockauv_truncation_io.{name} is NULL".encode() in err(), name
+            assert full(tio_for(env, **{name: None})) == -1 and f"dockauv_truncation_io.{name} is NULL".encode() in err(), name
+        for name in ("values", "v_terminal", "advantages", "returns"):
+            assert full(tio_for(env, **{name: None})) == -1 and f"dockauv_truncation_io.{name} is NULL".encode() in err(), name
+        assert scan(tio_for(env, values=None, v_terminal=None, advantages=None, returns=None)) == 0      # (the scan needs none of them)
+        assert full(tio_for(env, gamma=1.5)) == -1 and b"gamma" in err()
+        assert full(tio_for(env, gae_lambda=-0.1)) == -1 and b"gae_lambda" in err()
+
+        # dockauv_collect_truncated
+        rows0, acts, logp = z(N, 22), z(K, N, 6), z(K, N)
+
+        def collect(tio, actor=pol, crit=val, **over):
+            cio = _capi.CollectIO()
+            cio.struct_size = C.sizeof(_capi.CollectIO)
+            cio.n_steps = K
+            cio.rows_in, cio.actions_out, cio.log_prob = rows0.data_ptr(), acts.data_ptr(), logp.data_ptr()
+            for name in ("rows_out", "terminal_obs", "values", "advantages", "returns"):
+                setattr(cio, name, getattr(tio, name))
+            cio.gamma, cio.gae_lambda, cio.stochastic = 0.99, 0.95, 1
+            for k, v in over.items():
+                setattr(cio, k, v)
+            return lib.dockauv_collect_truncated(h, actor.ptr if actor is not None else None, crit.ptr if crit is not None else None,
+                                                 C.byref(cio), C.byref(tio), None)
+        assert collect(tio_for(env), crit=None) == -1 and b"null critic" in err()
+        assert collect(tio_for(env), actor=None) == -1 and b"null actor" in err()
+        assert collect(tio_for(env), crit=pol) == -1 and b"not a critic" in err()
+        assert collect(tio_for(env), actor=val) == -1 and b"is a critic" in err()
+        assert collect(tio_for(env), terminal_obs=None) == -1 and b"dockauv_collect_io.terminal_obs" in err()
+        assert collect(tio_for(env), struct_size=8) == -1 and b"dockauv_collect_io.struct_size" in err()
+        assert collect(tio_for(env), n_steps=K - 1) == -1 and b"dockauv_truncation_io.n_steps" in err()
+        assert collect(tio_for(env), gamma=0.9) == -1 and b"dockauv_truncation_io.gamma" in err()
+        assert collect(tio_for(env), values=rows0.data_ptr()) == -1 and b"dockauv_truncation_io.values" in err()
+        assert collect(tio_for(env, n_slots=1)) == -1 and b"dockauv_truncation_io.n_slots" in err()
+        assert lib.dockauv_collect_truncated(h, pol.ptr, val.ptr, None, C.byref(tio_for(env)), None) == -1 and b"cio is NULL" in err()
+        # ... and the handle is usable afterwards
+        good = tio_for(env)
+        assert collect(good) == 0
+        torch.cuda.synchronize()
+        env.poll_status()
+        adv = good._keep[7]
+        assert float(adv.abs().max()) > 0 and not torch.isnan(adv).any()
+        assert int((good._keep[4] >= 0).sum()) >= N // 2      # K = 12 steps from a reset: most envs reach the limit at step 9
+    finally:
+        env.close()
