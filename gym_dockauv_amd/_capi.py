@@ -188,6 +188,13 @@ class MonitorIO(C.Structure):
     ]
 
 
+class RewnormIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_steps", C.c_int32), ("training", C.c_int32), ("reserved", C.c_int32),
+        ("rows_out", C.c_void_p), ("reward_norm", C.c_void_p), ("discounted", C.c_void_p), ("step_stats", C.c_void_p),
+    ]
+
+
 # every symbol include/dockauv.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("dockauv_abi_version", C.c_int, []),
@@ -257,6 +264,15 @@ SYMBOLS = [
     ("dockauv_monitor_sync", C.c_int, [C.c_void_p, C.c_void_p]),
     ("dockauv_monitor_scan", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MonitorIO), C.c_void_p]),
     ("dockauv_monitor_carry", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ("dockauv_rewnorm_create", C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_double, C.POINTER(C.c_void_p)]),
+    ("dockauv_rewnorm_destroy", C.c_int, [C.c_void_p]),
+    ("dockauv_rewnorm_state", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ("dockauv_rewnorm_reset", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("dockauv_rewnorm_scan", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RewnormIO), C.c_void_p]),
+    ("dockauv_gae_normalized", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TruncationIO), C.c_void_p, C.c_void_p,
+                                         C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("dockauv_collect_normalized", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CollectIO), C.POINTER(TruncationIO),
+                                             C.c_void_p, C.POINTER(RewnormIO), C.c_void_p]),
 ]
 
 _lib: Optional[C.CDLL] = None

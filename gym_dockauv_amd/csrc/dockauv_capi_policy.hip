@@ -1,6 +1,6 @@
 // dockauv_capi_policy.hip -- C ABI of libdockauv.so (include/dockauv.h), second part: MLP policy and critic, closed-loop
-// rollout, PPO collector, backward, head, optimiser and episode monitor.  The kernels are in dockauv_policy / _collect /
-// _backward / _head / _optim / _monitor / _update.hip.
+// rollout, PPO collector, backward, head, optimiser, episode monitor and reward normaliser.  The kernels are in dockauv_policy /
+// _collect / _backward / _head / _optim / _monitor / _update / _rewnorm.hip.
 #include <cmath>
 #include <cstring>
 
@@ -45,6 +45,14 @@ struct dockauv_monitor_s {
     float* carry_ret = nullptr;   // [n_envs]: the running return of every env's episode
     int32_t* carry_len = nullptr; // [n_envs]: its length so far
     double* ws = nullptr;         // monitor_workspace_doubles(n_envs): the scan's partials, then the explained variance's
+};
+
+struct dockauv_rewnorm_s {
+    dockauv_handle h = nullptr;
+    float gamma = 0.0f, clip_reward = 0.0f;
+    double epsilon = 0.0;
+    float* carry = nullptr;       // [n_envs]: the discounted return of every env
+    double* state = nullptr;      // [4]: running mean, var, count, reserved
 };
 
 namespace {
@@ -249,6 +257,84 @@ int gae_truncated(dockauv_handle h, dockauv_policy critic, const dockauv_truncat
                               io->n_steps, h->cfg.n_envs, h->n_obs, io->gamma, io->gae_lambda, stream);
     if (rc != 0) return fail(h, DOCKAUV_E_HIP, "GAE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     h->last_stream = stream;
+    return 0;
+}
+
+// a dockauv_rewnorm_io on its own, before any device call and before the handle is looked at
+int check_rewnorm_io(dockauv_handle h, const dockauv_rewnorm_io* io, const char* fn) {
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "%s: the dockauv_rewnorm_io is NULL", fn);
+    if (io->struct_size != sizeof(dockauv_rewnorm_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_rewnorm_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_rewnorm_io));
+    if (io->n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_rewnorm_io.n_steps: %d must be >= 1", io->n_steps);
+    if (!io->rows_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_rewnorm_io.rows_out is NULL");
+    if (!io->reward_norm) return fail(h, DOCKAUV_E_INVALID, "dockauv_rewnorm_io.reward_norm is NULL");
+    if (io->training && !io->discounted) return fail(h, DOCKAUV_E_INVALID, "dockauv_rewnorm_io.discounted is NULL (required when training)");
+    if (io->training && !io->step_stats) return fail(h, DOCKAUV_E_INVALID, "dockauv_rewnorm_io.step_stats is NULL (required when training)");
+    return 0;
+}
+
+// handle and normaliser of `fn`, after the argument blocks
+int check_rewnorm(dockauv_handle h, dockauv_rewnorm rn, const char* fn) {
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
+    if (!rn) return fail(h, DOCKAUV_E_INVALID, "%s: null normaliser", fn);
+    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "%s: the packed rows are float32; the handle's precision is DOCKAUV_F64", fn);
+    if (rn->h != h) return fail(h, DOCKAUV_E_INVALID, "%s: the normaliser was created for another handle", fn);
+    return 0;
+}
+
+int rewnorm_scan(dockauv_handle h, dockauv_rewnorm rn, const dockauv_rewnorm_io* io, hipStream_t stream) {
+    RewnormArgs a{};
+    a.rows = io->rows_out;
+    a.carry = rn->carry;
+    a.state = rn->state;
+    a.discounted = io->discounted;
+    a.reward_norm = io->reward_norm;
+    a.step_stats = io->step_stats;
+    a.n_steps = io->n_steps;
+    a.n_envs = h->cfg.n_envs;
+    a.n_obs = h->n_obs;
+    a.row_stride = h->n_obs + 2;
+    a.training = io->training ? 1 : 0;
+    a.gamma = rn->gamma;
+    a.clip_reward = rn->clip_reward;
+    a.epsilon = rn->epsilon;
+    const int rc = launch_rewnorm_scan(a, stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "reward normalisation launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = stream;
+    return 0;
+}
+
+// GAE on the column; tio != nullptr: the scan and the value launch of gae_truncated in front of it
+int gae_normalized(dockauv_handle h, dockauv_policy critic, const float* reward_norm, const dockauv_truncation_io* tio,
+                   const float* rows_out, const float* values, int n_steps, float gamma, float gae_lambda, float* advantages,
+                   float* returns, hipStream_t stream) {
+    int rc;
+    if (tio) {
+        if ((rc = truncation_scan(h, tio, stream)) != 0) return rc;
+        const long n = (long)tio->n_slots * (long)h->cfg.n_envs;
+        rc = launch_policy_forward_rows(critic->S, critic->packed, tio->terminal_obs, (const long long*)tio->trunc_row, n, h->n_obs,
+                                        tio->v_terminal, stream);
+        if (rc != 0) return fail(h, DOCKAUV_E_HIP, "value kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    rc = launch_gae_column(rows_out, reward_norm, values, advantages, returns, tio ? tio->trunc_step : nullptr,
+                           tio ? tio->v_terminal : nullptr, tio ? tio->n_slots : 0, n_steps, h->cfg.n_envs, h->n_obs, gamma,
+                           gae_lambda, stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "GAE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = stream;
+    return 0;
+}
+
+// what a truncation block must share with a collect block (dockauv_collect_truncated, dockauv_collect_normalized)
+int check_truncation_matches(dockauv_handle h, const dockauv_truncation_io* tio, const dockauv_collect_io* cio) {
+    if (tio->n_steps != cio->n_steps) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.n_steps: %d, dockauv_collect_io's is %d", tio->n_steps, cio->n_steps);
+    if (tio->rows_out != cio->rows_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.rows_out is not dockauv_collect_io's");
+    if (tio->terminal_obs != cio->terminal_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.terminal_obs is not dockauv_collect_io's");
+    if (tio->values != cio->values) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.values is not dockauv_collect_io's");
+    if (tio->advantages != cio->advantages) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.advantages is not dockauv_collect_io's");
+    if (tio->returns != cio->returns) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.returns is not dockauv_collect_io's");
+    if (tio->gamma != cio->gamma) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.gamma: %g, dockauv_collect_io's is %g", (double)tio->gamma, (double)cio->gamma);
+    if (tio->gae_lambda != cio->gae_lambda)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.gae_lambda: %g, dockauv_collect_io's is %g", (double)tio->gae_lambda, (double)cio->gae_lambda);
     return 0;
 }
 
@@ -639,15 +725,7 @@ int dockauv_collect_truncated(dockauv_handle h, dockauv_policy actor, dockauv_po
     if (!cio->values || !cio->advantages || !cio->returns)
         return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: values/advantages/returns must not be NULL with a critic");
     if (int rc = check_truncation(h, tio, fn, true)) return rc;
-    if (tio->n_steps != cio->n_steps) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.n_steps: %d, dockauv_collect_io's is %d", tio->n_steps, cio->n_steps);
-    if (tio->rows_out != cio->rows_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.rows_out is not dockauv_collect_io's");
-    if (tio->terminal_obs != cio->terminal_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.terminal_obs is not dockauv_collect_io's");
-    if (tio->values != cio->values) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.values is not dockauv_collect_io's");
-    if (tio->advantages != cio->advantages) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.advantages is not dockauv_collect_io's");
-    if (tio->returns != cio->returns) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.returns is not dockauv_collect_io's");
-    if (tio->gamma != cio->gamma) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.gamma: %g, dockauv_collect_io's is %g", (double)tio->gamma, (double)cio->gamma);
-    if (tio->gae_lambda != cio->gae_lambda)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.gae_lambda: %g, dockauv_collect_io's is %g", (double)tio->gae_lambda, (double)cio->gae_lambda);
+    if (int rc = check_truncation_matches(h, tio, cio)) return rc;
     if (int rc = check_actor(h, actor, fn, cio->log_prob != nullptr)) return rc;
     if (int rc = check_critic(h, critic, fn)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1012,6 +1090,152 @@ int dockauv_monitor_scan(dockauv_handle h, dockauv_monitor m, const dockauv_moni
     if (rc != 0) return fail(h, DOCKAUV_E_HIP, "monitor launch failed: %s", hipGetErrorString((hipError_t)rc));
     h->last_stream = (hipStream_t)hip_stream;
     return 0;
+}
+
+int dockauv_rewnorm_create(dockauv_handle h, float gamma, float clip_reward, double epsilon, dockauv_rewnorm* out) {
+    if (!out) return fail(h, DOCKAUV_E_INVALID, "dockauv_rewnorm_create: out is NULL");
+    *out = nullptr;
+    if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail(h, DOCKAUV_E_INVALID, "dockauv_rewnorm_create: gamma %g outside [0, 1]", (double)gamma);
+    if (!(clip_reward > 0.0f)) return fail(h, DOCKAUV_E_INVALID, "dockauv_rewnorm_create: clip_reward %g must be > 0", (double)clip_reward);
+    if (!(epsilon >= 0.0)) return fail(h, DOCKAUV_E_INVALID, "dockauv_rewnorm_create: epsilon %g must be >= 0", epsilon);
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_rewnorm_create: null handle");
+    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "dockauv_rewnorm_create: the packed rows are float32; the handle's precision is DOCKAUV_F64");
+    HIP_TRY(h, hipSetDevice(h->device));
+    dockauv_rewnorm rn = new dockauv_rewnorm_s();
+    rn->h = h;
+    rn->gamma = gamma;
+    rn->clip_reward = clip_reward;
+    rn->epsilon = epsilon;
+    hipError_t e = hipMalloc((void**)&rn->carry, (size_t)h->cfg.n_envs * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&rn->state, 4 * sizeof(double));
+    if (e != hipSuccess) {
+        dockauv_rewnorm_destroy(rn);
+        return fail(h, DOCKAUV_E_HIP, "reward normaliser buffers: %s", hipGetErrorString(e));
+    }
+    const int rc = launch_rewnorm_reset(rn->carry, rn->state, h->cfg.n_envs, nullptr);
+    if (rc != 0) {
+        dockauv_rewnorm_destroy(rn);
+        return fail(h, DOCKAUV_E_HIP, "reward normaliser reset launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    e = hipStreamSynchronize(nullptr);   // (the object is usable on any stream on return)
+    if (e != hipSuccess) {
+        dockauv_rewnorm_destroy(rn);
+        return fail(h, DOCKAUV_E_HIP, "reward normaliser reset: %s", hipGetErrorString(e));
+    }
+    *out = rn;
+    return 0;
+}
+
+int dockauv_rewnorm_destroy(dockauv_rewnorm rn) {
+    if (!rn) return 0;
+    if (rn->h) (void)hipSetDevice(rn->h->device);
+    (void)hipDeviceSynchronize();
+    if (rn->carry) (void)hipFree(rn->carry);
+    if (rn->state) (void)hipFree(rn->state);
+    delete rn;
+    return 0;
+}
+
+int dockauv_rewnorm_state(dockauv_rewnorm rn, double** state, float** carry) {
+    if (!rn) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_rewnorm_state: null normaliser");
+    if (state) *state = rn->state;
+    if (carry) *carry = rn->carry;
+    return 0;
+}
+
+int dockauv_rewnorm_reset(dockauv_rewnorm rn, void* hip_stream) {
+    if (!rn) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_rewnorm_reset: null normaliser");
+    dockauv_handle h = rn->h;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = launch_rewnorm_reset(rn->carry, rn->state, h->cfg.n_envs, hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "reward normaliser reset launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
+    return 0;
+}
+
+int dockauv_rewnorm_scan(dockauv_handle h, dockauv_rewnorm rn, const dockauv_rewnorm_io* io, void* hip_stream) {
+    const char* fn = "dockauv_rewnorm_scan";
+    if (int rc = check_rewnorm_io(h, io, fn)) return rc;
+    if (int rc = check_rewnorm(h, rn, fn)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return rewnorm_scan(h, rn, io, (hipStream_t)hip_stream);
+}
+
+int dockauv_gae_normalized(dockauv_handle h, dockauv_policy critic, const float* reward_norm, const dockauv_truncation_io* tio,
+                           const float* rows_out, const float* values, int n_steps, float gamma, float gae_lambda,
+                           float* advantages, float* returns, void* hip_stream) {
+    const char* fn = "dockauv_gae_normalized";
+    if (!reward_norm) return fail(h, DOCKAUV_E_INVALID, "%s: reward_norm is NULL", fn);
+    if (!rows_out || !values || !advantages || !returns)
+        return fail(h, DOCKAUV_E_INVALID, "%s: rows_out/values/advantages/returns must not be NULL", fn);
+    if (n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "%s: n_steps %d must be >= 1", fn, n_steps);
+    if (int rc = check_gae_factors(h, fn, gamma, gae_lambda)) return rc;
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
+    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "%s: the packed rows are float32; the handle's precision is DOCKAUV_F64", fn);
+    if (tio) {
+        if (!critic) return fail(h, DOCKAUV_E_INVALID, "%s: null critic (the bootstrap is the critic's value)", fn);
+        if (int rc = check_truncation(h, tio, fn, true)) return rc;
+        if (tio->n_steps != n_steps) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.n_steps: %d, %s's is %d", tio->n_steps, fn, n_steps);
+        if (tio->rows_out != rows_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.rows_out is not %s's", fn);
+        if (tio->values != values) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.values is not %s's", fn);
+        if (tio->advantages != advantages) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.advantages is not %s's", fn);
+        if (tio->returns != returns) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.returns is not %s's", fn);
+        if (tio->gamma != gamma) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.gamma: %g, %s's is %g", (double)tio->gamma, fn, (double)gamma);
+        if (tio->gae_lambda != gae_lambda)
+            return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.gae_lambda: %g, %s's is %g", (double)tio->gae_lambda, fn, (double)gae_lambda);
+        if (int rc = check_critic(h, critic, fn)) return rc;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    return gae_normalized(h, critic, reward_norm, tio, rows_out, values, n_steps, gamma, gae_lambda, advantages, returns,
+                          (hipStream_t)hip_stream);
+}
+
+int dockauv_collect_normalized(dockauv_handle h, dockauv_policy actor, dockauv_policy critic, const dockauv_collect_io* cio,
+                               const dockauv_truncation_io* tio, dockauv_rewnorm rn, const dockauv_rewnorm_io* nio,
+                               void* hip_stream) {
+    const char* fn = "dockauv_collect_normalized";
+    if (!cio) return fail(h, DOCKAUV_E_INVALID, "%s: cio is NULL", fn);
+    if (cio->struct_size != sizeof(dockauv_collect_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.struct_size: got %u, library has %zu", cio->struct_size, sizeof(dockauv_collect_io));
+    if (cio->n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.n_steps: %d must be >= 1", cio->n_steps);
+    if (!cio->rows_in || !cio->rows_out || !cio->actions_out)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: rows_in/rows_out/actions_out must not be NULL");
+    if (!cio->values || !cio->advantages || !cio->returns)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: values/advantages/returns must not be NULL (%s needs a critic)", fn);
+    if (tio && !cio->terminal_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.terminal_obs is NULL (the truncation block reads it)");
+    if (int rc = check_gae_factors(h, "dockauv_collect_io", cio->gamma, cio->gae_lambda)) return rc;
+    if (int rc = check_rewnorm_io(h, nio, fn)) return rc;
+    if (nio->n_steps != cio->n_steps) return fail(h, DOCKAUV_E_INVALID, "dockauv_rewnorm_io.n_steps: %d, dockauv_collect_io's is %d", nio->n_steps, cio->n_steps);
+    if (nio->rows_out != cio->rows_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_rewnorm_io.rows_out is not dockauv_collect_io's");
+    if (int rc = check_rewnorm(h, rn, fn)) return rc;
+    if (rn->gamma != cio->gamma)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.gamma: %g, the normaliser's is %g", (double)cio->gamma, (double)rn->gamma);
+    if (!actor) return fail(h, DOCKAUV_E_INVALID, "%s: null actor", fn);
+    if (!critic) return fail(h, DOCKAUV_E_INVALID, "%s: null critic (advantages of normalised rewards need values)", fn);
+    if (tio) {
+        if (int rc = check_truncation(h, tio, fn, true)) return rc;
+        if (int rc = check_truncation_matches(h, tio, cio)) return rc;
+    }
+    if (int rc = check_actor(h, actor, fn, cio->log_prob != nullptr)) return rc;
+    if (int rc = check_critic(h, critic, fn)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int K = cio->n_steps;
+    const size_t N = (size_t)h->cfg.n_envs;
+    if (tio) {   // (dockauv_collect_truncated: the steps of every env's episode before step 0)
+        HIP_TRY(h, hipMemcpyAsync(tio->length_carry, h->B.t_steps, N * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+        h->last_stream = stream;
+    }
+    int rc = queue_rollout(h, actor, cio->rows_in, cio->rows_out, cio->actions_out, cio->terminal_obs, cio->log_prob, K, cio->t0,
+                           cio->stochastic, stream);
+    if (rc) return rc;
+    if ((rc = value_forward(h, critic, cio->rows_in, (long long)N, cio->values, stream)) != 0) return rc;
+    if ((rc = value_forward(h, critic, cio->rows_out, (long long)K * (long long)N, cio->values + N, stream)) != 0) return rc;
+    if ((rc = rewnorm_scan(h, rn, nio, stream)) != 0) return rc;
+    if ((rc = gae_normalized(h, critic, nio->reward_norm, tio, cio->rows_out, cio->values, K, cio->gamma, cio->gae_lambda,
+                             cio->advantages, cio->returns, stream)) != 0)
+        return rc;
+    return check_status(h);   // (what dockauv_poll_status looks at: no synchronisation)
 }
 
 }  // extern "C"

@@ -15,6 +15,10 @@
 // gamma V(terminal_observation) to the reward of a step that ended on the time limit) is two kernels of the same shape: a forward
 // scan that leaves every env's truncated steps in per-env slots, and the GAE kernel instantiated on those slots.  Between the two
 // the critic's indexed rows kernel (dockauv_policy.hip) evaluates the slots' terminal observations.
+//
+// GAE on normalised rewards (include/dockauv.h: dockauv_gae_normalized): the same kernel instantiated twice more, with and without
+// the slots, on argument blocks whose reward is a [K][N] column (Args::kColumn: one coalesced load a step in place of the rows'
+// reward word).  A trait, not a run-time branch: the two instantiations on the rows are the code they were.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -29,6 +33,7 @@ constexpr int kGaePairs = kGaeChunk / 2;   // truncated steps a chunk can hold: 
 
 struct GaeArgs {
     static constexpr bool kTrunc = false;   // (what the kernel is instantiated on: dockauv_gae's own)
+    static constexpr bool kColumn = false;
     const float* rows;            // [K][N][row_stride]
     const float* values;          // [K + 1][N]
     float* advantages;            // [K][N]
@@ -41,6 +46,16 @@ struct GaeArgsTrunc : GaeArgs {   // dockauv_gae_truncated: the scan's slot tabl
     const int32_t* trunc_step;    // [n_slots][N], ascending per env, -1 in unused slots
     const float* v_terminal;      // [n_slots][N]
     int n_slots;
+};
+// dockauv_gae_normalized: the reward of step k comes from reward_col [K][N] (dockauv_rewnorm_scan's reward_norm), not from the
+// rows' reward word; the done word still comes from the rows
+struct GaeArgsCol : GaeArgs {
+    static constexpr bool kColumn = true;
+    const float* reward_col;
+};
+struct GaeArgsTruncCol : GaeArgsTrunc {
+    static constexpr bool kColumn = true;
+    const float* reward_col;
 };
 
 // Args::kTrunc: the lane's slots are counted once (n_slots coalesced loads in front of the first chunk); `pend` is the slot of
@@ -68,7 +83,8 @@ __global__ __launch_bounds__(kGaeThreads) void gae_kernel(const Args a) {
         for (int j = 0; j < kGaeChunk; ++j) {
             const int k = k0 - j > 0 ? k0 - j : 0;      // (below step 0: step 0 again, dropped by the loop below)
             const float* p = rd + (size_t)k * N * stride;
-            r[j] = p[0];
+            if constexpr (Args::kColumn) r[j] = a.reward_col[(size_t)k * N + (size_t)env];
+            else r[j] = p[0];
             d[j] = p[1];
             v[j] = a.values[(size_t)k * N + (size_t)env];
         }
@@ -179,6 +195,22 @@ int launch_gae_truncated(const float* rows, const float* values, float* advantag
     GaeArgsTrunc a{{rows, values, advantages, returns, n_steps, n_envs, n_obs, n_obs + 2, gamma, gae_lambda}, trunc_step, v_terminal, n_slots};
     const unsigned groups = (unsigned)((n_envs + kGaeThreads - 1) / kGaeThreads);
     hipLaunchKernelGGL(gae_kernel<GaeArgsTrunc>, dim3(groups), dim3(kGaeThreads), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+int launch_gae_column(const float* rows, const float* reward_col, const float* values, float* advantages, float* returns,
+                      const int32_t* trunc_step, const float* v_terminal, int n_slots, int n_steps, int n_envs, int n_obs,
+                      float gamma, float gae_lambda, void* stream) {
+    if (n_steps < 1 || n_envs < 1 || n_obs < 1 || (trunc_step && n_slots < 1)) return (int)hipErrorInvalidValue;
+    const unsigned groups = (unsigned)((n_envs + kGaeThreads - 1) / kGaeThreads);
+    if (trunc_step) {
+        GaeArgsTruncCol a{{{rows, values, advantages, returns, n_steps, n_envs, n_obs, n_obs + 2, gamma, gae_lambda}, trunc_step, v_terminal, n_slots},
+                          reward_col};
+        hipLaunchKernelGGL(gae_kernel<GaeArgsTruncCol>, dim3(groups), dim3(kGaeThreads), 0, (hipStream_t)stream, a);
+    } else {
+        GaeArgsCol a{{rows, values, advantages, returns, n_steps, n_envs, n_obs, n_obs + 2, gamma, gae_lambda}, reward_col};
+        hipLaunchKernelGGL(gae_kernel<GaeArgsCol>, dim3(groups), dim3(kGaeThreads), 0, (hipStream_t)stream, a);
+    }
     return (int)hipGetLastError();
 }
 

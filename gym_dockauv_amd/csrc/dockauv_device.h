@@ -681,6 +681,36 @@ struct MonitorArgs {
 // Two launches on stream (scan, final sums), four with values / returns.  Returns a hipError_t as int.
 int launch_monitor_scan(const MonitorArgs& a, void* stream);
 
+// ------------------------------------------------------------------------------------------ reward normalisation (dockauv_rewnorm.hip)
+// SB3's VecNormalize(norm_reward=True) on the reward column of the packed rows (include/dockauv.h: dockauv_rewnorm_scan states the
+// arithmetic and the order of the sums).  state: float64 [4] = running mean, var, count, reserved; carry: float32 [N], the
+// discounted return of every env before step 0; discounted / reward_norm: [K][N]; step_stats: float64 [K][4] = batch mean, batch
+// variance, running variance after step k, sqrt(that + epsilon).
+constexpr int kRnThreads = 64;            // the scan: one wave per group, as the monitor's
+inline int rewnorm_groups(int n_envs) { return (n_envs + kRnThreads - 1) / kRnThreads; }
+struct RewnormArgs {
+    const float* rows;                    // [K][N][row_stride]; only the reward and done columns are read
+    float* carry;                         // [N], read and written back (training)
+    double* state;                        // [4], read and written back (training); read (frozen)
+    float* discounted;                    // [K][N] (training)
+    float* reward_norm;                   // [K][N]
+    double* step_stats;                   // [K][4]; nullable when frozen, where only [k][3] is written
+    int n_steps, n_envs, n_obs, row_stride, training;
+    float gamma, clip_reward;
+    double epsilon;
+};
+// Training: four launches on stream (scan, per-step moments, the K merges, apply); frozen: one (apply on the running variance).
+// Returns a hipError_t as int.
+int launch_rewnorm_scan(const RewnormArgs& a, void* stream);
+// carry <- 0, state <- (0, 1, 1e-4, 0): one launch.  Returns a hipError_t as int.
+int launch_rewnorm_reset(float* carry, double* state, int n_envs, void* stream);
+// launch_gae / launch_gae_truncated with the reward read from reward_col [K][N] instead of the rows' reward word (the done word
+// still comes from the rows): the same kernel instantiated on argument blocks with the column.  trunc_step == nullptr: without
+// the truncation slots.  Returns a hipError_t as int.
+int launch_gae_column(const float* rows, const float* reward_col, const float* values, float* advantages, float* returns,
+                      const int32_t* trunc_step, const float* v_terminal, int n_slots, int n_steps, int n_envs, int n_obs,
+                      float gamma, float gae_lambda, void* stream);
+
 #ifdef DOCKAUV_STAMPS
 int read_stamps(unsigned long long* out);   // diagnostic build only
 int read_span(unsigned long long* out, int groups);

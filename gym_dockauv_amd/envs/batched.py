@@ -952,6 +952,102 @@ class BatchedDocking3d:
             self._lib.dockauv_monitor_destroy(monitor.ptr)
             monitor.ptr = C.c_void_p()
 
+    # ------------------------------------------------------------------------------------------ reward normalisation
+    def make_reward_normalizer(self, gamma: float, clip_reward: float = 10.0, epsilon: float = 1e-8):
+        """A reward normaliser of this handle (dockauv_rewnorm_create): SB3's VecNormalize(norm_reward=True) statistics --
+        running (mean, var, count) of the discounted return and one carry per env -- on the device.  Needs a float32 handle.
+        ``close`` destroys it before the handle."""
+        from ..normalize import DeviceRewardNormalizer
+        ptr = C.c_void_p()
+        rc = self._lib.dockauv_rewnorm_create(self._handle, float(gamma), float(clip_reward), float(epsilon), C.byref(ptr))
+        _capi.check(self._lib, self._handle, rc, "dockauv_rewnorm_create")
+        rn = DeviceRewardNormalizer(ptr, gamma, clip_reward, epsilon)
+        self._rewnorms = getattr(self, "_rewnorms", []) + [rn]
+        return rn
+
+    def reward_normalizer_state(self, rn):
+        """(device address of the state float64 [4] = mean, var, count, reserved; of the carries float32 [N]):
+        dockauv_rewnorm_state"""
+        s, c = C.c_void_p(), C.c_void_p()
+        rc = self._lib.dockauv_rewnorm_state(rn.ptr, C.byref(s), C.byref(c))
+        _capi.check(self._lib, self._handle, rc, "dockauv_rewnorm_state")
+        return int(s.value or 0), int(c.value or 0)
+
+    def reward_normalizer_reset(self, rn, stream: int = 0) -> None:
+        """state <- (0, 1, 1e-4), carries <- 0 at this point of ``stream`` (dockauv_rewnorm_reset)"""
+        rc = self._lib.dockauv_rewnorm_reset(rn.ptr, C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_rewnorm_reset")
+
+    def _rewnorm_io(self, rows_out_ptr: int, n_steps: int, reward_norm_ptr: int, discounted_ptr: int, step_stats_ptr: int,
+                    training: bool):
+        io = _capi.RewnormIO()
+        io.struct_size = C.sizeof(_capi.RewnormIO)
+        io.n_steps, io.training = int(n_steps), 1 if training else 0
+        io.rows_out, io.reward_norm = rows_out_ptr or None, reward_norm_ptr or None
+        io.discounted, io.step_stats = discounted_ptr or None, step_stats_ptr or None
+        return io
+
+    def reward_normalizer_scan_device(self, rn, rows_out_ptr: int, n_steps: int, reward_norm_ptr: int, discounted_ptr: int = 0,
+                                      step_stats_ptr: int = 0, training: bool = True, stream: int = 0) -> None:
+        """Normalised rewards of rows_out [K][N][n_obs + 2] (dockauv_rewnorm_scan): reward_norm float32 [K][N]; discounted
+        float32 [K][N] and step_stats float64 [K][4] (batch mean, batch var, running var, divisor), both required when
+        ``training``; ``training`` False applies the current statistics and touches neither them nor the carries.
+        Asynchronous."""
+        io = self._rewnorm_io(rows_out_ptr, n_steps, reward_norm_ptr, discounted_ptr, step_stats_ptr, training)
+        rc = self._lib.dockauv_rewnorm_scan(self._handle, rn.ptr, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_rewnorm_scan")
+
+    def gae_normalized_device(self, value, reward_norm_ptr: int, rows_out_ptr: int, values_ptr: int, n_steps: int, gamma: float,
+                              gae_lambda: float, advantages_ptr: int, returns_ptr: int, stream: int = 0, trunc=None) -> None:
+        """``gae_device`` with the reward of step k read from reward_norm [K][N] (dockauv_gae_normalized); the done word still
+        comes from rows_out.  ``trunc``: None, or a dict(n_slots, terminal_obs, length_carry, trunc_step, trunc_row, v_terminal)
+        of device addresses -- ``gae_truncated_device``'s three launches with the GAE on the column (needs ``value``).
+        Asynchronous."""
+        tio = None
+        if trunc is not None:
+            tio = self._truncation_io(n_steps, trunc["n_slots"], rows_out_ptr, trunc["terminal_obs"], trunc["length_carry"],
+                                      trunc["trunc_step"], trunc["trunc_row"], values_ptr, trunc["v_terminal"], advantages_ptr,
+                                      returns_ptr, gamma, gae_lambda)
+        rc = self._lib.dockauv_gae_normalized(self._handle, value.ptr if value is not None else None,
+                                              C.c_void_p(reward_norm_ptr or None), C.byref(tio) if tio is not None else None,
+                                              C.c_void_p(rows_out_ptr or None), C.c_void_p(values_ptr or None), int(n_steps),
+                                              float(gamma), float(gae_lambda), C.c_void_p(advantages_ptr or None),
+                                              C.c_void_p(returns_ptr or None), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_gae_normalized")
+
+    def collect_normalized_device(self, policy, value, rn, rows_in_ptr: int, rows_out_ptr: int, actions_out_ptr: int, n_steps: int,
+                                  reward_norm_ptr: int, discounted_ptr: int, step_stats_ptr: int, values_ptr: int,
+                                  advantages_ptr: int, returns_ptr: int, training: bool = True, gamma: float = 0.99,
+                                  gae_lambda: float = 0.95, t0: int = 0, stochastic: bool = True, stream: int = 0,
+                                  terminal_obs_ptr: int = 0, log_prob_ptr: int = 0, trunc=None) -> None:
+        """``collect_device`` with reward normalisation (dockauv_collect_normalized): the rollout and the two value launches,
+        ``reward_normalizer_scan_device``, then ``gae_normalized_device`` -- with ``trunc`` (see there; its terminal_obs is
+        ``terminal_obs_ptr``) the truncation bootstrap on the normalised rewards.  Needs a critic.  Asynchronous; raises like
+        poll_status()."""
+        cio = _capi.CollectIO()
+        cio.struct_size = C.sizeof(_capi.CollectIO)
+        cio.n_steps = int(n_steps)
+        cio.rows_in, cio.rows_out, cio.actions_out = rows_in_ptr or None, rows_out_ptr or None, actions_out_ptr or None
+        cio.terminal_obs, cio.log_prob = terminal_obs_ptr or None, log_prob_ptr or None
+        cio.values, cio.advantages, cio.returns = values_ptr or None, advantages_ptr or None, returns_ptr or None
+        cio.t0, cio.stochastic = int(t0), 1 if stochastic else 0
+        cio.gamma, cio.gae_lambda = float(gamma), float(gae_lambda)
+        tio = None
+        if trunc is not None:
+            tio = self._truncation_io(n_steps, trunc["n_slots"], rows_out_ptr, terminal_obs_ptr, trunc["length_carry"],
+                                      trunc["trunc_step"], trunc["trunc_row"], values_ptr, trunc["v_terminal"], advantages_ptr,
+                                      returns_ptr, gamma, gae_lambda)
+        nio = self._rewnorm_io(rows_out_ptr, n_steps, reward_norm_ptr, discounted_ptr, step_stats_ptr, training)
+        rc = self._lib.dockauv_collect_normalized(self._handle, policy.ptr, value.ptr if value is not None else None, C.byref(cio),
+                                                  C.byref(tio) if tio is not None else None, rn.ptr, C.byref(nio),
+                                                  C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_collect_normalized")
+
+    def destroy_reward_normalizer(self, rn) -> None:
+        if rn.ptr is not None and rn.ptr.value:
+            self._lib.dockauv_rewnorm_destroy(rn.ptr)
+            rn.ptr = C.c_void_p()
+
     def destroy_optim(self, opt) -> None:
         if opt.ptr is not None and opt.ptr.value:
             self._lib.dockauv_optim_destroy(opt.ptr)
@@ -993,6 +1089,9 @@ class BatchedDocking3d:
             for mon in getattr(self, "_monitors", []):   # (a monitor goes before its handle)
                 self.destroy_monitor(mon)
             self._monitors = []
+            for rn in getattr(self, "_rewnorms", []):    # (a reward normaliser goes before its handle)
+                self.destroy_reward_normalizer(rn)
+            self._rewnorms = []
             for pol in getattr(self, "_policies", []):   # (a policy goes before its handle)
                 self.destroy_policy(pol)
             self._policies = []

@@ -18,6 +18,8 @@ from __future__ import annotations
 from collections import namedtuple
 from typing import Optional
 
+import numpy as np
+
 from .. import _capi
 from ..config.env_config import BASE_CONFIG
 from .batched import BatchedDocking3d
@@ -150,6 +152,13 @@ class TorchDocking3d:
         from ..monitor import EpisodeMonitor
         return EpisodeMonitor(self)
 
+    def make_reward_normalizer(self, gamma: float, clip_reward: float = 10.0, epsilon: float = 1e-8):
+        """A ``RewardNormalizer`` (gym_dockauv_amd/normalize.py) of this env for ``collect(..., reward_norm=rn)``: SB3's
+        ``VecNormalize(norm_reward=True)`` on the device -- rewards divided by the running standard deviation of the
+        discounted return (``gamma``: the learner's) and clipped to +- ``clip_reward``."""
+        from ..normalize import RewardNormalizer
+        return RewardNormalizer(self, gamma, clip_reward, epsilon)
+
     def _monitor_before(self, monitor) -> None:
         """before a monitored call queues its steps: the handle's own counters cover whatever the monitor did not see (``step``,
         ``reset``, unmonitored calls), so its carries are re-read from them unless its last scan ended where the trajectory is"""
@@ -199,7 +208,7 @@ class TorchDocking3d:
         return rows[:, :, : self.n_obs], acts, rows[:, :, self.n_obs], rows[:, :, self.n_obs + 1] > 0.5
 
     def collect(self, policy, value, n_steps: int, gamma: float, gae_lambda: float, stochastic: bool = True,
-                want_terminal_obs: bool = False, monitor=None, bootstrap_truncated: bool = False):
+                want_terminal_obs: bool = False, monitor=None, bootstrap_truncated: bool = False, reward_norm=None):
         """One PPO iteration's collection queued by ONE host call (dockauv_collect) on the current stream: ``rollout`` plus
         log pi(a|s), V(s) of the K + 1 observation sets and GAE.  Continues the trajectory exactly as ``rollout`` does.  Returns
         a ``Collected`` named tuple of views of buffers the env owns (reused by the next ``collect`` of the same K):
@@ -214,11 +223,25 @@ class TorchDocking3d:
         limit and on nothing else (the monitor's outcome 3), advantages and returns are those of reward + gamma *
         V(terminal observation) at that step; reward, values and log_prob are what they are without it.  Forces
         ``want_terminal_obs`` and needs a critic; the tuple keeps its fields.  With the default not one launch is added or
-        changed."""
+        changed.
+        ``reward_norm`` (``make_reward_normalizer``): SB3's VecNormalize(norm_reward=True) (dockauv_collect_normalized) -- behind
+        the value launches the normaliser's scan of these K steps (``rn.normalized``, ``rn.discounted``, ``rn.step_stats``: its
+        outputs, per K; with ``rn.training`` False the statistics are applied and not updated), and ``advantages`` / ``returns``
+        are those of the normalised rewards, with ``bootstrap_truncated`` of normalised reward + gamma * V(terminal
+        observation).  ``reward`` stays the raw column (the monitor's returns stay sums of raw rewards), values and log_prob are
+        what they are without it; the tuple keeps its fields.  Needs a critic and ``rn.gamma == gamma``.  With the default
+        not one launch is added or changed."""
         torch = self.torch
         K = int(n_steps)
         if K < 1:
             raise ValueError("n_steps must be >= 1")
+        if reward_norm is not None:
+            if value is None:
+                raise ValueError("reward_norm needs a critic: it changes advantages and returns only")
+            if reward_norm.env is not self:
+                raise ValueError("the reward normaliser belongs to another env")
+            if np.float32(reward_norm.gamma) != np.float32(gamma):
+                raise ValueError(f"gamma {gamma} is not the reward normaliser's ({reward_norm.gamma})")
         if bootstrap_truncated:
             if value is None:
                 raise ValueError("bootstrap_truncated needs a critic: the bootstrap is its value of the terminal observation")
@@ -241,6 +264,7 @@ class TorchDocking3d:
         has_v = value is not None
         values, adv, ret = (bufs["values"], bufs["adv"], bufs["ret"]) if has_v else (None, None, None)
         logp = bufs["logp"] if (policy.has_log_std and policy.shape.out_act == _capi.ACT_NONE) else None
+        ws = None
         if bootstrap_truncated:
             ws = bufs.get("trunc")
             if ws is None:      # the four workspaces of dockauv_truncation_io, once per K
@@ -249,6 +273,22 @@ class TorchDocking3d:
                                           step=torch.zeros((S, N), device=self.device, dtype=torch.int32),
                                           row=torch.zeros((S, N), device=self.device, dtype=torch.int64),
                                           v=torch.zeros((S, N), device=self.device, dtype=torch.float32))
+        if reward_norm is not None:
+            nws = bufs.get("rewnorm")
+            if nws is None:     # the outputs of dockauv_rewnorm_io, once per K
+                nws = bufs["rewnorm"] = reward_norm._workspace(K)
+            trunc = None if ws is None else dict(n_slots=ws["slots"], length_carry=ws["carry"].data_ptr(),
+                                                 trunc_step=ws["step"].data_ptr(), trunc_row=ws["row"].data_ptr(),
+                                                 v_terminal=ws["v"].data_ptr())
+            self.batch.collect_normalized_device(policy, value, reward_norm.handle, rows[0].data_ptr(), rows[1].data_ptr(),
+                                                 bufs["acts"].data_ptr(), K, nws["norm"].data_ptr(), nws["disc"].data_ptr(),
+                                                 nws["stats"].data_ptr(), values.data_ptr(), adv.data_ptr(), ret.data_ptr(),
+                                                 training=reward_norm.training, gamma=gamma, gae_lambda=gae_lambda, t0=self._t,
+                                                 stochastic=stochastic, stream=torch.cuda.current_stream().cuda_stream,
+                                                 terminal_obs_ptr=term.data_ptr() if term is not None else 0,
+                                                 log_prob_ptr=0 if logp is None else logp.data_ptr(), trunc=trunc)
+            reward_norm._attach(nws)
+        elif bootstrap_truncated:
             self.batch.collect_truncated_device(policy, value, rows[0].data_ptr(), rows[1].data_ptr(), bufs["acts"].data_ptr(), K,
                                                 ws["slots"], term.data_ptr(), values.data_ptr(), adv.data_ptr(), ret.data_ptr(),
                                                 ws["carry"].data_ptr(), ws["step"].data_ptr(), ws["row"].data_ptr(),

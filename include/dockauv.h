@@ -872,6 +872,86 @@ int dockauv_monitor_sync(dockauv_monitor m, void* hip_stream);
 int dockauv_monitor_scan(dockauv_handle h, dockauv_monitor m, const dockauv_monitor_io* io, void* hip_stream);
 int dockauv_monitor_carry(dockauv_monitor m, float** carry_return, int32_t** carry_length);
 
+/*
+ * Reward normalisation: SB3 1.5's VecNormalize(norm_reward=True, norm_obs=False) with its RunningMeanStd -- every reward divided
+ * by the running standard deviation of the discounted return, then clipped -- computed on the device from the reward and done
+ * columns of a collection.  The terminal rewards of this env are in the hundreds (config/env_config.py: w_goal 400, w_col -300)
+ * on per-step terms of order one; normalised rewards put the returns on the scale vf_coef, max_grad_norm and clip_range_vf were
+ * chosen for.  Observations are not normalised (the reference's are bounded in [-1, 1] by construction).  Opt-in: without these
+ * calls every other call queues exactly what it queued before.  All pointers are device pointers, the workspaces belong to the
+ * caller, no call but create allocates, every call but create and destroy is asynchronous on the stream.
+ *
+ * A dockauv_rewnorm belongs to one float32 handle.  It owns the running state, float64 [4] = (mean, var, count, reserved),
+ * starting at (0, 1, 1e-4, 0), one discounted-return carry per env, float32 [n_envs], starting at 0, and the constants gamma
+ * (float32, in [0, 1]), clip_reward (float32, > 0; SB3's default 10) and epsilon (float64, >= 0; SB3's default 1e-8), fixed at
+ * create.  Destroy it before its handle.  The calls on one normaliser must be ordered on one stream (or by events).
+ *
+ * dockauv_rewnorm_scan over K = n_steps steps of N = n_envs envs, for k = 0 .. K - 1 in this order:
+ *   1 per env, float32 with two roundings (a product, then a sum: never a fused multiply-add):
+ *       ret = carry * gamma + reward[k];   discounted[k][env] = ret;   carry = done[k] > 0.5f ? 0.0f : ret
+ *   2 the batch moments of discounted[k][0 .. N) in float64: batch_mean = sum / N, then in a second pass over the same column
+ *       batch_var = (sum of (x - batch_mean)^2) / N    (each term accumulated as fma(q, q, sum), q = x - batch_mean)
+ *   3 RunningMeanStd.update_from_moments with batch_count = N, every operation a float64 rounding of its own:
+ *       delta = batch_mean - mean;   tot = count + N
+ *       mean  = mean + (delta * N) / tot
+ *       M2    = (var * count + batch_var * N) + (((delta * delta) * count) * N) / tot
+ *       var   = M2 / tot;   count = tot
+ *   4 den_k = sqrt(var + epsilon) in float64;
+ *       reward_norm[k][env] = (float) min(max((double) reward[k][env] / den_k, -clip_reward), clip_reward)
+ *     the float64 division SB3 does, stored as float32 the way its rollout buffer stores it.  Step k's reward is divided by the
+ *     statistics that include step k, as VecNormalize.step_wait does.
+ * training == 0 (SB3's training=False, for evaluation): only 4 runs, every k with den = sqrt(var + epsilon) of the current
+ * state; carries and state are not touched, discounted is not written.
+ * step_stats: float64 [K][4] = batch_mean, batch_var, var after step k, den_k; with training == 0 nullable, and only den is written.
+ * discounted is a workspace the caller owns and an output; required, like step_stats, when training.
+ *
+ * Reproducible: no atomics.  The sums of 2 run on one group of 1 024 lanes per step: lane t adds the elements t, t + 1 024,
+ * t + 2 048, .. in that order, the 64 lanes of a wave are added by a fixed tree (the monitor's), the sixteen waves in order; all
+ * groups of 4 divide by the same den_k bits.  The bits depend on the inputs, n_envs and n_steps only.  Launches: four when
+ * training (1, 2, 3, 4), one otherwise (4).
+ *
+ * dockauv_rewnorm_state: device pointers to the state [4] and the carries [n_envs], owned by the normaliser; either output may be
+ *   NULL.  A checkpoint is a copy of these two arrays out and in.
+ * dockauv_rewnorm_reset: state <- (0, 1, 1e-4, 0), carries <- 0; one launch.
+ * dockauv_gae_normalized: dockauv_gae with the reward of step k read from reward_norm[k][env] instead of the rows' reward word
+ *   (the done word still comes from the rows): one launch, the same float32 order.  With a truncation block it queues
+ *   dockauv_gae_truncated's three launches -- the scan, the critic on the slots' terminal observations, the GAE, here on the
+ *   column -- with rb = fmaf(gamma, v_terminal[s][env], reward_norm[k][env]): SB3's order, VecNormalize normalises inside
+ *   step_wait and collect_rollouts adds the bootstrap afterwards.  critic may be NULL without a truncation block.  rows_out,
+ *   values, n_steps, gamma, gae_lambda, advantages and returns must be the block's.
+ * dockauv_collect_normalized: dockauv_collect's launches up to and including the value launches (with tio, in front of them,
+ *   dockauv_collect_truncated's copy of the step counters into length_carry), then dockauv_rewnorm_scan, then
+ *   dockauv_gae_normalized (with tio: its truncation form).  The critic is required.  nio's n_steps and rows_out must be cio's,
+ *   the normaliser's gamma must be cio's, tio must agree with cio as for dockauv_collect_truncated.  The reward column of the rows,
+ *   values and log-probabilities are what dockauv_collect writes: the monitor's returns stay sums of raw rewards, as SB3's Monitor
+ *   inside VecNormalize sees them.
+ * Refused before any device call (DOCKAUV_E_INVALID, the message naming the field): a NULL handle, normaliser, io or required
+ * pointer; a wrong struct_size; n_steps < 1; gamma outside [0, 1]; clip_reward <= 0; epsilon < 0; a float64 handle; a normaliser
+ * of another handle; blocks whose n_steps, rows_out or gamma disagree.
+ */
+typedef struct dockauv_rewnorm_s* dockauv_rewnorm;
+typedef struct dockauv_rewnorm_io {
+    uint32_t struct_size;          /* sizeof(dockauv_rewnorm_io): ABI check */
+    int32_t n_steps;               /* K >= 1 */
+    int32_t training;              /* 0: frozen statistics (evaluation) */
+    int32_t reserved;
+    const float* rows_out;         /* [K][n_envs][n_obs + 2]: only the reward and done columns are read */
+    float* reward_norm;            /* [K][n_envs] */
+    float* discounted;             /* [K][n_envs]; NULL allowed when training == 0 */
+    double* step_stats;            /* [K][4]; NULL allowed when training == 0 */
+} dockauv_rewnorm_io;
+int dockauv_rewnorm_create(dockauv_handle h, float gamma, float clip_reward, double epsilon, dockauv_rewnorm* out);
+int dockauv_rewnorm_destroy(dockauv_rewnorm rn);   /* NULL: 0 */
+int dockauv_rewnorm_state(dockauv_rewnorm rn, double** state, float** carry);
+int dockauv_rewnorm_reset(dockauv_rewnorm rn, void* hip_stream);
+int dockauv_rewnorm_scan(dockauv_handle h, dockauv_rewnorm rn, const dockauv_rewnorm_io* io, void* hip_stream);
+int dockauv_gae_normalized(dockauv_handle h, dockauv_policy critic, const float* reward_norm, const dockauv_truncation_io* tio,
+                           const float* rows_out, const float* values, int n_steps, float gamma, float gae_lambda,
+                           float* advantages, float* returns, void* hip_stream);
+int dockauv_collect_normalized(dockauv_handle h, dockauv_policy actor, dockauv_policy critic, const dockauv_collect_io* cio,
+                               const dockauv_truncation_io* tio, dockauv_rewnorm rn, const dockauv_rewnorm_io* nio,
+                               void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
