@@ -195,6 +195,13 @@ class RewnormIO(C.Structure):
     ]
 
 
+class EvalIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_steps", C.c_int32),
+        ("rows_out", C.c_void_p), ("terminal_obs", C.c_void_p), ("stats", C.c_void_p),
+    ]
+
+
 # every symbol include/dockauv.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("dockauv_abi_version", C.c_int, []),
@@ -264,6 +271,11 @@ SYMBOLS = [
     ("dockauv_monitor_sync", C.c_int, [C.c_void_p, C.c_void_p]),
     ("dockauv_monitor_scan", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MonitorIO), C.c_void_p]),
     ("dockauv_monitor_carry", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ("dockauv_eval_create", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    ("dockauv_eval_destroy", C.c_int, [C.c_void_p]),
+    ("dockauv_eval_begin", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    ("dockauv_eval_scan", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(EvalIO), C.c_void_p]),
+    ("dockauv_eval_state", C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 7),
     ("dockauv_rewnorm_create", C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_double, C.POINTER(C.c_void_p)]),
     ("dockauv_rewnorm_destroy", C.c_int, [C.c_void_p]),
     ("dockauv_rewnorm_state", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

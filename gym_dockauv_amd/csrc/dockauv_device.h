@@ -681,6 +681,36 @@ struct MonitorArgs {
 // Two launches on stream (scan, final sums), four with values / returns.  Returns a hipError_t as int.
 int launch_monitor_scan(const MonitorArgs& a, void* stream);
 
+// ------------------------------------------------------------------------------------------ policy evaluation (dockauv_eval.hip)
+// The monitor's walk with an episode quota per env (include/dockauv.h: dockauv_eval_scan states the arithmetic and the order of
+// the sums): env i's j-th counted episode goes to slot [j][i] of ep_return / ep_length / ep_outcome ([n_slots][N]) while
+// count[i] < target[i]; stats [16] covers every slot recorded since the begin.  The scan leaves kEvalWords float64 words a group
+// in `partial` ([kEvalWords][eval_groups(n_envs)]).
+constexpr int kEvalThreads = 64;          // one wave per group, as the monitor's scan
+constexpr int kEvalWords = 14;            // the monitor's thirteen and the episodes still missing
+inline int eval_groups(int n_envs) { return (n_envs + kEvalThreads - 1) / kEvalThreads; }
+inline size_t eval_workspace_doubles(int n_envs) { return (size_t)kEvalWords * (size_t)eval_groups(n_envs); }
+struct EvalArgs {
+    const float* rows;                    // [K][N][row_stride]; only the reward and done columns are read
+    const float* terminal_obs;            // nullable [K][N][n_obs]; columns 0, 6, 7 are read where a counted episode ends
+    float* carry_ret;                     // [N], read and written back
+    int32_t* carry_len;                   // [N]
+    int32_t* count;                       // [N], read and written back
+    const int32_t* target;                // [N], in [0, n_slots]
+    float* ep_return;                     // [n_slots][N]
+    int32_t* ep_length;                   // [n_slots][N]
+    uint8_t* ep_outcome;                  // [n_slots][N]; 255: not classified (no terminal_obs) or not recorded
+    double* partial;                      // eval_workspace_doubles
+    double* stats;                        // [16]
+    int n_steps, n_envs, n_obs, row_stride, max_timesteps, n_slots;
+};
+// count <- 0, target <- clamp(targets ? targets[env] : uniform_target, 0, n_slots), slots <- (0, 0, 255): one launch.  Needs
+// n_envs * n_slots < 2^31.  Returns a hipError_t as int.
+int launch_eval_begin(const int32_t* targets, int uniform_target, int32_t* count, int32_t* target, float* ep_return,
+                      int32_t* ep_length, uint8_t* ep_outcome, int n_envs, int n_slots, void* stream);
+// Two launches on stream (scan, final sums).  Returns a hipError_t as int.
+int launch_eval_scan(const EvalArgs& a, void* stream);
+
 // ------------------------------------------------------------------------------------------ reward normalisation (dockauv_rewnorm.hip)
 // SB3's VecNormalize(norm_reward=True) on the reward column of the packed rows (include/dockauv.h: dockauv_rewnorm_scan states the
 // arithmetic and the order of the sums).  state: float64 [4] = running mean, var, count, reserved; carry: float32 [N], the

@@ -952,6 +952,53 @@ class BatchedDocking3d:
             self._lib.dockauv_monitor_destroy(monitor.ptr)
             monitor.ptr = C.c_void_p()
 
+    # ------------------------------------------------------------------------------------------ policy evaluation
+    def make_evaluator(self, max_episodes_per_env: int):
+        """An evaluator of this handle (dockauv_eval_create): per-env carries, counts and quotas, ``max_episodes_per_env`` episode
+        slots per env and the reduction workspace, in the state of a begin with target 0.  Needs a float32 handle with an
+        auto-reset mode.  ``close`` destroys it before the handle."""
+        from ..evaluate import DeviceEvaluator
+        ptr = C.c_void_p()
+        rc = self._lib.dockauv_eval_create(self._handle, int(max_episodes_per_env), C.byref(ptr))
+        _capi.check(self._lib, self._handle, rc, "dockauv_eval_create")
+        ev = DeviceEvaluator(ptr, max_episodes_per_env)
+        self._evaluators = getattr(self, "_evaluators", []) + [ev]
+        return ev
+
+    def evaluator_begin(self, evaluator, targets_ptr: int = 0, uniform_target: int = 1, stream: int = 0) -> None:
+        """A new evaluation at this point of ``stream`` (dockauv_eval_begin): carries <- the handle's cumulative rewards / step
+        counters, counts and slots cleared, quotas from the device array int32 [N] at ``targets_ptr`` (clamped to [0,
+        max_episodes_per_env] on the device) or, with 0, ``uniform_target`` for every env.  Asynchronous."""
+        rc = self._lib.dockauv_eval_begin(evaluator.ptr, C.c_void_p(targets_ptr or None), int(uniform_target),
+                                          C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_eval_begin")
+
+    def evaluator_scan_device(self, evaluator, rows_out_ptr: int, n_steps: int, stats_ptr: int, terminal_obs_ptr: int = 0,
+                              stream: int = 0) -> None:
+        """The episodes that finish inside rows_out [K][N][n_obs + 2] go to the evaluator's slots while their env is below its
+        quota (dockauv_eval_scan); stats float64 [16] over everything recorded since the begin; terminal_obs [K][N][n_obs] or 0
+        (no outcomes).  Asynchronous."""
+        io = _capi.EvalIO()
+        io.struct_size = C.sizeof(_capi.EvalIO)
+        io.n_steps = int(n_steps)
+        io.rows_out, io.terminal_obs, io.stats = rows_out_ptr or None, terminal_obs_ptr or None, stats_ptr or None
+        rc = self._lib.dockauv_eval_scan(self._handle, evaluator.ptr, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_eval_scan")
+
+    def evaluator_state(self, evaluator) -> dict:
+        """Device addresses of the evaluator's arrays (dockauv_eval_state): count, target, carry_length int32 [N], carry_return
+        float32 [N], ep_return float32 / ep_length int32 / ep_outcome uint8 [max_episodes_per_env][N]"""
+        names = ("count", "target", "ep_return", "ep_length", "ep_outcome", "carry_return", "carry_length")
+        out = [C.c_void_p() for _ in names]
+        rc = self._lib.dockauv_eval_state(evaluator.ptr, *[C.byref(p) for p in out])
+        _capi.check(self._lib, self._handle, rc, "dockauv_eval_state")
+        return {n: int(p.value or 0) for n, p in zip(names, out)}
+
+    def destroy_evaluator(self, evaluator) -> None:
+        if evaluator.ptr is not None and evaluator.ptr.value:
+            self._lib.dockauv_eval_destroy(evaluator.ptr)
+            evaluator.ptr = C.c_void_p()
+
     # ------------------------------------------------------------------------------------------ reward normalisation
     def make_reward_normalizer(self, gamma: float, clip_reward: float = 10.0, epsilon: float = 1e-8):
         """A reward normaliser of this handle (dockauv_rewnorm_create): SB3's VecNormalize(norm_reward=True) statistics --
@@ -1089,6 +1136,9 @@ class BatchedDocking3d:
             for mon in getattr(self, "_monitors", []):   # (a monitor goes before its handle)
                 self.destroy_monitor(mon)
             self._monitors = []
+            for ev in getattr(self, "_evaluators", []):  # (an evaluator goes before its handle)
+                self.destroy_evaluator(ev)
+            self._evaluators = []
             for rn in getattr(self, "_rewnorms", []):    # (a reward normaliser goes before its handle)
                 self.destroy_reward_normalizer(rn)
             self._rewnorms = []

@@ -59,6 +59,7 @@ class TorchDocking3d:
         self._rollout_bufs = {}
         self._collect_bufs = {}
         self.rollout_terminal_observation = None
+        self.evaluator = None           # the Evaluator of the last evaluate(): summary(), episodes(), n_chunks
         # mixed batches built with sort_vehicles=True: row j of every tensor handed in / out belongs to the caller's env
         # perm[j] (kind-sorted on the device, the caller's order within a kind); identity otherwise
         self.perm = torch.as_tensor(self.batch.perm, device=self.device)
@@ -158,6 +159,12 @@ class TorchDocking3d:
         discounted return (``gamma``: the learner's) and clipped to +- ``clip_reward``."""
         from ..normalize import RewardNormalizer
         return RewardNormalizer(self, gamma, clip_reward, epsilon)
+
+    def make_evaluator(self, max_episodes_per_env: int):
+        """An ``Evaluator`` (gym_dockauv_amd/evaluate.py) of this env for ``evaluate``: an episode quota per env and
+        ``max_episodes_per_env`` episode slots per env, on the device."""
+        from ..evaluate import Evaluator
+        return Evaluator(self, max_episodes_per_env)
 
     def _monitor_before(self, monitor) -> None:
         """before a monitored call queues its steps: the handle's own counters cover whatever the monitor did not see (``step``,
@@ -310,6 +317,54 @@ class TorchDocking3d:
             self._monitor_after(monitor, rows[1:], term, values, ret)
         return Collected(rows[:, :, : self.n_obs], bufs["acts"], rows[1:, :, self.n_obs], rows[1:, :, self.n_obs + 1] > 0.5,
                          logp, values, adv, ret)
+
+    def evaluate(self, policy, n_eval_episodes: int, deterministic: bool = True, seed: Optional[int] = None,
+                 n_steps: Optional[int] = None, return_episode_rewards: bool = False, evaluator=None):
+        """The reference's ``predict`` (train.py:86-118) and SB3's ``evaluate_policy`` in one call: ``reset(seed)``, then chunks of
+        ``rollout(policy, K, stochastic=not deterministic, want_terminal_obs=True)`` + the evaluator's scan until every env has
+        finished its quota ``evaluation_targets(n_eval_episodes, num_envs)[i]`` of episodes -- SB3's rule, under which short
+        episodes (collisions) weigh no more than long ones.  K = ``n_steps``, default min(128, max_timesteps + 1).  One 8-byte
+        read per chunk (``Evaluator.missing``) is all that waits for the device.  After a reset every episode ends within
+        max_timesteps + 1 steps, so ceil(max(targets) (max_timesteps + 1) / K) chunks always suffice: RuntimeError if episodes
+        are still missing after that many.
+        Returns (mean_reward, std_reward) over the n_eval_episodes episode returns (np.mean / np.std: the population std, as
+        SB3), or with ``return_episode_rewards`` (episode_rewards, episode_lengths), lists in env-major order.  The evaluator
+        keeps the details and stays at ``self.evaluator``: ``summary()`` carries the five outcome rates, ``episodes()`` the
+        outcomes, ``n_chunks`` the chunks run.  ``evaluator`` (``make_evaluator``, at least max(targets) slots per env); None:
+        the last call's when it has slots enough, else a new one."""
+        from ..evaluate import evaluation_targets
+        targets = evaluation_targets(n_eval_episodes, self.num_envs)
+        S = int(targets.max())
+        ev = evaluator
+        if ev is None:
+            ev = self.evaluator if (self.evaluator is not None and self.evaluator.n_slots >= S) else self.make_evaluator(S)
+        if ev.env is not self:
+            raise ValueError("the evaluator belongs to another env")
+        if ev.n_slots < S:
+            raise ValueError(f"the evaluator has {ev.n_slots} slots per env, {n_eval_episodes} episodes need {S}")
+        self.evaluator = ev
+        horizon = int(self.batch.config["max_timesteps"]) + 1
+        K = min(128, horizon) if n_steps is None else int(n_steps)
+        if K < 1:
+            raise ValueError("n_steps must be >= 1")
+        self.reset(seed)
+        ev.begin(targets)
+        max_chunks = -(-S * horizon // K)
+        ev.n_chunks = 0
+        missing = int(n_eval_episodes)
+        while missing and ev.n_chunks < max_chunks:
+            self.rollout(policy, K, stochastic=not deterministic, want_terminal_obs=True)
+            ev.scan(self._rollout_bufs[K][0], self.rollout_terminal_observation)
+            ev.n_chunks += 1
+            missing = ev.missing()
+        if missing:
+            raise RuntimeError(f"{missing} of {n_eval_episodes} episodes are still missing after {ev.n_chunks} chunks of {K} steps: "
+                               f"an episode outlived max_timesteps + 1 = {horizon} steps")
+        returns, lengths, _, _ = ev.episodes()
+        rewards = returns.cpu().numpy().astype(np.float64)
+        if return_episode_rewards:
+            return rewards.tolist(), lengths.cpu().numpy().tolist()
+        return float(np.mean(rewards)), float(np.std(rewards))
 
     # ------------------------------------------------------------------------------------------ the network's share of the update
     def _mlp_rows(self, policy, rows, index):

@@ -873,6 +873,74 @@ int dockauv_monitor_scan(dockauv_handle h, dockauv_monitor m, const dockauv_moni
 int dockauv_monitor_carry(dockauv_monitor m, float** carry_return, int32_t** carry_length);
 
 /*
+ * Policy evaluation: the reference's predict(gym_env, model_path, n_episodes) (train.py:86-118) and SB3's evaluate_policy(model,
+ * env, n_eval_episodes) on the device.  The monitor counts every episode that finishes inside a window of K steps; with
+ * auto-reset an env whose episodes are short -- in this task the collisions and out-of-range failures -- finishes many in the
+ * window and one whose episodes are long -- time limits, slow dockings -- few, so the window's rates are length-biased.  SB3's
+ * evaluate_policy gives every env a quota, episode_count_targets[i] = (n_eval_episodes + i) / n_envs, and counts only the first
+ * targets[i] episodes of env i.  This is that rule, computed from the buffers dockauv_rollout writes by a pass AFTER it: the
+ * step kernels, dockauv_rollout, dockauv_collect* and the monitor queue exactly what they queue without an evaluator.  All
+ * pointers are device pointers; begin, scan and state never synchronise.
+ *
+ * A dockauv_eval belongs to one float32 handle with an auto-reset mode.  It owns, allocated once at create for S =
+ * max_episodes_per_env: per env the carries (float32 running return, int32 running length), count and target (int32); the episode
+ * slots ep_return float32 [S][n_envs], ep_length int32 [S][n_envs], ep_outcome uint8 [S][n_envs] -- env i's j-th counted episode
+ * is at [j][i], as the truncation slots of dockauv_truncation_scan: no compaction, no atomics --; and its reduction workspace.
+ * Later calls allocate nothing.  Destroy it before its handle.  The calls on one evaluator must be ordered on one stream (or by
+ * events).  Create leaves the state of a begin with target 0 (it waits for what the handle has queued and for its own launch).
+ *
+ * dockauv_eval_begin (two device copies and one launch):
+ *   carries <- the handle's own DOCKAUV_F_CUM_REWARD / DOCKAUV_F_TSTEPS arrays at this point of the stream, as
+ *     dockauv_monitor_sync: zero right after a reset, right mid-trajectory too;
+ *   count <- 0;  ep_return <- 0.0f;  ep_length <- 0;  ep_outcome <- 255;
+ *   target[i] <- min(max(targets[i], 0), S) -- clamped in the kernel --, or uniform_target for every env when targets is NULL; a
+ *     uniform_target outside [0, S] is refused on the host.
+ *
+ * dockauv_eval_scan over K = n_steps steps, per env, forwards from k = 0, in exactly this order -- the monitor's arithmetic and
+ * outcome rule (dockauv_monitor_scan), word for word:
+ *   ret = carry_return + reward[k]        (float32, one plain add)
+ *   len = carry_length + 1                (int32)
+ *   if done[k] > 0.5f:  code = outcome(terminal_obs[k][env], len)     (the monitor's five codes; 255 when terminal_obs is NULL)
+ *                       if count < target:  slot[count][env] = (ret, len, code);  count += 1
+ *                       carry_return = 0.0f;  carry_length = 0
+ *   else:               carry_return = ret;  carry_length = len
+ * Episodes beyond an env's target are walked, because the carries must stay those of the handle; they are recorded nowhere.
+ * Slots that no episode reached keep (0, 0, 255).
+ *
+ * stats: float64 [16] over ALL episodes recorded since the begin, not only this scan's, in the layout of dockauv_monitor_io.stats:
+ *   0 n_episodes   1 sum of returns   2 sum of returns^2   3 sum of lengths
+ *   4, 5 min, max return   6, 7 min, max length            (NaN when n_episodes == 0)
+ *   8 .. 12 episodes per outcome 0 .. 4   13 episodes classified (those recorded with terminal_obs)
+ *   14 NaN         15 the episodes still missing, sum over i of (target[i] - count[i]), exact
+ * Sums 1 and 2 are float64 sums of (double)ret and (double)ret * (double)ret; the counts are exact.
+ * Reproducible: no atomics.  After its walk a lane adds its own slots j = 0 .. count - 1 in order; the 64 lanes of a group are
+ * added by the monitor's fixed tree, the groups' partials -- in the evaluator's workspace -- by one final group of 1 024 lanes
+ * (lane t the groups t, t + 1 024, .. in order, then the same tree, then the sixteen waves in order), as the monitor's final
+ * launch does.  The bits depend on the inputs, n_envs, S and the union of the steps scanned since the begin only: one scan of
+ * 57 steps and three of 19 leave the same bits everywhere.  Launches: two a scan (the walk, the final sums).
+ *
+ * dockauv_eval_state: device pointers to the per-env arrays ([n_envs]) and the slots ([S][n_envs]), owned by the evaluator; each
+ *   output may be NULL.
+ * Refused before any device call (DOCKAUV_E_INVALID, the message naming the field): a NULL handle, evaluator, io, rows_out or
+ * stats; a wrong struct_size; n_steps < 1; max_episodes_per_env < 1; slot arrays that would reach 2^31 elements; a uniform_target
+ * outside [0, S]; a float64 handle; a handle with DOCKAUV_RESET_NONE; an evaluator of another handle.
+ */
+typedef struct dockauv_eval_s* dockauv_eval;
+typedef struct dockauv_eval_io {
+    uint32_t struct_size;          /* sizeof(dockauv_eval_io): ABI check */
+    int32_t n_steps;               /* K >= 1 */
+    const float* rows_out;         /* [K][n_envs][n_obs + 2]: only the reward and done columns are read */
+    const float* terminal_obs;     /* nullable [K][n_envs][n_obs]: columns 0, 6 and 7 are read where a counted episode ends */
+    double* stats;                 /* [16] */
+} dockauv_eval_io;
+int dockauv_eval_create(dockauv_handle h, int max_episodes_per_env, dockauv_eval* out);
+int dockauv_eval_destroy(dockauv_eval e);   /* NULL: 0 */
+int dockauv_eval_begin(dockauv_eval e, const int32_t* targets /* device [n_envs], nullable */, int uniform_target, void* hip_stream);
+int dockauv_eval_scan(dockauv_handle h, dockauv_eval e, const dockauv_eval_io* io, void* hip_stream);
+int dockauv_eval_state(dockauv_eval e, int32_t** count, int32_t** target, float** ep_return, int32_t** ep_length, uint8_t** ep_outcome,
+                       float** carry_return, int32_t** carry_length);   /* each output nullable */
+
+/*
  * Reward normalisation: SB3 1.5's VecNormalize(norm_reward=True, norm_obs=False) with its RunningMeanStd -- every reward divided
  * by the running standard deviation of the discounted return, then clipped -- computed on the device from the reward and done
  * columns of a collection.  The terminal rewards of this env are in the hundreds (config/env_config.py: w_goal 400, w_col -300)
