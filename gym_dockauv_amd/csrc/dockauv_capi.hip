@@ -350,6 +350,7 @@ int init_handle(dockauv_handle h, const dockauv_config& c, int device) {
             fill_vehicle(h->a64.P.V[v], c.vehicle[v]);
             pack_hot(h->a64.P.H[v], h->a64.P.E, h->a64.P.V[v]);
         }
+        pack_tail(h->a64.P.Q, h->a64.P.E);
         h->a64.B = B;
     } else {
         fill_env(h->a32.P.E, *h);
@@ -357,6 +358,7 @@ int init_handle(dockauv_handle h, const dockauv_config& c, int device) {
             fill_vehicle(h->a32.P.V[v], c.vehicle[v]);
             pack_hot(h->a32.P.H[v], h->a32.P.E, h->a32.P.V[v]);
         }
+        pack_tail(h->a32.P.Q, h->a32.P.E);
         h->a32.B = B;
     }
     // the parameter block is read by the kernel from device memory (dockauv_device.h: ParamBlock)

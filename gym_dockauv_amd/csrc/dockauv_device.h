@@ -170,6 +170,47 @@ inline void pack_hot(HotP<T>& H, const EnvP<T>& E, const VehicleP<T>& V) {
     for (int i = 0; i < L_COUNT; ++i) H.lauv[i] = V.lauv[i];
 }
 
+// The scalars the wave roles read BEHIND the integrator, packed by role: COPIES of the EnvP values (pack_tail), three adjacent
+// 64-byte lines in float32, so that a role can request what it needs as one batch of wide scalar loads where it waits
+// anyway (dockauv_step.hip.inc: request_tail_ / pin_tail_).  Field names are EnvP's: the kernels that keep their loads at the
+// uses read the same expressions from EnvP.
+template <typename T>
+struct alignas(64) TailP {
+    // integrating wave (whoever decides `done`): navigation errors, done conditions, its three observations
+    T inv_log_tol, dtol, dmax, max_att;
+    int max_timesteps;
+    // ... and every role
+    int reset_mode, n_obs;
+    T inv_dmax;
+    // record completion (every wave of a ray group): reach of the fan, safety margin, slot counts
+    T ray_max, fan_cos, fan_sin, safety;
+    int max_cap, max_sph;
+    // pass waves (with ray_max and the slot counts in front)
+    int ray_pad, ray_pad_log2, n_rays, n_red;
+    T inv_ray_max, sum_beta;
+    // observation / resetter wave and bookkeeper
+    T inv_vel[6], inv_max_att, inv_log_tol_eps;
+    T w_d, w_dth, w_dpsi, w_phi, w_th, w_thdot, w_oa;
+    T w_done[5];
+};
+static_assert(sizeof(TailP<float>) == 192 && sizeof(TailP<double>) % 64 == 0, "whole 64-byte lines");
+
+template <typename T>
+inline void pack_tail(TailP<T>& Q, const EnvP<T>& E) {
+    Q = TailP<T>{};
+    Q.inv_dmax = E.inv_dmax; Q.inv_log_tol = E.inv_log_tol; Q.dtol = E.dtol; Q.dmax = E.dmax; Q.max_att = E.max_att;
+    Q.max_timesteps = E.max_timesteps; Q.reset_mode = E.reset_mode; Q.n_obs = E.n_obs;
+    Q.ray_max = E.ray_max; Q.fan_cos = E.fan_cos; Q.fan_sin = E.fan_sin; Q.safety = E.safety;
+    Q.max_cap = E.max_cap; Q.max_sph = E.max_sph;
+    Q.ray_pad = E.ray_pad; Q.ray_pad_log2 = E.ray_pad_log2; Q.n_rays = E.n_rays; Q.n_red = E.n_red;
+    Q.inv_ray_max = E.inv_ray_max; Q.sum_beta = E.sum_beta;
+    for (int i = 0; i < 6; ++i) Q.inv_vel[i] = E.inv_vel[i];
+    Q.inv_max_att = E.inv_max_att; Q.inv_log_tol_eps = E.inv_log_tol_eps;
+    Q.w_d = E.w_d; Q.w_dth = E.w_dth; Q.w_dpsi = E.w_dpsi; Q.w_phi = E.w_phi; Q.w_th = E.w_th; Q.w_thdot = E.w_thdot;
+    Q.w_oa = E.w_oa;
+    for (int i = 0; i < 5; ++i) Q.w_done[i] = E.w_done[i];
+}
+
 // Vehicle / reward / fan parameters (~2.5 KB in f32).  They live in a DEVICE buffer that persists across launches
 // (uploaded once by dockauv_create) and are read through a constant-address-space pointer: wave-uniform scalar loads
 // (s_load -> SGPR operands) that hit in L2 from the second launch on.  Passing them by value in the kernarg segment
@@ -179,12 +220,13 @@ inline void pack_hot(HotP<T>& H, const EnvP<T>& E, const VehicleP<T>& V) {
 // needs in front of stage 2, line-aligned (HotP).  The rule for reading the block: ONE batch of scalar loads per wave role,
 // requested where the role waits anyway (behind its row loads, in front of a barrier or a hand-over flag) and pinned
 // (pin_sgpr_), never a load that is awaited where its value is used -- each of those is a scalar-cache round trip on the
-// role's own instruction stream.
+// role's own instruction stream.  Q repeats what the roles read behind the integrator (TailP), appended: no older field moves.
 template <typename T, int NV>
 struct ParamBlock {
     EnvP<T> E;
     VehicleP<T> V[NV];
     HotP<T> H[NV];
+    TailP<T> Q;
 };
 
 // copy groups riding in the launch (dockauv_ride.h); plan == nullptr: none

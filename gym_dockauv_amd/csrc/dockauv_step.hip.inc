@@ -507,10 +507,14 @@ __device__ __forceinline__ void rhs_pinned_(const VP& V, const T att[3], const T
 // one from moving above it, which nothing needs once they are in registers), and behind the constant part of the control
 // force request_kinetics() asks for the second batch (request_hot_kinetics_), into the registers the input stage has given
 // back; pin_kinetics() awaits it behind the kinematics of stage 1 (some 30 vector instructions), which cover the round trip.
-template <typename T, int VK, bool SYM, int VOFF, bool HOTV = false, typename VP, typename EP, typename REQ = NoFetch, typename PIN = NoFetch>
+// request_tail() stands behind the last right-hand side, where the kinetics' registers are free again: the wave asks there for
+// what it reads behind the integrator (request_tail_), and the final sums and the post-step trigonometry cover the round trip.
+template <typename T, int VK, bool SYM, int VOFF, bool HOTV = false, typename VP, typename EP, typename REQ = NoFetch, typename PIN = NoFetch,
+          typename REQT = NoFetch>
 __device__ __forceinline__ void vehicle_step_(const VP& V, const EP& E, T y[9], T dpos[3], T u[kMaxU],
                                               const T act[kMaxU], const T nuc[3], T* g_u, long S, unsigned ul, T& psi_lo,
-                                              const REQ& request_kinetics = REQ(), const PIN& pin_kinetics = PIN()) {
+                                              const REQ& request_kinetics = REQ(), const PIN& pin_kinetics = PIN(),
+                                              const REQT& request_tail = REQT()) {
     const int n_u = (VK == VK_LAUV) ? 3 : (VK == VK_JOY ? 6 : V.n_u);
     const T one_m_alpha = T(1) - E.lp_alpha;
 #pragma unroll
@@ -589,6 +593,7 @@ __device__ __forceinline__ void vehicle_step_(const VP& V, const EP& E, T y[9], 
     }
     rhs_<T, VK, SYM, true>(V, ys, ys + 3, nuc, tau_c, u, pd, k1, k1 + 3);   // k5 reuses k1's registers
     DOCKAUV_STAMP_PIN(21, k1, 9);
+    if (HOTV) request_tail();
 #pragma unroll
     for (int i = 0; i < 3; ++i) dpos[i] += b5 * pd[i];
 #pragma unroll
@@ -974,6 +979,68 @@ __device__ __forceinline__ void pin_hot_kinetics_(HotRegs<T>& R) {
     }
 }
 
+// What a wave role reads BEHIND the integrator (dockauv_device.h: TailP), as one batch per role.  G: the groups of the block
+// the role needs -- they are adjacent in TailP, so a role's batch is two or three wide loads.  request_tail_ issues every load
+// and nothing else (nothing may be scheduled across its end), pin_tail_ awaits them and keeps them in SGPRs (pin_sgpr_); the
+// caller puts work that needs none of them in between.  Q: the tail's scalars, RC: the record completion's, RQ: the pass waves'
+// (step_body).  Fields of a group the role did not ask for stay unset and are never read by it.
+enum TailGroup { kTgDone = 1, kTgAll = 2, kTgRec = 4, kTgPass = 8, kTgObs = 16, kTgBk = 32 };
+template <int G, typename TP, typename QT, typename RCT, typename RQT>
+__device__ __forceinline__ void request_tail_(const TP& P, QT& Q, RCT& RC, RQT& RQ) {
+    if (G & kTgDone) {
+        Q.inv_log_tol = P.inv_log_tol; Q.dtol = P.dtol; Q.dmax = P.dmax; Q.max_att = P.max_att; Q.max_timesteps = P.max_timesteps;
+    }
+    if (G & kTgAll) { Q.reset_mode = P.reset_mode; Q.n_obs = P.n_obs; Q.inv_dmax = P.inv_dmax; }
+    if (G & kTgRec) { RC.ray_max = P.ray_max; RC.fan_cos = P.fan_cos; RC.fan_sin = P.fan_sin; RC.safety = P.safety; }
+    if (G & kTgPass) {
+        RQ.ray_max = P.ray_max; RQ.max_cap = P.max_cap; RQ.max_sph = P.max_sph; RQ.pad = P.ray_pad; RQ.pad_log2 = P.ray_pad_log2;
+        RQ.n_rays = P.n_rays; RQ.n_red = P.n_red; RQ.inv_ray_max = P.inv_ray_max; RQ.sum_beta = P.sum_beta;
+    }
+    if (G & kTgObs) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) Q.inv_vel[k] = P.inv_vel[k];
+        Q.inv_max_att = P.inv_max_att;
+    }
+    if (G & kTgBk) {
+        Q.inv_log_tol_eps = P.inv_log_tol_eps;
+        Q.w_d = P.w_d; Q.w_dth = P.w_dth; Q.w_dpsi = P.w_dpsi; Q.w_phi = P.w_phi; Q.w_th = P.w_th; Q.w_thdot = P.w_thdot;
+        Q.w_oa = P.w_oa;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) Q.w_done[k] = P.w_done[k];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+template <int G, typename QT, typename RCT, typename RQT>
+__device__ __forceinline__ void pin_tail_(QT& Q, RCT& RC, RQT& RQ) {
+    __builtin_amdgcn_sched_barrier(0);
+    if (G & kTgDone) {
+        Q.inv_log_tol = pin_sgpr_(Q.inv_log_tol); Q.dtol = pin_sgpr_(Q.dtol); Q.dmax = pin_sgpr_(Q.dmax);
+        Q.max_att = pin_sgpr_(Q.max_att); Q.max_timesteps = pin_sgpr_(Q.max_timesteps);
+    }
+    if (G & kTgAll) { Q.reset_mode = pin_sgpr_(Q.reset_mode); Q.n_obs = pin_sgpr_(Q.n_obs); Q.inv_dmax = pin_sgpr_(Q.inv_dmax); }
+    if (G & kTgRec) {
+        RC.ray_max = pin_sgpr_(RC.ray_max); RC.fan_cos = pin_sgpr_(RC.fan_cos); RC.fan_sin = pin_sgpr_(RC.fan_sin);
+        RC.safety = pin_sgpr_(RC.safety);
+    }
+    if (G & kTgPass) {
+        RQ.ray_max = pin_sgpr_(RQ.ray_max); RQ.max_cap = pin_sgpr_(RQ.max_cap); RQ.max_sph = pin_sgpr_(RQ.max_sph);
+        RQ.pad = pin_sgpr_(RQ.pad); RQ.pad_log2 = pin_sgpr_(RQ.pad_log2); RQ.n_rays = pin_sgpr_(RQ.n_rays);
+        RQ.n_red = pin_sgpr_(RQ.n_red); RQ.inv_ray_max = pin_sgpr_(RQ.inv_ray_max); RQ.sum_beta = pin_sgpr_(RQ.sum_beta);
+    }
+    if (G & kTgObs) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) Q.inv_vel[k] = pin_sgpr_(Q.inv_vel[k]);
+        Q.inv_max_att = pin_sgpr_(Q.inv_max_att);
+    }
+    if (G & kTgBk) {
+        Q.inv_log_tol_eps = pin_sgpr_(Q.inv_log_tol_eps);
+        Q.w_d = pin_sgpr_(Q.w_d); Q.w_dth = pin_sgpr_(Q.w_dth); Q.w_dpsi = pin_sgpr_(Q.w_dpsi); Q.w_phi = pin_sgpr_(Q.w_phi);
+        Q.w_th = pin_sgpr_(Q.w_th); Q.w_thdot = pin_sgpr_(Q.w_thdot); Q.w_oa = pin_sgpr_(Q.w_oa);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) Q.w_done[k] = pin_sgpr_(Q.w_done[k]);
+    }
+}
+
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the wave's global stores
 // (s_waitcnt vmcnt(0)): every hand-over in this kernel goes through LDS, and the state / input write-backs that are
 // in flight at that point have no reader inside the launch.  A single-wave group needs no s_barrier at all: LDS
@@ -1094,6 +1161,22 @@ constexpr bool hot_params_() {
     if (VK != VK_JOY) return false;
     if (KIND == 1) return !(RAYS && NT == 64);
     if (KIND == 2) return RAYS ? NT != 256 : NT == 64;
+    return true;
+}
+
+// Which kernels fetch what their roles read behind the integrator in one batch per role (request_tail_ / pin_tail_, TailP):
+// kernels with a hot block -- the integrating wave's request stands in the registers the kinetics batch has given back -- that
+// kept the guard rails with it (DESIGN.md section 3, profiles/tail_params/kernel_usage.txt); the others, and every full (LOG)
+// instantiation, keep reading EnvP at the uses.
+template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool LOG, bool TERM, bool WB, int KIND>
+constexpr bool tail_params_() {
+    if (!hot_params_<T, VK, SYM, RAYS, EPG, NT, LOG, TERM, WB, KIND>()) return false;
+    // ray kernels of four waves only: a one-wave group (everything is the integrating wave's) took one more SGPR spill with its
+    // batch; in the sensor-free kernels the batch removed no round trip from the straight-line path (their one batch already
+    // stood behind the trigonometry; the kernarg word that used to ride in its wait got a wait of its own); in groups of eight
+    // waves the integrating wave takes ray passes, whose scalars need a batch of their own in front of the hand-over barrier:
+    // the plain and the riding kernel took two more SGPR spills, the other two lost no round trip behind the integrator
+    if (!RAYS || NT / EPG != 4) return false;
     return true;
 }
 
@@ -1278,6 +1361,39 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
     // cost config 3's kernel four more spills)
     constexpr bool HOT_WACT = !RAYS;
     HotRegs<T> HR;   // (HOT: the integrating wave's parameters, see fetch_hot_input_)
+    // TAIL: one batch per role for what is read behind the integrator (request_tail_).  The integrating wave asks behind its
+    // last right-hand side and awaits behind the post-step trigonometry -- G0: what IT reads there; in groups of four waves it
+    // takes no ray pass (NO_PASS) and asks neither for the pass scalars nor for the lane table --, the other waves ask where
+    // they idle in front of the hand-over barrier (GH).
+    constexpr bool TAIL = tail_params_<T, VK, SYM, RAYS, EPG, NT, LOG, TERM, WB, KIND>();
+    constexpr bool NO_PASS = SHARE_NAV && NT / EPG == 4 && !MIXED2;
+    constexpr int G0 = kTgDone | kTgAll | (RAYS ? kTgRec : 0) | ((RAYS && !DUAL) ? kTgPass : 0) | (QUAD ? 0 : kTgObs) | (DUAL ? 0 : kTgBk);
+    constexpr int GH = kTgAll | (SHARE_NAV ? 0 : kTgDone) | (RAYS ? (kTgRec | kTgPass) : 0) | kTgObs | kTgBk;
+    // the tail's parameters (filled below: one batch of scalar loads, pinned -- see pin_sgpr_), the pass waves' and the record
+    // completion's
+    struct {
+        T inv_dmax, inv_log_tol, inv_log_tol_eps, inv_max_att, inv_vel[6], dtol, dmax, max_att;
+        T w_d, w_dth, w_dpsi, w_phi, w_th, w_thdot, w_oa, w_done[5];
+        int max_timesteps, reward_set, n_obs, reset_mode;
+    } Q;
+    struct {
+        int pad, pad_log2, n_rays, n_red, max_cap, max_sph;
+        T ray_max, inv_ray_max, sum_beta;
+    } RQ;
+    if (!TAIL) {   // (TAIL: no value but the role's own batch -- a zero would make a per-lane merge of it)
+        __builtin_memset(&RQ, 0, sizeof(RQ));
+    }
+    struct { T ray_max, fan_cos, fan_sin, safety; } RC;
+    // (the record completion reads a TAIL kernel's pinned copy or, in the kernels that keep their loads at the uses, EnvP)
+    auto rc_ray_max = [&]() -> T { if constexpr (TAIL) return RC.ray_max; else return E.ray_max; };
+    auto rc_fan_cos = [&]() -> T { if constexpr (TAIL) return RC.fan_cos; else return E.fan_cos; };
+    auto rc_fan_sin = [&]() -> T { if constexpr (TAIL) return RC.fan_sin; else return E.fan_sin; };
+    auto rc_safety = [&]() -> T { if constexpr (TAIL) return RC.safety; else return E.safety; };
+    // What WHOLE waves read behind the integrator -- the terminal copy and the bfloat16 tile store run on every lane of a wave,
+    // the lanes of a partial group's missing envs included -- has a source of its own.  The integrating wave's batch is requested
+    // and pinned under its lane mask (owner), so Q holds nothing on its other lanes: every thread requests these two words
+    // itself, outside every mask, in front of the hand-over barrier, and pins them behind it (TAIL; the others: Q's, below).
+    struct { int n_obs, reset_mode; } WQ;
     // episode-storage trace of selected envs (include/dockauv.h: dockauv_trace_*) and its row in the ring for this step
     typedef const __attribute__((address_space(1))) TraceDev GTrace;
     GTrace* const TR = LOG ? (GTrace*)(uintptr_t)IO.trace : nullptr;
@@ -1347,6 +1463,11 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
             constexpr int h0 = (int)(__builtin_offsetof(PBlock, H) / 4), hw = (int)(sizeof(HotP<T>) / 4);
 #pragma unroll
             for (int off = h0; off < h0 + hw; off += 16) param_touch ^= pw[off];
+            if (TAIL) {   // (the roles' batches behind the integrator)
+                constexpr int q0 = (int)(__builtin_offsetof(PBlock, Q) / 4), qw = (int)(sizeof(TailP<T>) / 4);
+#pragma unroll
+                for (int off = q0; off < q0 + qw; off += 16) param_touch ^= pw[off];
+            }
 #pragma unroll
             for (int off = 0; off < (int)(sizeof(EnvP<T>) / 4); off += 16) param_touch ^= pw[off];
         } else {
@@ -1517,7 +1638,8 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
         if constexpr (HOT) {
             vehicle_step_<T, VK, SYM, VOFF, true>(HR.V, HR, st + 3, dpos, u, act, nuc, g_u, S, ul, psi_lo,
                                                   [&]() { request_hot_kinetics_<T, VK>(PB->H[0], HR); },
-                                                  [&]() { pin_hot_kinetics_<T, VK>(HR); });
+                                                  [&]() { pin_hot_kinetics_<T, VK>(HR); },
+                                                  [&]() { if constexpr (TAIL) request_tail_<G0>(PB->Q, Q, RC, RQ); });
         } else if (VK == VK_MIXED) {
             if (vid == 0) {
                 vehicle_step_<T, VK_JOY, SYM, VOFF>(PB->V[0], E, st + 3, dpos, u, act, nuc, g_u, S, ul, psi_lo);
@@ -1599,9 +1721,25 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
                 for (int k = 0; k < 3; ++k) o4[k] = nuc[k];
             }
         }
+        // (TAIL: the integrating wave's batch, requested behind the last right-hand side, has landed behind the trigonometry.
+        // Request and pin stand under the wave's lane mask: on this wave only the lanes that integrate an env hold them, and only
+        // those lanes read them -- every later use on this wave is the role's own, under the same mask (record completion,
+        // w0_tail); what a whole wave reads comes from WQ.)
+        if constexpr (TAIL) pin_tail_<G0>(Q, RC, RQ);
     }
 
     if (RAISE_PRIO && wv == 0) __builtin_amdgcn_s_setprio(0);
+    // TAIL: the other waves' batch, where they idle in front of the hand-over barrier
+    if constexpr (TAIL && DUAL) {
+        static_assert(NO_PASS, "an integrating wave that takes ray passes would need their scalars here");
+        if (wv != 0) {
+            request_tail_<GH>(PB->Q, Q, RC, RQ);
+            pin_tail_<GH>(Q, RC, RQ);
+        }
+    }
+    // (every thread, outside every mask: the line is in the scalar cache by now, and the wait of the pose's LDS writes in front
+    // of the barrier covers the trip)
+    if constexpr (TAIL) { WQ.n_obs = PB->Q.n_obs; WQ.reset_mode = PB->Q.reset_mode; }
     // what the bookkeeper needs from the env phase: new state (12), V_c, action penalty, |euler_dot|^2, collision
     // (SHARE_NAV kernels: the integrating wave alone needs position and heading -- navigation errors -- and writes the
     // state of the envs that go on itself; V_c only travels with a reset, whose resetter takes the new one; the collision
@@ -1635,21 +1773,22 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
     // stage's parameters are fetched as ONE batch of scalar loads; both are requested here, before the record
     // completion, so that they have landed when the stage starts (they used to be fetched one by one at its start:
     // a dozen exposed scalar-cache round trips, four integer divisions and a global load in front of the first pass)
-    struct {
-        int pad, pad_log2, n_rays, n_red, max_cap, max_sph;
-        T ray_max, inv_ray_max, sum_beta;
-    } RQ{};
+    // (TAIL: the scalars came with the role's batch; an integrating wave that takes no pass needs no ray either)
     T lr_bx = T(0), lr_by = T(0), lr_bz = T(0), lr_beta = T(0);
     int lr_cell = 0;
     if (RAYS && (!LOG || E.n_rays <= 64)) {
-        RQ.pad = E.ray_pad; RQ.pad_log2 = E.ray_pad_log2; RQ.n_rays = E.n_rays; RQ.n_red = E.n_red;
-        RQ.max_cap = E.max_cap; RQ.max_sph = E.max_sph;
-        RQ.ray_max = E.ray_max; RQ.inv_ray_max = E.inv_ray_max; RQ.sum_beta = E.sum_beta;
-        typedef const __attribute__((address_space(1))) T GT;
-        typedef const __attribute__((address_space(1))) int GI;
-        GT* const lt = (GT*)(uintptr_t)B.lane_tab + (unsigned)(tid % 64) * 4u;
-        lr_bx = lt[0]; lr_by = lt[1]; lr_bz = lt[2]; lr_beta = lt[3];
-        lr_cell = ((GI*)(uintptr_t)B.lane_cell)[tid % 64];
+        if (!TAIL) {
+            RQ.pad = E.ray_pad; RQ.pad_log2 = E.ray_pad_log2; RQ.n_rays = E.n_rays; RQ.n_red = E.n_red;
+            RQ.max_cap = E.max_cap; RQ.max_sph = E.max_sph;
+            RQ.ray_max = E.ray_max; RQ.inv_ray_max = E.inv_ray_max; RQ.sum_beta = E.sum_beta;
+        }
+        if (!(TAIL && NO_PASS && wv == 0)) {
+            typedef const __attribute__((address_space(1))) T GT;
+            typedef const __attribute__((address_space(1))) int GI;
+            GT* const lt = (GT*)(uintptr_t)B.lane_tab + (unsigned)(tid % 64) * 4u;
+            lr_bx = lt[0]; lr_by = lt[1]; lr_bz = lt[2]; lr_beta = lt[3];
+            lr_cell = ((GI*)(uintptr_t)B.lane_cell)[tid % 64];
+        }
     }
 
     // ------------------------------------------------------------------------------------------ tail (definitions)
@@ -1661,33 +1800,31 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
     // roles behind that barrier (as the full instantiation still has them) the group spent ~2 000 cycles at 4 waves per
     // SIMD there while most of its waves had idled through the ray stage (config 3: ~1 env in 100 takes a pass).
     constexpr bool EARLY = EARLY_;
-    // the tail's parameters, fetched as one batch of scalar loads and pinned (see pin_sgpr_)
-    struct {
-        T inv_dmax, inv_log_tol, inv_log_tol_eps, inv_max_att, inv_vel[6], dtol, dmax, max_att;
-        T w_d, w_dth, w_dpsi, w_phi, w_th, w_thdot, w_oa, w_done[5];
-        int max_timesteps, reward_set, n_obs, reset_mode;
-    } Q;
-    Q.inv_dmax = E.inv_dmax; Q.inv_log_tol = E.inv_log_tol; Q.inv_log_tol_eps = E.inv_log_tol_eps;
-    Q.inv_max_att = E.inv_max_att; Q.dtol = E.dtol; Q.dmax = E.dmax; Q.max_att = E.max_att;
-    Q.w_d = E.w_d; Q.w_dth = E.w_dth; Q.w_dpsi = E.w_dpsi; Q.w_phi = E.w_phi; Q.w_th = E.w_th;
-    Q.w_thdot = E.w_thdot; Q.w_oa = E.w_oa;
-    Q.max_timesteps = E.max_timesteps; Q.reward_set = E.reward_set; Q.n_obs = E.n_obs; Q.reset_mode = E.reset_mode;
+    // the tail's parameters, fetched as one batch of scalar loads and pinned (see pin_sgpr_) -- TAIL: per role, above
+    if constexpr (!TAIL) {
+        Q.inv_dmax = E.inv_dmax; Q.inv_log_tol = E.inv_log_tol; Q.inv_log_tol_eps = E.inv_log_tol_eps;
+        Q.inv_max_att = E.inv_max_att; Q.dtol = E.dtol; Q.dmax = E.dmax; Q.max_att = E.max_att;
+        Q.w_d = E.w_d; Q.w_dth = E.w_dth; Q.w_dpsi = E.w_dpsi; Q.w_phi = E.w_phi; Q.w_th = E.w_th;
+        Q.w_thdot = E.w_thdot; Q.w_oa = E.w_oa;
+        Q.max_timesteps = E.max_timesteps; Q.reward_set = E.reward_set; Q.n_obs = E.n_obs; Q.reset_mode = E.reset_mode;
 #pragma unroll
-    for (int k = 0; k < 6; ++k) Q.inv_vel[k] = E.inv_vel[k];
+        for (int k = 0; k < 6; ++k) Q.inv_vel[k] = E.inv_vel[k];
 #pragma unroll
-    for (int k = 0; k < 5; ++k) Q.w_done[k] = E.w_done[k];
-    Q.inv_dmax = pin_sgpr_(Q.inv_dmax); Q.inv_log_tol = pin_sgpr_(Q.inv_log_tol);
-    Q.inv_log_tol_eps = pin_sgpr_(Q.inv_log_tol_eps); Q.inv_max_att = pin_sgpr_(Q.inv_max_att);
-    Q.dtol = pin_sgpr_(Q.dtol); Q.dmax = pin_sgpr_(Q.dmax); Q.max_att = pin_sgpr_(Q.max_att);
-    Q.w_d = pin_sgpr_(Q.w_d); Q.w_dth = pin_sgpr_(Q.w_dth); Q.w_dpsi = pin_sgpr_(Q.w_dpsi);
-    Q.w_phi = pin_sgpr_(Q.w_phi); Q.w_th = pin_sgpr_(Q.w_th); Q.w_thdot = pin_sgpr_(Q.w_thdot);
-    Q.w_oa = pin_sgpr_(Q.w_oa);
-    Q.max_timesteps = pin_sgpr_(Q.max_timesteps); Q.reward_set = pin_sgpr_(Q.reward_set); Q.n_obs = pin_sgpr_(Q.n_obs);
-    Q.reset_mode = pin_sgpr_(Q.reset_mode);
+        for (int k = 0; k < 5; ++k) Q.w_done[k] = E.w_done[k];
+        Q.inv_dmax = pin_sgpr_(Q.inv_dmax); Q.inv_log_tol = pin_sgpr_(Q.inv_log_tol);
+        Q.inv_log_tol_eps = pin_sgpr_(Q.inv_log_tol_eps); Q.inv_max_att = pin_sgpr_(Q.inv_max_att);
+        Q.dtol = pin_sgpr_(Q.dtol); Q.dmax = pin_sgpr_(Q.dmax); Q.max_att = pin_sgpr_(Q.max_att);
+        Q.w_d = pin_sgpr_(Q.w_d); Q.w_dth = pin_sgpr_(Q.w_dth); Q.w_dpsi = pin_sgpr_(Q.w_dpsi);
+        Q.w_phi = pin_sgpr_(Q.w_phi); Q.w_th = pin_sgpr_(Q.w_th); Q.w_thdot = pin_sgpr_(Q.w_thdot);
+        Q.w_oa = pin_sgpr_(Q.w_oa);
+        Q.max_timesteps = pin_sgpr_(Q.max_timesteps); Q.reward_set = pin_sgpr_(Q.reward_set); Q.n_obs = pin_sgpr_(Q.n_obs);
+        Q.reset_mode = pin_sgpr_(Q.reset_mode);
 #pragma unroll
-    for (int k = 0; k < 6; ++k) Q.inv_vel[k] = pin_sgpr_(Q.inv_vel[k]);
+        for (int k = 0; k < 6; ++k) Q.inv_vel[k] = pin_sgpr_(Q.inv_vel[k]);
 #pragma unroll
-    for (int k = 0; k < 5; ++k) Q.w_done[k] = pin_sgpr_(Q.w_done[k]);
+        for (int k = 0; k < 5; ++k) Q.w_done[k] = pin_sgpr_(Q.w_done[k]);
+        WQ.n_obs = Q.n_obs; WQ.reset_mode = Q.reset_mode;
+    }
 
     // 9. navigation errors (envs/docking3d.py:404-413) -- both halves of the tail need them
     // (the squared distance is formed by explicit fused multiply-adds in ONE order wherever it is needed: the roles
@@ -2146,6 +2283,7 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
             for (int k = 0; k < 9; ++k) lds_pose[(5 + k) * EPG + ul] = R1[k];
         }
         if (!SOLO) lds_barrier_<NT>();   // raw obstacle records, slot counts and the pose are in LDS
+        if constexpr (TAIL) { WQ.n_obs = pin_sgpr_(WQ.n_obs); WQ.reset_mode = pin_sgpr_(WQ.reset_mode); }
         if (env0 + (int)ule < A.n_envs) {
             const T* P = lds_pose + ule;
             const int ncap = SOLO ? ncap_r : (int)P[0 * EPG], nsph = SOLO ? nsph_r : (int)P[1 * EPG];
@@ -2173,8 +2311,8 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
                 o[7] = len;
                 o[8] = rad * rad;
                 o[9] = oa_par - len;
-                const bool may = capsule_may_be_hit_<T>(o[0], o[3], px * px + py * py + pz * pz, oa_par, len, rad, E.ray_max,
-                                                        E.fan_cos, E.fan_sin);
+                const bool may = capsule_may_be_hit_<T>(o[0], o[3], px * px + py * py + pz * pz, oa_par, len, rad, rc_ray_max(),
+                                                        rc_fan_cos(), rc_fan_sin());
                 // collision_capsule_sphere / dist_line_point (objects/shape.py:195-210, 393-417):
                 // hypot(max(s, t, 0), |(p - l1) x d|) with s = (l1 - p).d = -oa_par, t = (p - l2).d = oa_par - |ba|
                 // and |(p - l1) x d| = |oa_perp| for the unit axis d
@@ -2182,7 +2320,7 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
                 T hh = s_ > t_ ? s_ : t_;
                 hh = hh > T(0) ? hh : T(0);
                 const T dist = sqrt_(hh * hh + (px * px + py * py + pz * pz));   // np.hypot
-                hits_body = dist <= rad + E.safety;
+                hits_body = dist <= rad + rc_safety();
                 return may;
             };
             if (REGREC_OK && regrec) {
@@ -2220,8 +2358,8 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
                 cp[7 * EPG] = len;
                 cp[8 * EPG] = rad * rad;
                 cp[9 * EPG] = oa_par - len;
-                if (capsule_may_be_hit_<T>(cp[0 * EPG], cp[3 * EPG], px * px + py * py + pz * pz, oa_par, len, rad, E.ray_max,
-                                           E.fan_cos, E.fan_sin)) {
+                if (capsule_may_be_hit_<T>(cp[0 * EPG], cp[3 * EPG], px * px + py * py + pz * pz, oa_par, len, rad, rc_ray_max(),
+                                           rc_fan_cos(), rc_fan_sin())) {
                     if (SOLO) cmask_r |= 1u << c;
                     else atomicOr(reinterpret_cast<unsigned int*>(lds_pose + 14 * EPG + ule), 1u << c);
                 }
@@ -2229,7 +2367,7 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
                 T hh = s_ > t_ ? s_ : t_;
                 hh = hh > T(0) ? hh : T(0);
                 const T dist = sqrt_(hh * hh + (px * px + py * py + pz * pz));   // np.hypot
-                col = col || (dist <= rad + E.safety);
+                col = col || (dist <= rad + rc_safety());
             }
             for (int s_i = wv; s_i < nsph; s_i += W) {
                 T* sp = lds_sph + (size_t)s_i * kSphFields * EPG + ule;
@@ -2241,12 +2379,12 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
                 sp[2 * EPG] = R1[2] * ocx + R1[5] * ocy + R1[8] * ocz;
                 sp[3 * EPG] = rad * rad;
                 const T dist = sqrt_(d2);
-                if (sphere_may_be_hit_<T>(sp[0 * EPG], d2, dist, rad, E.ray_max, E.fan_cos, E.fan_sin)) {
+                if (sphere_may_be_hit_<T>(sp[0 * EPG], d2, dist, rad, rc_ray_max(), rc_fan_cos(), rc_fan_sin())) {
                     if (SOLO) smask_r |= 1u << s_i;
                     else atomicOr(reinterpret_cast<unsigned int*>(lds_pose + 15 * EPG + ule), 1u << s_i);
                 }
                 // collision_sphere_spheres (objects/shape.py:182-192)
-                col = col || (dist <= E.safety + rad);
+                col = col || (dist <= rc_safety() + rad);
             }
             if (SOLO) collision = col; else lds_col[wv * EPG + ule] = col ? T(1) : T(0);
             DOCKAUV_STAMP(15);   // obstacle records complete
@@ -2664,8 +2802,8 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
         // rows go to terminal_obs [n_envs][n_obs] (written only where done) and are zeroed in the tile; one wave, a few
         // rows per step
         if (tid < 64) {
-            const int n_obs_ = Q.n_obs;
-            const bool dn = (tid < n_valid) && (lds_obs[(size_t)tid * row_len + n_obs_ + 1] != 0.0f) && Q.reset_mode != 0;
+            const int n_obs_ = WQ.n_obs;   // (whole wave: see WQ)
+            const bool dn = (tid < n_valid) && (lds_obs[(size_t)tid * row_len + n_obs_ + 1] != 0.0f) && WQ.reset_mode != 0;
             unsigned long long m = __ballot(dn);
             float* const to0 = term_out + (size_t)env0 * n_obs_;
             while (m) {
@@ -2684,7 +2822,7 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
         // packed rows for a half-precision gather (one learner over several GPUs: the rows cross xGMI every step and the
         // links, not the kernels, set the pace -- DESIGN.md section 7): observation columns as bfloat16, round to nearest
         // even, two per word; reward and done stay float32.  Word idx of the group's rows -> (row, word) by mul_hi.
-        const int n_obs_ = Q.n_obs, npair = (n_obs_ + 1) >> 1, wpr = pin_sgpr_(E.bf16_wpr);
+        const int n_obs_ = WQ.n_obs, npair = (n_obs_ + 1) >> 1, wpr = pin_sgpr_(E.bf16_wpr);
         const unsigned magic = pin_sgpr_(E.bf16_magic);
         const int totalw = n_valid * wpr;
         unsigned* const dstw = reinterpret_cast<unsigned*>(IO.obs) + (size_t)env0 * wpr;

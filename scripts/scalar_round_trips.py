@@ -13,7 +13,9 @@ The float32 and the resident-sequence translation units are compiled with the fl
   trips-env                   round trips between the first vector load and the fifth right-hand side, in layout order: from
                               the first `global_load` to the fifth `v_rcp_f32` behind it (rhs_ divides by cos(theta) once and
                               nothing in front of the stages divides; the mixed kernels lay out two vehicle models: the tenth)
-Only `s_load*`, `s_waitcnt`, `global_load*` and `v_rcp_f32` are looked at."""
+  trips-tail                  round trips behind the integrator, in layout order: from that fifth (mixed: tenth) `v_rcp_f32` to the
+                              first `s_endpgm` behind it
+Only `s_load*`, `s_waitcnt`, `global_load*`, `v_rcp_f32` and `s_endpgm` are looked at."""
 import os
 import re
 import subprocess
@@ -74,7 +76,7 @@ def analyse(asm, remarks):
                 parts = ln.strip().split(None, 1)
                 lines.append((parts[0], parts[1] if len(parts) > 1 else ""))
         first = next((i for i, (op, _) in enumerate(lines) if op.startswith("global_load")), None)
-        env = "-"
+        env = tail = "-"
         if first is not None:
             need, seen, end = (10 if vk == 3 else 5), 0, None
             for i in range(first, len(lines)):
@@ -85,13 +87,15 @@ def analyse(asm, remarks):
                         break
             if end is not None:
                 env = str(count_trips(lines[first:end]))
+                stop = next((i for i in range(end, len(lines)) if lines[i][0] == "s_endpgm"), len(lines))
+                tail = str(count_trips(lines[end:stop]))
         u = re.search(re.escape(nm) + r".*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?SGPRs Spill: (\d+)", remarks, re.S)
         vg, scr, ssp = u.groups() if u else ("?",) * 3
         what = "full" if log else ("term" if term else ("wb" if wb else "plain"))
         name = f"{kind:16s} {VK[vk]:8s} sym={int(sym)} rays={int(rays)} threads={nt:3d} {what:5s}"
         n_load = sum(1 for op, _ in lines if op.startswith("s_load"))
         rows.append((kind, not sym, log, vk, not rays, -nt, what,
-                     f"{name} | vgpr {vg:>3s} sgpr-spill {ssp:>3s} scratch {scr:>3s} | s_load {n_load:3d} trips {count_trips(lines):3d} trips-env {env:>3s}"))
+                     f"{name} | vgpr {vg:>3s} sgpr-spill {ssp:>3s} scratch {scr:>3s} | s_load {n_load:3d} trips {count_trips(lines):3d} trips-env {env:>3s} trips-tail {tail:>3s}"))
     return rows
 
 
@@ -100,7 +104,8 @@ def diff(before, after):
         t = {}
         for ln in open(path):
             if "|" in ln:
-                t[ln.split("|")[0].strip()] = [int(x) if x.isdigit() else None for x in re.findall(r"(?:vgpr|sgpr-spill|scratch|trips|trips-env) +(\S+)", ln)]
+                v = [int(x) if x.isdigit() else None for x in re.findall(r"(?:vgpr|sgpr-spill|scratch|trips|trips-env|trips-tail) +(\S+)", ln)]
+                t[ln.split("|")[0].strip()] = (v + [None])[:6]   # (tables older than the trips-tail column)
         return t
     b, a = table(before), table(after)
     bad = 0
@@ -108,12 +113,12 @@ def diff(before, after):
         if k not in b:
             print(f"{k}: new")
             continue
-        (v0, s0, c0, t0, e0), (v1, s1, c1, t1, e1) = b[k], a[k]
+        (v0, s0, c0, t0, e0, l0), (v1, s1, c1, t1, e1, l1) = b[k], a[k]
         broken = (v1 > 128) or (c1 > c0) or (s1 > s0)
         bad += broken
-        if broken or (v0, s0, c0, t0, e0) != (v1, s1, c1, t1, e1):
-            print(f"{k}: vgpr {v0} -> {v1}, sgpr-spill {s0} -> {s1}, scratch {c0} -> {c1}, trips {t0} -> {t1}, trips-env {e0} -> {e1}"
-                  + ("   ** GUARD RAIL **" if broken else ""))
+        if broken or (v0, s0, c0, t0, e0, l0) != (v1, s1, c1, t1, e1, l1):
+            print(f"{k}: vgpr {v0} -> {v1}, sgpr-spill {s0} -> {s1}, scratch {c0} -> {c1}, trips {t0} -> {t1}, trips-env {e0} -> {e1}, "
+                  f"trips-tail {l0} -> {l1}" + ("   ** GUARD RAIL **" if broken else ""))
     print(f"{len(a)} kernels, {bad} over a guard rail (VGPRs <= 128, no scratch added, no more SGPR spills)")
     return bad
 
