@@ -26,6 +26,7 @@ struct dockauv_env_s {
     bool has_rays = false;
     bool sym = false;
     int threads = 64;
+    bool no_current = false;   // no water current in any env (dockauv_device.h: no_current_after_write); cleared by dockauv_set_field
     dockauv::Buffers B{};
     std::vector<void*> allocs;
     dockauv::KernelArgs<float, 2> a32{};

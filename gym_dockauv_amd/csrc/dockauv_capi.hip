@@ -267,6 +267,7 @@ int init_handle(dockauv_handle h, const dockauv_config& c, int device) {
     if (c.n_vehicles == 2 && c.vehicle[1].n_u > h->n_u_max) h->n_u_max = c.vehicle[1].n_u;
     h->has_rays = (c.max_capsules + c.max_spheres) > 0;
     h->threads = choose_threads(h->f64, c.n_envs, h->n_rays, c.max_capsules, c.max_spheres, c.n_vehicles, c.threads_per_group);
+    h->no_current = scenario_without_current(c.scenario);   // (the current rows start as zeros: dalloc)
     if (c.n_vehicles == 2) {
         if (!(c.vehicle[0].kind == DOCKAUV_VEH_CONSTB && b_is_diagonal(c.vehicle[0]) && c.vehicle[1].kind == DOCKAUV_VEH_LAUV))
             return fail(h, DOCKAUV_E_INVALID, "mixed batches support vehicle[0] = diagonal-B (BlueROV2 joystick), vehicle[1] = LAUV");
@@ -377,7 +378,8 @@ int init_handle(dockauv_handle h, const dockauv_config& c, int device) {
 StepRequest step_request(dockauv_handle h, const dockauv_step_io& io, bool ride) {
     const bool extras = io.noise || io.reward_terms || io.conditions || io.nav || io.ray_dist || io.state_dot || h->trace_dev || h->cfg.device_noise;
     return StepRequest{h->f64, h->sym, h->vk, h->has_rays, h->threads, h->cfg.n_envs, ceil_log2(h->n_rays), h->cfg.reset_mode,
-                       h->cfg.reward_set, extras, io.terminal_obs != nullptr, io.pack_reward_done == 2 ? 2 : (io.pack_reward_done ? 1 : 0), ride};
+                       h->cfg.reward_set, extras, io.terminal_obs != nullptr, io.pack_reward_done == 2 ? 2 : (io.pack_reward_done ? 1 : 0), ride,
+                       h->no_current};
 }
 
 }  // namespace
@@ -497,6 +499,12 @@ int dockauv_destroy(dockauv_handle h) {
 
 int dockauv_n_obs(dockauv_handle h) { return h ? h->n_obs : DOCKAUV_E_INVALID; }
 int dockauv_threads_per_group(dockauv_handle h) { return h ? h->threads : DOCKAUV_E_INVALID; }
+int dockauv_step_uses_current(dockauv_handle h) {
+    if (!h) return DOCKAUV_E_INVALID;
+    dockauv_step_io plain{};
+    plain.pack_reward_done = 1;
+    return select_step(step_request(h, plain, false)).NOCUR ? 0 : 1;
+}
 int dockauv_n_rays(dockauv_handle h) { return h ? h->n_rays : DOCKAUV_E_INVALID; }
 int dockauv_n_u(dockauv_handle h) { return h ? h->n_u_max : DOCKAUV_E_INVALID; }
 
@@ -520,6 +528,8 @@ int dockauv_set_field(dockauv_handle h, int field, int first, int count, const d
     const size_t es = elem_size(h, fd.kind);
     std::vector<unsigned char> tmp((size_t)fd.rows * count * es);
     if (is_current_field(field)) {
+        // (the handle's "no water current" property survives a write of exact zeros only: before the copy goes out)
+        h->no_current = no_current_after_write(h->no_current, src, count);
         // host (V_c, V_min, V_max, alpha, beta) -> device rows (V_c, dir xyz, V_min, V_max, alpha, beta);
         // dir = (cos a cos b, sin b, sin a cos b): objects/current.py:70-74
         for (int i = 0; i < count; ++i) {

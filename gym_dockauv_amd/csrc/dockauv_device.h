@@ -322,6 +322,7 @@ struct StepRequest {
     bool terminal_obs;
     int pack;             // StepIO::pack
     bool ride;            // copy groups ride in this launch (RideLaunch::plan)
+    bool no_current;      // the handle's "no water current" property holds (no_current_after_write, below)
 };
 
 // the template arguments of the kernel that serves it (RAYS = has_rays, EPG = 64)
@@ -330,7 +331,31 @@ struct StepVariant {
     bool LOG, TERM, WB;
     bool ride;            // step_ride_kernel<..., NT> instead of step_kernel<..., NT, LOG, TERM, WB>
     bool unsupported;     // no such kernel: hipErrorNotSupported (select_sequence: the caller launches the steps one by one)
+    bool NOCUR;           // the lean twin without the water current (step_nocur_kernel / _ride_ / _seq_; nocur_shape)
 };
+
+// "This handle has no water current": V_c = V_min = V_max = 0 in every env for as long as the property holds, so the lean
+// (NOCUR) kernels may leave the current out of the step altogether -- its six row loads, the V_c filter, the hand-over of V_c
+// and nu_c, the V_c store, observations 13-15 (exactly +0) and the eight current rows of an episode reset.
+//  * It starts true where the scenario's generator (dockauv_step.hip.inc: generate_episode_; scenarios.py) never draws a current:
+//    every in-kernel reset of such a handle writes zeros into rows that hold zeros.
+//  * The HOST clears it, for good, with the first write of DOCKAUV_F_CURRENT / DOCKAUV_F_POOL_CURRENT rows that are not all
+//    exact (+0.0) zeros (dockauv_set_field: the only path from the host into those buffers; dockauv_reset_envs does not touch
+//    them).  The speed columns decide what a step computes; the two angle columns are held to zero as well, because a reset of
+//    the general kernel would overwrite them with the generator's zeros and the lean kernel leaves the rows alone.
+//  * A step with a noise input, device noise or any other extra is served by the full instantiation whatever the property says.
+constexpr int kCurrentCols = 5;   // host layout of a current row: V_c, V_min, V_max, alpha, beta
+inline bool scenario_without_current(int scenario) {   // DOCKAUV_SCN_*: SIMPLE, CAPSULE, OBSTACLES, OBSTACLES_NOCAP, SPHERES
+    return scenario == 0 || scenario == 2 || scenario == 4 || scenario == 5 || scenario == 7;
+}
+inline bool exact_zero(double x) { return x == 0.0 && !__builtin_signbit(x); }
+// the property after the host wrote `count` rows [count][kCurrentCols] into a current buffer
+inline bool no_current_after_write(bool no_current, const double* rows, long count) {
+    if (!no_current) return false;   // (never comes back)
+    for (long i = 0; i < count * kCurrentCols; ++i)
+        if (!exact_zero(rows[i])) return false;
+    return true;
+}
 
 // The product instantiations cover what a throughput rollout runs: mandatory outputs only, reward set 1, reset modes
 // NONE (the caller resets) and DEVICE (in-kernel episode generation), fans of 9..16 or 33..64 rays.  Everything else --
@@ -352,13 +377,24 @@ inline int group_threads(bool has_rays, int threads) {
 // 1 048 576: 191 / 165)
 inline bool many_rounds(int n_envs) { return n_envs > 262144; }
 
+// The group shapes that have a lean (NOCUR) twin: what dockauv_create picks for BASELINE configs 2, 3 and 4 at their batch
+// sizes -- BlueROV2 without sensors and with a ray fan in groups of 256 threads, the LAUV with a ray fan in groups of 512 --
+// float32, structural fast path.  Each exists as the plain kernel (written through), its TERM form, the riding kernel and the
+// resident sequence kernel.  Mixed batches, one-wave groups, the write-back twins, float64 and every full (LOG) kernel keep
+// the general body.
+inline bool nocur_shape(const StepRequest& r, int NT) {
+    if (r.f64 || !r.sym) return false;
+    if (r.vk == VK_JOY) return NT == 256;
+    return r.vk == VK_LAUV && r.has_rays && NT == 512;
+}
+
 inline StepVariant select_step(const StepRequest& r) {
     const bool fast = !r.f64 && r.sym;   // the float32 kernels of the structural fast path
     // product kernels that also deliver terminal observations (TERM): float32, structural fast path, packed rows, the two
     // default group shapes -- what a device-resident learner runs (TorchDocking3d.step(want_terminal_obs=True))
     const bool term_ok = fast && r.vk != VK_DENSEB;
     const bool term_product = term_ok && r.terminal_obs && r.pack && !r.ride;
-    StepVariant v{256, false, false, false, false, false};
+    StepVariant v{256, false, false, false, false, false, false};
     if (needs_full_kernel(r) || (r.terminal_obs && !term_product)) {
         v.LOG = true;
         v.unsupported = r.ride;   // (the riding gather is a throughput feature)
@@ -367,6 +403,7 @@ inline StepVariant select_step(const StepRequest& r) {
     if (term_product) {
         v.TERM = true;
         if (r.has_rays && r.threads >= 512) v.NT = 512;
+        v.NOCUR = r.no_current && nocur_shape(r, v.NT);
         return v;
     }
     // write-through stores while the launch is one round of resident groups, write-back beyond (store_global_): the
@@ -378,6 +415,7 @@ inline StepVariant select_step(const StepRequest& r) {
     v.WB = r.has_rays ? (v.NT == 256 && term_ok && many_rounds(r.n_envs) && !r.ride) : (v.NT < 256 && !(fast && r.ride));
     v.ride = r.ride && fast && !v.WB;
     v.unsupported = r.ride && !v.ride;
+    v.NOCUR = r.no_current && !v.WB && nocur_shape(r, v.NT);
     return v;
 }
 
@@ -389,11 +427,13 @@ inline StepVariant select_step(const StepRequest& r) {
 // (profiles/r4/ab_same_box.txt): write-back stores config 2 3.61 -> 3.39 us per step, config 4 8.72 -> 8.52, but config 3
 // 7.05 -> 7.39: the four-wave ray kernels stay written through.
 inline StepVariant select_sequence(const StepRequest& r) {
-    StepVariant v{group_threads(r.has_rays, r.threads), false, false, false, false, false};
+    StepVariant v{group_threads(r.has_rays, r.threads), false, false, false, false, false, false};
     v.unsupported = r.f64 || !r.sym || r.vk == VK_DENSEB || needs_full_kernel(r) || r.terminal_obs || r.pack == 0;
     // (the mixed kernel -- two integrating waves writing interleaved lanes of the same lines -- did NOT reproduce the single
     // launches with write-back stores between resident steps, tests/test_gpu_reset.py: written through like config 3's)
     v.WB = !r.has_rays || v.NT == 512 || (v.NT == 256 && many_rounds(r.n_envs) && r.vk != VK_MIXED);
+    // (the lean twins: the sequence kernel of each nocur_shape with the stores it has at the BASELINE batch size)
+    v.NOCUR = r.no_current && !v.unsupported && nocur_shape(r, v.NT) && !(r.has_rays && v.NT == 256 && v.WB);
     return v;
 }
 

@@ -1186,8 +1186,15 @@ constexpr bool tail_params_() {
 // of every env into the tile, and behind the tile's last barrier one wave copies the rows of the finished envs to
 // terminal_obs and zeroes them (the reference's reset observation, Q8) before the tile is streamed out.
 // WB: plain write-back stores (instantiations that serve launches of several rounds of groups only, see store_global_)
-template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool LOG = false, bool TERM = false, bool WB = false, int KIND = 0>
+// NOCUR (float32 product kernels of the shapes nocur_shape names, dockauv_device.h): the handle has no water current -- V_c =
+// V_min = V_max = 0 in every env for as long as select_step picks this form -- and the step carries none of it: no `cur` row is
+// loaded or stored, V_c is not filtered, V_c and nu_c do not travel through lds_hx (rows 12 and 16-18 stay unused), observations
+// 13-15 are written as the +0 they always were, and an episode reset leaves the current rows, which hold what it would write,
+// alone.  The right-hand sides keep their three nu + nu_c additions with nu_c a literal zero: x + 0 is not x for x = -0.
+template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool LOG = false, bool TERM = false, bool WB = false, int KIND = 0,
+          bool NOCUR = false>
 __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix = threadIdx.x, const unsigned bix = blockIdx.x) {
+    static_assert(!NOCUR || (sizeof(T) == 4 && SYM && !LOG && VK != VK_MIXED && NT / EPG >= 4), "the lean form: see nocur_shape");
     DOCKAUV_SPAN(0);   // (diagnostic build: the group's very first instructions)
     extern __shared__ __align__(16) unsigned char smem_raw[];
     typedef const __attribute__((address_space(4))) ParamBlock<T, 2> CParams;
@@ -1357,6 +1364,11 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
     T cdx = T(0), cdy = T(0), cdz = T(0), vmin = T(0), vmax = T(0), w_noise = T(0);
     int vid_l = 0;
     constexpr bool HOT = hot_params_<T, VK, SYM, RAYS, EPG, NT, LOG, TERM, WB, KIND>();
+    // NOCUR: nu_c is a literal zero in the right-hand sides -- except in the BlueROV2's ray kernels, where the zero stands in three
+    // registers that stay live up to the hand-over, as nu_c's do in the general kernel (no instruction, same sums).  With the
+    // literal those kernels took 13 / 18 / 13 SGPR spills (plain / TERM / riding) against their general twins' 10 / 14 / 12; with
+    // the registers 6 / 10 / 7.  The other lean kernels stay within their twins' registers and spills either way.
+    constexpr bool NUC_REGS = NOCUR && RAYS && VK == VK_JOY;
     // (ray kernels: the action weights stay with EnvP, one round trip of their own -- six more SGPRs across the row loads
     // cost config 3's kernel four more spills)
     constexpr bool HOT_WACT = !RAYS;
@@ -1427,9 +1439,11 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
                 act[k] = T(0);
             }
         }
-        Vc = ldgx_<VOFF>(g_cur, 0, S, ul);
-        cdx = ldgx_<VOFF>(g_cur, 1, S, ul); cdy = ldgx_<VOFF>(g_cur, 2, S, ul); cdz = ldgx_<VOFF>(g_cur, 3, S, ul);
-        vmin = ldgx_<VOFF>(g_cur, 4, S, ul); vmax = ldgx_<VOFF>(g_cur, 5, S, ul);
+        if (!NOCUR) {
+            Vc = ldgx_<VOFF>(g_cur, 0, S, ul);
+            cdx = ldgx_<VOFF>(g_cur, 1, S, ul); cdy = ldgx_<VOFF>(g_cur, 2, S, ul); cdz = ldgx_<VOFF>(g_cur, 3, S, ul);
+            vmin = ldgx_<VOFF>(g_cur, 4, S, ul); vmax = ldgx_<VOFF>(g_cur, 5, S, ul);
+        }
         // everything the tail of the step needs is requested now as well: a lone wave per SIMD (small batches) has
         // nothing to hide a late load behind.  (Mixed product kernels, at the 128-VGPR limit: held through the stages
         // these five values were spilled to scratch and reloaded; they are requested behind the stages instead.)
@@ -1589,7 +1603,8 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
 #pragma unroll
         for (int k = 0; k < 4; ++k) lds_spec[(6 + k) * EPG + ule] = goal_s[k];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) lds_spec[(10 + k) * EPG + ule] = cur_s[k];
+        for (int k = 0; k < 8; ++k)
+            if (!NOCUR) lds_spec[(10 + k) * EPG + ule] = cur_s[k];   // (NOCUR: the resetter writes no current row)
         lds_spec[18 * EPG + ule] = ring_s;
     }
 
@@ -1605,11 +1620,17 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
         // ---------------- 1. Current.sim (objects/current.py:78-96) ----------------
         if (LOG && IO.device_noise && __any(sigma_l != T(0)))
             w_noise = sigma_l * device_normal_<T>(E.seed, env0 + (int)ul, episode_l, t_steps);
-        if constexpr (HOT) Vc += (-HR.mu * Vc + w_noise) * HR.h; else Vc += (-E.mu * Vc + w_noise) * E.h;
-        Vc = clip_(Vc, vmin, vmax);
+        if constexpr (!NOCUR) {   // (NOCUR: V_c = 0 stays 0 under the filter and the clip to [0, 0])
+            if constexpr (HOT) Vc += (-HR.mu * Vc + w_noise) * HR.h; else Vc += (-E.mu * Vc + w_noise) * E.h;
+            Vc = clip_(Vc, vmin, vmax);
+        }
         // ---------------- 2. nu_c = R(Theta_pre)^T v_c^n (objects/current.py:33-53) ----------------
         nuc[0] = nuc[1] = nuc[2] = T(0);
-        if (__any(Vc != T(0))) {   // scenarios without current: V_c = 0 in every lane, nu_c = R^T 0 = 0
+        if (NUC_REGS) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) asm volatile("" : "+v"(nuc[k]));
+        }
+        if (!NOCUR && __any(Vc != T(0))) {   // scenarios without current: V_c = 0 in every lane, nu_c = R^T 0 = 0
             const Trig<T> g0 = trig_(st[3], st[4], st[5]);
             rot_ned_to_body_(g0, Vc * cdx, Vc * cdy, Vc * cdz, nuc);
         }
@@ -1749,13 +1770,18 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
 #pragma unroll
         for (int k = 0; k < 12; ++k)
             if (!(LEAN_HX && (k < 3 || k == 5))) lds_hx[k * EPG + ul] = st[k];
-        if (!LEAN_HX) lds_hx[12 * EPG + ul] = Vc;
+        if (!LEAN_HX && !NOCUR) lds_hx[12 * EPG + ul] = Vc;
         lds_hx[13 * EPG + ul] = act_pen;
         lds_hx[14 * EPG + ul] = edot_norm2;
         if (!LEAN_HX) lds_hx[15 * EPG + ul] = collision ? T(1) : T(0);
         if (QUAD) {
+            if (!NOCUR) {
 #pragma unroll
-            for (int k = 0; k < 3; ++k) lds_hx[(16 + k) * EPG + ul] = nuc[k];
+                for (int k = 0; k < 3; ++k) lds_hx[(16 + k) * EPG + ul] = nuc[k];
+            } else if (NUC_REGS) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) asm volatile("" ::"v"(nuc[k]));
+            }
             lds_hx[19 * EPG + ul] = g1.sp;
             lds_hx[20 * EPG + ul] = g1.cp;
         }
@@ -1934,9 +1960,13 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
         o[10] = clip_(s_[9] * Q.inv_vel[3], T(-1), T(1));
         o[11] = clip_(s_[10] * Q.inv_vel[4], T(-1), T(1));
         o[12] = clip_(s_[11] * Q.inv_vel[5], T(-1), T(1));
-        o[13] = clip_(nuc_[0] * T(0.5), T(-1), T(1));
-        o[14] = clip_(nuc_[1] * T(0.5), T(-1), T(1));
-        o[15] = clip_(nuc_[2] * T(0.5), T(-1), T(1));
+        if constexpr (NOCUR) {   // (clip(+0 * 0.5, -1, 1))
+            o[13] = o[14] = o[15] = T(0);
+        } else {
+            o[13] = clip_(nuc_[0] * T(0.5), T(-1), T(1));
+            o[14] = clip_(nuc_[1] * T(0.5), T(-1), T(1));
+            o[15] = clip_(nuc_[2] * T(0.5), T(-1), T(1));
+        }
         if (SHARE_NAV && lazy_done && !TERM) {   // (TERM: this role never zeroes: it does not need to know)
 #pragma unroll
             for (int k = 3; k < 16; ++k) asm volatile("" : "+v"(o[k]));   // (the values exist before the wait starts)
@@ -2023,7 +2053,7 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
             // this wave still holds the new state: it writes the state of the envs that go on, the resetter the others
 #pragma unroll
             for (int k = 0; k < 12; ++k) stgx_<VOFF>(g_state, k, S, ul, st[k]);
-            stgx_<VOFF>(g_cur, 0, S, ul, Vc);
+            if (!NOCUR) stgx_<VOFF>(g_cur, 0, S, ul, Vc);
         }
         if (sizeof(T) == 4) {   // (a new episode starts with exact coordinates)
 #pragma unroll
@@ -2040,7 +2070,7 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
 #pragma unroll
             for (int k = 0; k < 12; ++k) so[k] = lds_hx[k * EPG + ule];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) nuco[k] = lds_hx[(16 + k) * EPG + ule];
+            for (int k = 0; k < 3; ++k) nuco[k] = NOCUR ? T(0) : lds_hx[(16 + k) * EPG + ule];
             if (SHARE_NAV) {
                 obs_rest(so, nuco, lds_hx[19 * EPG + ule], lds_hx[20 * EPG + ule], false, ule, true);   // (sets ob_zero_row)
             } else {
@@ -2064,7 +2094,7 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
         if (DUAL) {
 #pragma unroll
             for (int k = 0; k < 12; ++k) sb[k] = lds_hx[k * EPG + ule];
-            Vc_b = lds_hx[12 * EPG + ule];
+            Vc_b = NOCUR ? T(0) : lds_hx[12 * EPG + ule];
             act_pen_b = lds_hx[13 * EPG + ule];
             edot_b = lds_hx[14 * EPG + ule];
             col_b = EARLY ? col_from_records(ule) : (lds_hx[15 * EPG + ule] != T(0));
@@ -2237,7 +2267,7 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
 #pragma unroll
                     for (int k = 0; k < 4; ++k) goal_b[k] = lds_spec[(6 + k) * EPG + ule];
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) curv[k] = lds_spec[(10 + k) * EPG + ule];
+                    for (int k = 0; k < 8; ++k) curv[k] = NOCUR ? T(0) : lds_spec[(10 + k) * EPG + ule];
                     ring_s = lds_spec[18 * EPG + ule];
                 } else {
                     T Ub[12];
@@ -2253,15 +2283,17 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
                 if (k < n_u_max) stgx_<VOFF>(g_u, k, S, ule, T(0));
 #pragma unroll
             for (int k = 0; k < 4; ++k) stgx_<VOFF>(g_goal, k, S, ule, goal_b[k]);
+            if (!NOCUR) {   // (NOCUR: the rows hold the generator's zeros already)
 #pragma unroll
-            for (int k = 1; k < 8; ++k) stgx_<VOFF>(g_cur, k, S, ule, curv[k]);
+                for (int k = 1; k < 8; ++k) stgx_<VOFF>(g_cur, k, S, ule, curv[k]);
+            }
             Vc_b = curv[0];
             stgx_<VOFF>(g_episode, 0, S, ule, ep_next);
         }
         if (!DUAL || reset_now) {
 #pragma unroll
             for (int k = 0; k < 12; ++k) stgx_<VOFF>(g_state, k, S, ule, sb[k]);
-            stgx_<VOFF>(g_cur, 0, S, ule, Vc_b);
+            if (!NOCUR) stgx_<VOFF>(g_cur, 0, S, ule, Vc_b);
         }
     };
 
@@ -2898,6 +2930,13 @@ __global__ __launch_bounds__(NT, (min_waves_<T, NT>())) void step_kernel(const D
     step_body<T, VK, SYM, RAYS, EPG, NT, LOG, TERM, WB>(A);
 }
 
+// The lean twins for handles without a water current (NOCUR, see step_body; select_step picks them): the plain kernel and its
+// TERM form.  Kernels of their own names, so that every other instantiation keeps its symbol and its code.
+template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool TERM = false>
+__global__ __launch_bounds__(NT, (min_waves_<T, NT>())) void step_nocur_kernel(const DevArgs A) {
+    step_body<T, VK, SYM, RAYS, EPG, NT, false, TERM, false, 0, true>(A);
+}
+
 // The step kernel with copy groups behind the step groups (dockauv_ride.h): the previous step's rows travel to the
 // peers while this step is integrated.
 template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT>
@@ -2909,6 +2948,17 @@ __global__ __launch_bounds__(NT, (min_waves_<T, NT>())) void step_ride_kernel(co
         return;
     }
     step_body<T, VK, SYM, RAYS, EPG, NT, false, false, false, 1>(A);
+}
+// (its lean twin)
+template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT>
+__global__ __launch_bounds__(NT, (min_waves_<T, NT>())) void step_ride_nocur_kernel(const DevArgs A, const RideArgs R) {
+    const unsigned groups = (unsigned)((A.n_envs + EPG - 1) / EPG);
+    if (blockIdx.x >= groups) {
+        extern __shared__ __align__(16) unsigned char smem_raw[];
+        ride_body<NT>(R, blockIdx.x - groups, gridDim.x - groups, reinterpret_cast<uint32_t*>(smem_raw));
+        return;
+    }
+    step_body<T, VK, SYM, RAYS, EPG, NT, false, false, false, 1, true>(A);
 }
 
 // The RESIDENT step sequence (round 4; dockauv_step_sequence's fast path for open-loop action sequences: the scripted /
@@ -2958,8 +3008,38 @@ __global__ __launch_bounds__(NT, (min_waves_<T, NT>())) void step_seq_kernel(con
         }
     }
 }
+// Its lean twin for handles without a water current (NOCUR, see step_body; select_sequence picks it): the same loop around the
+// lean body -- a copy, not a shared function, so that step_seq_kernel keeps the code it has.
+template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool WB>
+__global__ __launch_bounds__(NT, (min_waves_<T, NT>())) void step_seq_nocur_kernel(const DevArgs, const SeqArgs) {
+    struct KernArgs { DevArgs A; SeqArgs Q; };   // (the kernarg segment: both arguments by value, 8-byte aligned)
+    static_assert(alignof(DevArgs) == 8 && alignof(SeqArgs) == 8 && sizeof(DevArgs) % 8 == 0, "kernarg layout");
+    typedef const __attribute__((address_space(4))) KernArgs CKA;
+    CKA* ka = (CKA*)__builtin_amdgcn_kernarg_segment_ptr();
+    unsigned tix = threadIdx.x, bix = blockIdx.x;
+    const int n = ka->Q.n;
+    for (int k = 0; k < n; ++k) {
+        asm volatile("" : "+s"(ka));
+        asm volatile("" : "+v"(tix));
+        asm volatile("" : "+s"(bix));
+        union { DevArgs a; unsigned long long w[sizeof(DevArgs) / 8]; } Ak;
+        typedef const __attribute__((address_space(4))) unsigned long long CW8;
+        CW8* const src = (CW8*)ka;
+#pragma unroll
+        for (unsigned i = 0; i < sizeof(DevArgs) / 8; ++i) Ak.w[i] = src[i];
+        Ak.a.io.actions = ka->Q.actions[k];
+        Ak.a.io.obs = ka->Q.obs[k];
+        step_body<T, VK, SYM, RAYS, EPG, NT, false, false, WB, 2, true>(Ak.a, tix, bix);
+        if (k + 1 < n) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            if (NT > 64) __builtin_amdgcn_s_barrier();
+            asm volatile("buffer_inv sc0" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        }
+    }
+}
 
-template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool WB = false>
+template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool WB = false, bool NOCUR = false>
 static int launch_seq_one(const KernelArgs<T, 2>& a, const SeqArgs& seq, void* stream) {
     const EnvP<T>& E = a.P.E;
     const int groups = (E.n_envs + EPG - 1) / EPG;
@@ -2969,12 +3049,13 @@ static int launch_seq_one(const KernelArgs<T, 2>& a, const SeqArgs& seq, void* s
     d.B = a.B;
     d.io = a.io;
     d.n_envs = E.n_envs;
+    void (*kernel)(const DevArgs, const SeqArgs);
+    if constexpr (NOCUR) kernel = &step_seq_nocur_kernel<T, VK, SYM, RAYS, EPG, NT, WB>; else kernel = &step_seq_kernel<T, VK, SYM, RAYS, EPG, NT, WB>;
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_seq_kernel<T, VK, SYM, RAYS, EPG, NT, WB>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL((step_seq_kernel<T, VK, SYM, RAYS, EPG, NT, WB>), dim3(groups), dim3(NT), lds, (hipStream_t)stream, d, seq);
+    hipLaunchKernelGGL(kernel, dim3(groups), dim3(NT), lds, (hipStream_t)stream, d, seq);
     return (int)hipGetLastError();
 }
 
@@ -2985,6 +3066,16 @@ static int launch_seq_vk(const KernelArgs<T, 2>& a, const StepRequest& r, const 
     const StepVariant v = select_sequence(r);
     if (v.unsupported) return (int)hipErrorNotSupported;
     const auto is = [&](bool rays, int nt, bool wb) { return r.has_rays == rays && v.NT == nt && v.WB == wb; };
+    if (v.NOCUR) {   // (the lean twins: nocur_shape)
+        if constexpr (VK == VK_JOY) {
+            if (is(false, 256, true)) return launch_seq_one<T, VK, true, false, 64, 256, true, true>(a, seq, stream);
+            if (is(true, 256, false)) return launch_seq_one<T, VK, true, true, 64, 256, false, true>(a, seq, stream);
+        }
+        if constexpr (VK == VK_LAUV) {
+            if (is(true, 512, true)) return launch_seq_one<T, VK, true, true, 64, 512, true, true>(a, seq, stream);
+        }
+        return (int)hipErrorNotSupported;
+    }
     if (is(false, 256, true)) return launch_seq_one<T, VK, true, false, 64, 256, true>(a, seq, stream);
     if (is(false, 128, true)) return launch_seq_one<T, VK, true, false, 64, 128, true>(a, seq, stream);
     if (is(false, 64, true)) return launch_seq_one<T, VK, true, false, 64, 64, true>(a, seq, stream);
@@ -2996,8 +3087,12 @@ static int launch_seq_vk(const KernelArgs<T, 2>& a, const StepRequest& r, const 
 }
 
 // ------------------------------------------------------------------------------------------ launchers
-template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool LOG = false, bool TERM = false, bool WB = false>
+// NOCUR: the lean twin of a plain or TERM product kernel (step_nocur_kernel / step_ride_nocur_kernel)
+template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool LOG = false, bool TERM = false, bool WB = false, bool NOCUR = false>
 static int launch_one(const KernelArgs<T, 2>& a, void* stream, void* ev0, void* ev1) {
+    static_assert(!NOCUR || (!LOG && !WB), "the lean twins: plain and TERM product kernels");
+    void (*kernel)(const DevArgs);
+    if constexpr (NOCUR) kernel = &step_nocur_kernel<T, VK, SYM, RAYS, EPG, NT, TERM>; else kernel = &step_kernel<T, VK, SYM, RAYS, EPG, NT, LOG, TERM, WB>;
     const EnvP<T>& E = a.P.E;
     const int groups = (E.n_envs + EPG - 1) / EPG;
     const size_t lds = lds_bytes<T>(EPG, NT, E.max_cap, E.max_sph, E.n_obs, RAYS, E.ray_pad_log2);
@@ -3010,8 +3105,7 @@ static int launch_one(const KernelArgs<T, 2>& a, void* stream, void* ev0, void* 
         // gfx950 has 160 KiB of LDS per CU; more than 64 KiB per group must be requested explicitly.  The attribute
         // belongs to the (device, function) pair, and handles on several devices may share this process: it is set on
         // the launch path (wide fans / many obstacles only; a host-side call of a few microseconds), not cached
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_kernel<T, VK, SYM, RAYS, EPG, NT, LOG, TERM, WB>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
     }
     if (a.ride.plan) {
@@ -3019,9 +3113,10 @@ static int launch_one(const KernelArgs<T, 2>& a, void* stream, void* ev0, void* 
         // float kernels of the structural fast path only (both shipped vehicles); the caller falls back to a
         // separate gather kernel otherwise
         if constexpr (sizeof(T) == 4 && SYM) {
+            void (*ride_kernel)(const DevArgs, const RideArgs);
+            if constexpr (NOCUR) ride_kernel = &step_ride_nocur_kernel<T, VK, SYM, RAYS, EPG, NT>; else ride_kernel = &step_ride_kernel<T, VK, SYM, RAYS, EPG, NT>;
             if (lds > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_ride_kernel<T, VK, SYM, RAYS, EPG, NT>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ride_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 if (e != hipSuccess) return (int)e;
             }
             RideArgs r;
@@ -3029,8 +3124,7 @@ static int launch_one(const KernelArgs<T, 2>& a, void* stream, void* ev0, void* 
             r.src = a.ride.src;
             r.stamp = a.ride.stamp;
             r.wait_stamp = a.ride.wait_stamp;
-            hipLaunchKernelGGL((step_ride_kernel<T, VK, SYM, RAYS, EPG, NT>), dim3(groups + a.ride.groups), dim3(NT),
-                               lds < 16 ? (size_t)16 : lds, (hipStream_t)stream, d, r);
+            hipLaunchKernelGGL(ride_kernel, dim3(groups + a.ride.groups), dim3(NT), lds < 16 ? (size_t)16 : lds, (hipStream_t)stream, d, r);
             return (int)hipGetLastError();
         } else {
             return (int)hipErrorNotSupported;
@@ -3038,10 +3132,9 @@ static int launch_one(const KernelArgs<T, 2>& a, void* stream, void* ev0, void* 
     }
     if (ev0 || ev1) {
         // start/stop events attached to THIS dispatch: the elapsed time is the kernel's own duration
-        hipExtLaunchKernelGGL((step_kernel<T, VK, SYM, RAYS, EPG, NT, LOG, TERM, WB>), dim3(groups), dim3(NT), lds, (hipStream_t)stream,
-                              (hipEvent_t)ev0, (hipEvent_t)ev1, 0, d);
+        hipExtLaunchKernelGGL(kernel, dim3(groups), dim3(NT), lds, (hipStream_t)stream, (hipEvent_t)ev0, (hipEvent_t)ev1, 0, d);
     } else {
-        hipLaunchKernelGGL((step_kernel<T, VK, SYM, RAYS, EPG, NT, LOG, TERM, WB>), dim3(groups), dim3(NT), lds, (hipStream_t)stream, d);
+        hipLaunchKernelGGL(kernel, dim3(groups), dim3(NT), lds, (hipStream_t)stream, d);
     }
     return (int)hipGetLastError();
 }
@@ -3055,6 +3148,19 @@ static int launch_vk(const KernelArgs<T, 2>& a, const StepRequest& r, void* stre
         return r.has_rays == rays && v.NT == nt && v.LOG == log && v.TERM == term && v.WB == wb;
     };
     constexpr bool TERM_OK = sizeof(T) == 4 && SYM && VK != VK_DENSEB;
+    if (v.NOCUR) {   // (the lean twins: nocur_shape; launch_one takes the ride branch of a plain one)
+        if constexpr (sizeof(T) == 4 && SYM && VK == VK_JOY) {
+            if (is(false, 256)) return launch_one<T, VK, SYM, false, 64, 256, false, false, false, true>(a, stream, ev0, ev1);
+            if (is(true, 256)) return launch_one<T, VK, SYM, true, 64, 256, false, false, false, true>(a, stream, ev0, ev1);
+            if (is(false, 256, false, true)) return launch_one<T, VK, SYM, false, 64, 256, false, true, false, true>(a, stream, ev0, ev1);
+            if (is(true, 256, false, true)) return launch_one<T, VK, SYM, true, 64, 256, false, true, false, true>(a, stream, ev0, ev1);
+        }
+        if constexpr (sizeof(T) == 4 && SYM && VK == VK_LAUV) {
+            if (is(true, 512)) return launch_one<T, VK, SYM, true, 64, 512, false, false, false, true>(a, stream, ev0, ev1);
+            if (is(true, 512, false, true)) return launch_one<T, VK, SYM, true, 64, 512, false, true, false, true>(a, stream, ev0, ev1);
+        }
+        return (int)hipErrorNotSupported;
+    }
     if (is(true, 256, true)) return launch_one<T, VK, SYM, true, 64, 256, true>(a, stream, ev0, ev1);
     if (is(false, 256, true)) return launch_one<T, VK, SYM, false, 64, 256, true>(a, stream, ev0, ev1);
     if constexpr (TERM_OK) {

@@ -611,6 +611,12 @@ class BatchedDocking3d:
         rc = self._lib.dockauv_step_sequence(self._handle, ios, len(ios), C.c_void_p(stream or None))
         _capi.check(self._lib, self._handle, rc, "dockauv_step_sequence")
 
+    @property
+    def step_uses_current(self) -> bool:
+        """False while the next plain step runs the lean kernel that leaves the water current out (dockauv_step_uses_current:
+        a scenario without current and no non-zero current row written since the handle was created)."""
+        return bool(self._lib.dockauv_step_uses_current(self._handle))
+
     def set_sequence_resident(self, on: bool) -> None:
         """Switch the resident fast path of run_step_sequence (on by default) for this handle."""
         rc = self._lib.dockauv_set_option(self._handle, _capi.OPT_SEQUENCE_RESIDENT, 1 if on else 0)

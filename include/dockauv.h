@@ -200,6 +200,13 @@ int dockauv_n_obs(dockauv_handle h);
 /* waves x 64 = threads per 64-env group the handle's step kernels run with (dockauv_config::threads_per_group, or the
  * library's choice for this workload and batch size when that was 0).  No reference counterpart: a tuning read-out. */
 int dockauv_threads_per_group(dockauv_handle h);
+/* 1: the next plain step (mandatory outputs, packed rows) runs the general step kernel; 0: the lean one that leaves the water
+ * current out.  The lean kernels exist for the float32 group shapes of BlueROV2 (256 threads) and LAUV-with-fan (512 threads)
+ * handles and are picked while the handle has no current: a scenario whose generator draws none (SimpleDocking3d,
+ * CapsuleDocking3d, ObstaclesDocking3d, ObstaclesNoCapDocking3d, SphereDocking3d) and no dockauv_set_field of
+ * DOCKAUV_F_CURRENT / DOCKAUV_F_POOL_CURRENT rows other than exact zeros since dockauv_create; the first such write switches the
+ * handle to the general kernels for good.  Same results either way, bit for bit.  No reference counterpart: a tuning read-out. */
+int dockauv_step_uses_current(dockauv_handle h);
 int dockauv_n_rays(dockauv_handle h);
 int dockauv_n_u(dockauv_handle h);
 
