@@ -189,14 +189,6 @@ int queue_rollout(dockauv_handle h, dockauv_policy p, const float* rows_in, floa
     return 0;
 }
 
-int gae(dockauv_handle h, const float* rows_out, const float* values, int n_steps, float gamma, float gae_lambda, float* advantages,
-        float* returns, hipStream_t stream) {
-    const int rc = launch_gae(rows_out, values, advantages, returns, n_steps, h->cfg.n_envs, h->n_obs, gamma, gae_lambda, stream);
-    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "GAE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    h->last_stream = stream;
-    return 0;
-}
-
 // a dockauv_truncation_io against the handle, before any device call; `full`: also what the value launch and GAE touch
 int check_truncation(dockauv_handle h, const dockauv_truncation_io* io, const char* fn, bool full) {
     if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
@@ -246,15 +238,23 @@ int truncation_scan(dockauv_handle h, const dockauv_truncation_io* io, hipStream
     return 0;
 }
 
-// the three launches of dockauv_gae_truncated: the scan, V of the slots' terminal observations, GAE with the bootstrap
-int gae_truncated(dockauv_handle h, dockauv_policy critic, const dockauv_truncation_io* io, hipStream_t stream) {
-    if (int rc = truncation_scan(h, io, stream)) return rc;
-    const long n = (long)io->n_slots * (long)h->cfg.n_envs;
-    int rc = launch_policy_forward_rows(critic->S, critic->packed, io->terminal_obs, (const long long*)io->trunc_row, n, h->n_obs,
-                                        io->v_terminal, stream);
-    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "value kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    rc = launch_gae_truncated(io->rows_out, io->values, io->advantages, io->returns, io->trunc_step, io->v_terminal, io->n_slots,
-                              io->n_steps, h->cfg.n_envs, h->n_obs, io->gamma, io->gae_lambda, stream);
+// the GAE stage of every entry point: g carries the caller's buffers and factors (reward_col: the reward column of
+// dockauv_gae_normalized).  With tio the three launches of dockauv_gae_truncated: the scan, V of the slots' terminal observations,
+// and the GAE launch on the slots
+int queue_gae(dockauv_handle h, dockauv_policy critic, const dockauv_truncation_io* tio, GaeLaunch g, hipStream_t stream) {
+    g.n_envs = h->cfg.n_envs;
+    g.n_obs = h->n_obs;
+    if (tio) {
+        if (int rc = truncation_scan(h, tio, stream)) return rc;
+        const long n = (long)tio->n_slots * (long)h->cfg.n_envs;
+        const int rc = launch_policy_forward_rows(critic->S, critic->packed, tio->terminal_obs, (const long long*)tio->trunc_row, n, h->n_obs,
+                                                  tio->v_terminal, stream);
+        if (rc != 0) return fail(h, DOCKAUV_E_HIP, "value kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        g.trunc_step = tio->trunc_step;
+        g.v_terminal = tio->v_terminal;
+        g.n_slots = tio->n_slots;
+    }
+    const int rc = launch_gae(g, stream);
     if (rc != 0) return fail(h, DOCKAUV_E_HIP, "GAE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     h->last_stream = stream;
     return 0;
@@ -304,38 +304,59 @@ int rewnorm_scan(dockauv_handle h, dockauv_rewnorm rn, const dockauv_rewnorm_io*
     return 0;
 }
 
-// GAE on the column; tio != nullptr: the scan and the value launch of gae_truncated in front of it
-int gae_normalized(dockauv_handle h, dockauv_policy critic, const float* reward_norm, const dockauv_truncation_io* tio,
-                   const float* rows_out, const float* values, int n_steps, float gamma, float gae_lambda, float* advantages,
-                   float* returns, hipStream_t stream) {
-    int rc;
-    if (tio) {
-        if ((rc = truncation_scan(h, tio, stream)) != 0) return rc;
-        const long n = (long)tio->n_slots * (long)h->cfg.n_envs;
-        rc = launch_policy_forward_rows(critic->S, critic->packed, tio->terminal_obs, (const long long*)tio->trunc_row, n, h->n_obs,
-                                        tio->v_terminal, stream);
-        if (rc != 0) return fail(h, DOCKAUV_E_HIP, "value kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    }
-    rc = launch_gae_column(rows_out, reward_norm, values, advantages, returns, tio ? tio->trunc_step : nullptr,
-                           tio ? tio->v_terminal : nullptr, tio ? tio->n_slots : 0, n_steps, h->cfg.n_envs, h->n_obs, gamma,
-                           gae_lambda, stream);
-    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "GAE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    h->last_stream = stream;
+// what a truncation block must share with the GAE arguments `g` of the call it belongs to; `whose`: the block
+// (dockauv_collect_io, whose terminal_obs must be the truncation block's too) or the function (dockauv_gae_normalized) they come from
+int check_truncation_matches(dockauv_handle h, const dockauv_truncation_io* tio, const GaeLaunch& g, const float* terminal_obs, const char* whose) {
+    if (tio->n_steps != g.n_steps) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.n_steps: %d, %s's is %d", tio->n_steps, whose, g.n_steps);
+    if (tio->rows_out != g.rows) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.rows_out is not %s's", whose);
+    if (terminal_obs && tio->terminal_obs != terminal_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.terminal_obs is not %s's", whose);
+    if (tio->values != g.values) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.values is not %s's", whose);
+    if (tio->advantages != g.advantages) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.advantages is not %s's", whose);
+    if (tio->returns != g.returns) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.returns is not %s's", whose);
+    if (tio->gamma != g.gamma) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.gamma: %g, %s's is %g", (double)tio->gamma, whose, (double)g.gamma);
+    if (tio->gae_lambda != g.gae_lambda)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.gae_lambda: %g, %s's is %g", (double)tio->gae_lambda, whose, (double)g.gae_lambda);
     return 0;
 }
 
-// what a truncation block must share with a collect block (dockauv_collect_truncated, dockauv_collect_normalized)
-int check_truncation_matches(dockauv_handle h, const dockauv_truncation_io* tio, const dockauv_collect_io* cio) {
-    if (tio->n_steps != cio->n_steps) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.n_steps: %d, dockauv_collect_io's is %d", tio->n_steps, cio->n_steps);
-    if (tio->rows_out != cio->rows_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.rows_out is not dockauv_collect_io's");
-    if (tio->terminal_obs != cio->terminal_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.terminal_obs is not dockauv_collect_io's");
-    if (tio->values != cio->values) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.values is not dockauv_collect_io's");
-    if (tio->advantages != cio->advantages) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.advantages is not dockauv_collect_io's");
-    if (tio->returns != cio->returns) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.returns is not dockauv_collect_io's");
-    if (tio->gamma != cio->gamma) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.gamma: %g, dockauv_collect_io's is %g", (double)tio->gamma, (double)cio->gamma);
-    if (tio->gae_lambda != cio->gae_lambda)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.gae_lambda: %g, dockauv_collect_io's is %g", (double)tio->gae_lambda, (double)cio->gae_lambda);
+// what the three collect calls check alike on their dockauv_collect_io, `arg` in the words of `fn`
+int check_collect_io(dockauv_handle h, const dockauv_collect_io* io, const char* fn, const char* arg) {
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "%s: %s is NULL", fn, arg);
+    if (io->struct_size != sizeof(dockauv_collect_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_collect_io));
+    if (io->n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.n_steps: %d must be >= 1", io->n_steps);
+    if (!io->rows_in || !io->rows_out || !io->actions_out)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: rows_in/rows_out/actions_out must not be NULL");
     return 0;
+}
+
+// the GAE arguments of a collect block
+GaeLaunch gae_of(const dockauv_collect_io* cio, const float* reward_col = nullptr) {
+    return {cio->rows_out, cio->values, cio->advantages, cio->returns, cio->n_steps, cio->gamma, cio->gae_lambda, reward_col};
+}
+
+// One collection, validated by its entry point: with tio, length_carry <- the steps of every env's episode before step 0 (the
+// handle's own counters at this point of the stream: monitor_sync); the rollout; with a critic V of the K + 1 observation sets,
+// with rn the normaliser's scan, and the GAE stage
+int queue_collect(dockauv_handle h, dockauv_policy actor, dockauv_policy critic, const dockauv_collect_io* cio,
+                  const dockauv_truncation_io* tio, dockauv_rewnorm rn, const dockauv_rewnorm_io* nio, hipStream_t stream) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int K = cio->n_steps;
+    const size_t N = (size_t)h->cfg.n_envs;
+    if (tio) {
+        HIP_TRY(h, hipMemcpyAsync(tio->length_carry, h->B.t_steps, N * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+        h->last_stream = stream;
+    }
+    int rc = queue_rollout(h, actor, cio->rows_in, cio->rows_out, cio->actions_out, cio->terminal_obs, cio->log_prob, K, cio->t0,
+                           cio->stochastic, stream);
+    if (rc) return rc;
+    if (critic) {
+        if ((rc = value_forward(h, critic, cio->rows_in, (long long)N, cio->values, stream)) != 0) return rc;
+        if ((rc = value_forward(h, critic, cio->rows_out, (long long)K * (long long)N, cio->values + N, stream)) != 0) return rc;
+        if (rn && (rc = rewnorm_scan(h, rn, nio, stream)) != 0) return rc;
+        if ((rc = queue_gae(h, critic, tio, gae_of(cio, rn ? nio->reward_norm : nullptr), stream)) != 0) return rc;
+    }
+    return check_status(h);   // (what dockauv_poll_status looks at: no synchronisation)
 }
 
 // actor (dockauv_policy_create) or critic (dockauv_value_create): `fn` names the entry point in the messages
@@ -650,16 +671,11 @@ int dockauv_gae(dockauv_handle h, const float* rows_out, const float* values, in
     if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_gae: null handle");
     if (h->f64) return fail(h, DOCKAUV_E_INVALID, "dockauv_gae: the packed rows are float32; the handle's precision is DOCKAUV_F64");
     HIP_TRY(h, hipSetDevice(h->device));
-    return gae(h, rows_out, values, n_steps, gamma, gae_lambda, advantages, returns, (hipStream_t)hip_stream);
+    return queue_gae(h, nullptr, nullptr, {rows_out, values, advantages, returns, n_steps, gamma, gae_lambda}, (hipStream_t)hip_stream);
 }
 
 int dockauv_collect(dockauv_handle h, dockauv_policy actor, dockauv_policy critic, const dockauv_collect_io* io, void* hip_stream) {
-    if (!io) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect: io is NULL");
-    if (io->struct_size != sizeof(dockauv_collect_io))
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_collect_io));
-    if (io->n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.n_steps: %d must be >= 1", io->n_steps);
-    if (!io->rows_in || !io->rows_out || !io->actions_out)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: rows_in/rows_out/actions_out must not be NULL");
+    if (int rc = check_collect_io(h, io, "dockauv_collect", "io")) return rc;
     if (critic && (!io->values || !io->advantages || !io->returns))
         return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: values/advantages/returns must not be NULL with a critic");
     if (!critic && (io->values || io->advantages || io->returns))
@@ -671,19 +687,7 @@ int dockauv_collect(dockauv_handle h, dockauv_policy actor, dockauv_policy criti
     if (int rc = check_actor(h, actor, "dockauv_collect", io->log_prob != nullptr)) return rc;
     if (critic)
         if (int rc = check_critic(h, critic, "dockauv_collect")) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const int K = io->n_steps;
-    int rc = queue_rollout(h, actor, io->rows_in, io->rows_out, io->actions_out, io->terminal_obs, io->log_prob, K, io->t0,
-                           io->stochastic, stream);
-    if (rc) return rc;
-    if (critic) {
-        const size_t N = (size_t)h->cfg.n_envs;
-        if ((rc = value_forward(h, critic, io->rows_in, (long long)N, io->values, stream)) != 0) return rc;
-        if ((rc = value_forward(h, critic, io->rows_out, (long long)K * (long long)N, io->values + N, stream)) != 0) return rc;
-        if ((rc = gae(h, io->rows_out, io->values, K, io->gamma, io->gae_lambda, io->advantages, io->returns, stream)) != 0) return rc;
-    }
-    return check_status(h);   // (what dockauv_poll_status looks at: no synchronisation)
+    return queue_collect(h, actor, critic, io, nullptr, nullptr, nullptr, (hipStream_t)hip_stream);
 }
 
 int dockauv_truncation_slots(dockauv_handle h, int n_steps) {
@@ -706,7 +710,8 @@ int dockauv_gae_truncated(dockauv_handle h, dockauv_policy critic, const dockauv
     if (int rc = check_truncation(h, io, "dockauv_gae_truncated", true)) return rc;
     if (int rc = check_critic(h, critic, "dockauv_gae_truncated")) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    return gae_truncated(h, critic, io, (hipStream_t)hip_stream);
+    return queue_gae(h, critic, io, {io->rows_out, io->values, io->advantages, io->returns, io->n_steps, io->gamma, io->gae_lambda},
+                     (hipStream_t)hip_stream);
 }
 
 int dockauv_collect_truncated(dockauv_handle h, dockauv_policy actor, dockauv_policy critic, const dockauv_collect_io* cio,
@@ -715,33 +720,15 @@ int dockauv_collect_truncated(dockauv_handle h, dockauv_policy actor, dockauv_po
     if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
     if (!actor) return fail(h, DOCKAUV_E_INVALID, "%s: null actor", fn);
     if (!critic) return fail(h, DOCKAUV_E_INVALID, "%s: null critic (the bootstrap is the critic's value)", fn);
-    if (!cio) return fail(h, DOCKAUV_E_INVALID, "%s: cio is NULL", fn);
-    if (cio->struct_size != sizeof(dockauv_collect_io))
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.struct_size: got %u, library has %zu", cio->struct_size, sizeof(dockauv_collect_io));
-    if (cio->n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.n_steps: %d must be >= 1", cio->n_steps);
-    if (!cio->rows_in || !cio->rows_out || !cio->actions_out)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: rows_in/rows_out/actions_out must not be NULL");
+    if (int rc = check_collect_io(h, cio, fn, "cio")) return rc;
     if (!cio->terminal_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.terminal_obs is NULL (%s reads it)", fn);
     if (!cio->values || !cio->advantages || !cio->returns)
         return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: values/advantages/returns must not be NULL with a critic");
     if (int rc = check_truncation(h, tio, fn, true)) return rc;
-    if (int rc = check_truncation_matches(h, tio, cio)) return rc;
+    if (int rc = check_truncation_matches(h, tio, gae_of(cio), cio->terminal_obs, "dockauv_collect_io")) return rc;
     if (int rc = check_actor(h, actor, fn, cio->log_prob != nullptr)) return rc;
     if (int rc = check_critic(h, critic, fn)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const int K = cio->n_steps;
-    const size_t N = (size_t)h->cfg.n_envs;
-    // the steps of every env's episode before step 0: the handle's own counters at this point of the stream (monitor_sync)
-    HIP_TRY(h, hipMemcpyAsync(tio->length_carry, h->B.t_steps, N * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
-    h->last_stream = stream;
-    int rc = queue_rollout(h, actor, cio->rows_in, cio->rows_out, cio->actions_out, cio->terminal_obs, cio->log_prob, K, cio->t0,
-                           cio->stochastic, stream);
-    if (rc) return rc;
-    if ((rc = value_forward(h, critic, cio->rows_in, (long long)N, cio->values, stream)) != 0) return rc;
-    if ((rc = value_forward(h, critic, cio->rows_out, (long long)K * (long long)N, cio->values + N, stream)) != 0) return rc;
-    if ((rc = gae_truncated(h, critic, tio, stream)) != 0) return rc;
-    return check_status(h);   // (what dockauv_poll_status looks at: no synchronisation)
+    return queue_collect(h, actor, critic, cio, tio, nullptr, nullptr, (hipStream_t)hip_stream);
 }
 
 int dockauv_rollout(dockauv_handle h, dockauv_policy p, const float* rows_in, float* rows_out, float* actions_out,
@@ -1165,6 +1152,7 @@ int dockauv_gae_normalized(dockauv_handle h, dockauv_policy critic, const float*
                            const float* rows_out, const float* values, int n_steps, float gamma, float gae_lambda,
                            float* advantages, float* returns, void* hip_stream) {
     const char* fn = "dockauv_gae_normalized";
+    const GaeLaunch g{rows_out, values, advantages, returns, n_steps, gamma, gae_lambda, reward_norm};
     if (!reward_norm) return fail(h, DOCKAUV_E_INVALID, "%s: reward_norm is NULL", fn);
     if (!rows_out || !values || !advantages || !returns)
         return fail(h, DOCKAUV_E_INVALID, "%s: rows_out/values/advantages/returns must not be NULL", fn);
@@ -1175,31 +1163,18 @@ int dockauv_gae_normalized(dockauv_handle h, dockauv_policy critic, const float*
     if (tio) {
         if (!critic) return fail(h, DOCKAUV_E_INVALID, "%s: null critic (the bootstrap is the critic's value)", fn);
         if (int rc = check_truncation(h, tio, fn, true)) return rc;
-        if (tio->n_steps != n_steps) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.n_steps: %d, %s's is %d", tio->n_steps, fn, n_steps);
-        if (tio->rows_out != rows_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.rows_out is not %s's", fn);
-        if (tio->values != values) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.values is not %s's", fn);
-        if (tio->advantages != advantages) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.advantages is not %s's", fn);
-        if (tio->returns != returns) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.returns is not %s's", fn);
-        if (tio->gamma != gamma) return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.gamma: %g, %s's is %g", (double)tio->gamma, fn, (double)gamma);
-        if (tio->gae_lambda != gae_lambda)
-            return fail(h, DOCKAUV_E_INVALID, "dockauv_truncation_io.gae_lambda: %g, %s's is %g", (double)tio->gae_lambda, fn, (double)gae_lambda);
+        if (int rc = check_truncation_matches(h, tio, g, nullptr, fn)) return rc;
         if (int rc = check_critic(h, critic, fn)) return rc;
     }
     HIP_TRY(h, hipSetDevice(h->device));
-    return gae_normalized(h, critic, reward_norm, tio, rows_out, values, n_steps, gamma, gae_lambda, advantages, returns,
-                          (hipStream_t)hip_stream);
+    return queue_gae(h, critic, tio, g, (hipStream_t)hip_stream);
 }
 
 int dockauv_collect_normalized(dockauv_handle h, dockauv_policy actor, dockauv_policy critic, const dockauv_collect_io* cio,
                                const dockauv_truncation_io* tio, dockauv_rewnorm rn, const dockauv_rewnorm_io* nio,
                                void* hip_stream) {
     const char* fn = "dockauv_collect_normalized";
-    if (!cio) return fail(h, DOCKAUV_E_INVALID, "%s: cio is NULL", fn);
-    if (cio->struct_size != sizeof(dockauv_collect_io))
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.struct_size: got %u, library has %zu", cio->struct_size, sizeof(dockauv_collect_io));
-    if (cio->n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.n_steps: %d must be >= 1", cio->n_steps);
-    if (!cio->rows_in || !cio->rows_out || !cio->actions_out)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: rows_in/rows_out/actions_out must not be NULL");
+    if (int rc = check_collect_io(h, cio, fn, "cio")) return rc;
     if (!cio->values || !cio->advantages || !cio->returns)
         return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io: values/advantages/returns must not be NULL (%s needs a critic)", fn);
     if (tio && !cio->terminal_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_collect_io.terminal_obs is NULL (the truncation block reads it)");
@@ -1214,28 +1189,11 @@ int dockauv_collect_normalized(dockauv_handle h, dockauv_policy actor, dockauv_p
     if (!critic) return fail(h, DOCKAUV_E_INVALID, "%s: null critic (advantages of normalised rewards need values)", fn);
     if (tio) {
         if (int rc = check_truncation(h, tio, fn, true)) return rc;
-        if (int rc = check_truncation_matches(h, tio, cio)) return rc;
+        if (int rc = check_truncation_matches(h, tio, gae_of(cio), cio->terminal_obs, "dockauv_collect_io")) return rc;
     }
     if (int rc = check_actor(h, actor, fn, cio->log_prob != nullptr)) return rc;
     if (int rc = check_critic(h, critic, fn)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const int K = cio->n_steps;
-    const size_t N = (size_t)h->cfg.n_envs;
-    if (tio) {   // (dockauv_collect_truncated: the steps of every env's episode before step 0)
-        HIP_TRY(h, hipMemcpyAsync(tio->length_carry, h->B.t_steps, N * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
-        h->last_stream = stream;
-    }
-    int rc = queue_rollout(h, actor, cio->rows_in, cio->rows_out, cio->actions_out, cio->terminal_obs, cio->log_prob, K, cio->t0,
-                           cio->stochastic, stream);
-    if (rc) return rc;
-    if ((rc = value_forward(h, critic, cio->rows_in, (long long)N, cio->values, stream)) != 0) return rc;
-    if ((rc = value_forward(h, critic, cio->rows_out, (long long)K * (long long)N, cio->values + N, stream)) != 0) return rc;
-    if ((rc = rewnorm_scan(h, rn, nio, stream)) != 0) return rc;
-    if ((rc = gae_normalized(h, critic, nio->reward_norm, tio, cio->rows_out, cio->values, K, cio->gamma, cio->gae_lambda,
-                             cio->advantages, cio->returns, stream)) != 0)
-        return rc;
-    return check_status(h);   // (what dockauv_poll_status looks at: no synchronisation)
+    return queue_collect(h, actor, critic, cio, tio, rn, nio, (hipStream_t)hip_stream);
 }
 
 }  // extern "C"

@@ -179,39 +179,23 @@ __global__ __launch_bounds__(kGaeThreads) void truncation_scan_kernel(const Trun
 
 }  // namespace
 
-int launch_gae(const float* rows, const float* values, float* advantages, float* returns, int n_steps, int n_envs, int n_obs,
-               float gamma, float gae_lambda, void* stream) {
-    if (n_steps < 1 || n_envs < 1 || n_obs < 1) return (int)hipErrorInvalidValue;
-    GaeArgs a{rows, values, advantages, returns, n_steps, n_envs, n_obs, n_obs + 2, gamma, gae_lambda};
-    const unsigned groups = (unsigned)((n_envs + kGaeThreads - 1) / kGaeThreads);
-    hipLaunchKernelGGL(gae_kernel<GaeArgs>, dim3(groups), dim3(kGaeThreads), 0, (hipStream_t)stream, a);
+namespace {
+
+template <class Args>
+int launch_gae_on(const Args& a, void* stream) {
+    const unsigned groups = (unsigned)((a.n_envs + kGaeThreads - 1) / kGaeThreads);
+    hipLaunchKernelGGL(gae_kernel<Args>, dim3(groups), dim3(kGaeThreads), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
-int launch_gae_truncated(const float* rows, const float* values, float* advantages, float* returns, const int32_t* trunc_step,
-                         const float* v_terminal, int n_slots, int n_steps, int n_envs, int n_obs, float gamma, float gae_lambda,
-                         void* stream) {
-    if (n_steps < 1 || n_envs < 1 || n_obs < 1 || n_slots < 1) return (int)hipErrorInvalidValue;
-    GaeArgsTrunc a{{rows, values, advantages, returns, n_steps, n_envs, n_obs, n_obs + 2, gamma, gae_lambda}, trunc_step, v_terminal, n_slots};
-    const unsigned groups = (unsigned)((n_envs + kGaeThreads - 1) / kGaeThreads);
-    hipLaunchKernelGGL(gae_kernel<GaeArgsTrunc>, dim3(groups), dim3(kGaeThreads), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-}
+}  // namespace
 
-int launch_gae_column(const float* rows, const float* reward_col, const float* values, float* advantages, float* returns,
-                      const int32_t* trunc_step, const float* v_terminal, int n_slots, int n_steps, int n_envs, int n_obs,
-                      float gamma, float gae_lambda, void* stream) {
-    if (n_steps < 1 || n_envs < 1 || n_obs < 1 || (trunc_step && n_slots < 1)) return (int)hipErrorInvalidValue;
-    const unsigned groups = (unsigned)((n_envs + kGaeThreads - 1) / kGaeThreads);
-    if (trunc_step) {
-        GaeArgsTruncCol a{{{rows, values, advantages, returns, n_steps, n_envs, n_obs, n_obs + 2, gamma, gae_lambda}, trunc_step, v_terminal, n_slots},
-                          reward_col};
-        hipLaunchKernelGGL(gae_kernel<GaeArgsTruncCol>, dim3(groups), dim3(kGaeThreads), 0, (hipStream_t)stream, a);
-    } else {
-        GaeArgsCol a{{rows, values, advantages, returns, n_steps, n_envs, n_obs, n_obs + 2, gamma, gae_lambda}, reward_col};
-        hipLaunchKernelGGL(gae_kernel<GaeArgsCol>, dim3(groups), dim3(kGaeThreads), 0, (hipStream_t)stream, a);
-    }
-    return (int)hipGetLastError();
+int launch_gae(const GaeLaunch& g, void* stream) {
+    if (g.n_steps < 1 || g.n_envs < 1 || g.n_obs < 1 || (g.trunc_step && g.n_slots < 1)) return (int)hipErrorInvalidValue;
+    const GaeArgs rows{g.rows, g.values, g.advantages, g.returns, g.n_steps, g.n_envs, g.n_obs, g.n_obs + 2, g.gamma, g.gae_lambda};
+    const GaeArgsTrunc slots{rows, g.trunc_step, g.v_terminal, g.n_slots};
+    if (!g.reward_col) return !g.trunc_step ? launch_gae_on(rows, stream) : launch_gae_on(slots, stream);
+    return g.trunc_step ? launch_gae_on(GaeArgsTruncCol{slots, g.reward_col}, stream) : launch_gae_on(GaeArgsCol{rows, g.reward_col}, stream);
 }
 
 int launch_truncation_scan(const TruncArgs& a, void* stream) {

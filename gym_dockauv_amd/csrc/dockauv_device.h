@@ -612,9 +612,26 @@ int launch_policy_backward(const PolicyShape& s, const float* packed, const floa
 // ------------------------------------------------------------------------------------------ GAE (dockauv_collect.hip)
 // SB3's compute_returns_and_advantage over packed rows: rows [K][N][row_stride] with the reward in column n_obs and done in
 // column n_obs + 1 (the observation columns are never read), values [K + 1][N], advantages / returns [K][N]; one lane per
-// env walks k = K - 1 .. 0.  The float32 expression order is stated in include/dockauv.h (dockauv_gae).  Returns a hipError_t.
-int launch_gae(const float* rows, const float* values, float* advantages, float* returns, int n_steps, int n_envs, int n_obs,
-               float gamma, float gae_lambda, void* stream);
+// env walks k = K - 1 .. 0.  The float32 expression order is stated in include/dockauv.h (dockauv_gae).  One kernel, instantiated on
+// what the two nullable parts ask for.  trunc_step (with v_terminal and n_slots; the tables of the truncation bootstrap, below): at
+// step trunc_step[s][env] the reward is fmaf(gamma, v_terminal[s][env], reward); without a used slot the bits are those without the
+// tables.  reward_col [K][N]: the reward is read from it instead of the rows' reward word (the done word still comes from the
+// rows).
+struct GaeLaunch {                        // (a call's own arguments first: the C ABI initialises those as an aggregate)
+    const float* rows;                    // [K][N][n_obs + 2]
+    const float* values;                  // [K + 1][N]
+    float* advantages;                    // [K][N]
+    float* returns;                       // [K][N]
+    int n_steps;
+    float gamma, gae_lambda;
+    const float* reward_col;              // [K][N], nullable
+    int n_envs, n_obs;
+    const int32_t* trunc_step;            // [n_slots][N], nullable
+    const float* v_terminal;              // [n_slots][N]
+    int n_slots;
+};
+// One launch.  Returns a hipError_t as int.
+int launch_gae(const GaeLaunch& g, void* stream);
 
 // ------------------------------------------------------------------------------------------ truncation bootstrap (dockauv_collect.hip)
 // SB3's rewards[idx] += gamma * V(terminal_observation) for the dones that are time limits (include/dockauv.h:
@@ -634,11 +651,6 @@ struct TruncArgs {
 };
 // One launch.  Returns a hipError_t as int.
 int launch_truncation_scan(const TruncArgs& a, void* stream);
-// launch_gae with the bootstrap: at step trunc_step[s][env] the reward is fmaf(gamma, v_terminal[s][env], reward).  The same
-// kernel instantiated on the two tables; without a used slot the bits are launch_gae's.  Returns a hipError_t as int.
-int launch_gae_truncated(const float* rows, const float* values, float* advantages, float* returns, const int32_t* trunc_step,
-                         const float* v_terminal, int n_slots, int n_steps, int n_envs, int n_obs, float gamma, float gae_lambda,
-                         void* stream);
 
 // ------------------------------------------------------------------------------------------ PPO head (dockauv_head.hip)
 // Loss terms, statistics and the gradients on the networks' raw outputs and on log_std for one minibatch (include/dockauv.h:
@@ -816,12 +828,6 @@ struct RewnormArgs {
 int launch_rewnorm_scan(const RewnormArgs& a, void* stream);
 // carry <- 0, state <- (0, 1, 1e-4, 0): one launch.  Returns a hipError_t as int.
 int launch_rewnorm_reset(float* carry, double* state, int n_envs, void* stream);
-// launch_gae / launch_gae_truncated with the reward read from reward_col [K][N] instead of the rows' reward word (the done word
-// still comes from the rows): the same kernel instantiated on argument blocks with the column.  trunc_step == nullptr: without
-// the truncation slots.  Returns a hipError_t as int.
-int launch_gae_column(const float* rows, const float* reward_col, const float* values, float* advantages, float* returns,
-                      const int32_t* trunc_step, const float* v_terminal, int n_slots, int n_steps, int n_envs, int n_obs,
-                      float gamma, float gae_lambda, void* stream);
 
 #ifdef DOCKAUV_STAMPS
 int read_stamps(unsigned long long* out);   // diagnostic build only

@@ -707,13 +707,9 @@ class BatchedDocking3d:
                                    C.c_void_p(stream or None))
         _capi.check(self._lib, self._handle, rc, "dockauv_gae")
 
-    def collect_device(self, policy, value, rows_in_ptr: int, rows_out_ptr: int, actions_out_ptr: int, n_steps: int,
-                       gamma: float = 0.99, gae_lambda: float = 0.95, t0: int = 0, stochastic: bool = True, stream: int = 0,
-                       terminal_obs_ptr: int = 0, log_prob_ptr: int = 0, values_ptr: int = 0, advantages_ptr: int = 0,
-                       returns_ptr: int = 0) -> None:
-        """One PPO iteration's collection queued by one host call (dockauv_collect): the rollout (log_prob [K][N] when asked
-        for), V of the K + 1 observation sets -> values [K + 1][N], GAE -> advantages, returns [K][N].  ``value`` None: rollout
-        and log-probabilities only.  Asynchronous; raises like poll_status()."""
+    def _collect_io(self, rows_in_ptr: int, rows_out_ptr: int, actions_out_ptr: int, n_steps: int, gamma: float, gae_lambda: float,
+                    t0: int, stochastic: bool, terminal_obs_ptr: int, log_prob_ptr: int, values_ptr: int, advantages_ptr: int,
+                    returns_ptr: int):
         io = _capi.CollectIO()
         io.struct_size = C.sizeof(_capi.CollectIO)
         io.n_steps = int(n_steps)
@@ -722,6 +718,17 @@ class BatchedDocking3d:
         io.values, io.advantages, io.returns = values_ptr or None, advantages_ptr or None, returns_ptr or None
         io.t0, io.stochastic = int(t0), 1 if stochastic else 0
         io.gamma, io.gae_lambda = float(gamma), float(gae_lambda)
+        return io
+
+    def collect_device(self, policy, value, rows_in_ptr: int, rows_out_ptr: int, actions_out_ptr: int, n_steps: int,
+                       gamma: float = 0.99, gae_lambda: float = 0.95, t0: int = 0, stochastic: bool = True, stream: int = 0,
+                       terminal_obs_ptr: int = 0, log_prob_ptr: int = 0, values_ptr: int = 0, advantages_ptr: int = 0,
+                       returns_ptr: int = 0) -> None:
+        """One PPO iteration's collection queued by one host call (dockauv_collect): the rollout (log_prob [K][N] when asked
+        for), V of the K + 1 observation sets -> values [K + 1][N], GAE -> advantages, returns [K][N].  ``value`` None: rollout
+        and log-probabilities only.  Asynchronous; raises like poll_status()."""
+        io = self._collect_io(rows_in_ptr, rows_out_ptr, actions_out_ptr, n_steps, gamma, gae_lambda, t0, stochastic, terminal_obs_ptr,
+                              log_prob_ptr, values_ptr, advantages_ptr, returns_ptr)
         rc = self._lib.dockauv_collect(self._handle, policy.ptr, value.ptr if value is not None else None, C.byref(io),
                                        C.c_void_p(stream or None))
         _capi.check(self._lib, self._handle, rc, "dockauv_collect")
@@ -774,14 +781,8 @@ class BatchedDocking3d:
         """``collect_device`` with the truncation bootstrap (dockauv_collect_truncated): length_carry <- the handle's step
         counters, the rollout, the two value launches, then ``gae_truncated_device``'s three launches in place of the GAE
         launch.  Needs a critic and terminal_obs.  Asynchronous; raises like poll_status()."""
-        cio = _capi.CollectIO()
-        cio.struct_size = C.sizeof(_capi.CollectIO)
-        cio.n_steps = int(n_steps)
-        cio.rows_in, cio.rows_out, cio.actions_out = rows_in_ptr or None, rows_out_ptr or None, actions_out_ptr or None
-        cio.terminal_obs, cio.log_prob = terminal_obs_ptr or None, log_prob_ptr or None
-        cio.values, cio.advantages, cio.returns = values_ptr or None, advantages_ptr or None, returns_ptr or None
-        cio.t0, cio.stochastic = int(t0), 1 if stochastic else 0
-        cio.gamma, cio.gae_lambda = float(gamma), float(gae_lambda)
+        cio = self._collect_io(rows_in_ptr, rows_out_ptr, actions_out_ptr, n_steps, gamma, gae_lambda, t0, stochastic, terminal_obs_ptr,
+                               log_prob_ptr, values_ptr, advantages_ptr, returns_ptr)
         tio = self._truncation_io(n_steps, n_slots, rows_out_ptr, terminal_obs_ptr, length_carry_ptr, trunc_step_ptr, trunc_row_ptr,
                                   values_ptr, v_terminal_ptr, advantages_ptr, returns_ptr, gamma, gae_lambda)
         rc = self._lib.dockauv_collect_truncated(self._handle, policy.ptr, value.ptr if value is not None else None, C.byref(cio),
@@ -1077,14 +1078,8 @@ class BatchedDocking3d:
         ``reward_normalizer_scan_device``, then ``gae_normalized_device`` -- with ``trunc`` (see there; its terminal_obs is
         ``terminal_obs_ptr``) the truncation bootstrap on the normalised rewards.  Needs a critic.  Asynchronous; raises like
         poll_status()."""
-        cio = _capi.CollectIO()
-        cio.struct_size = C.sizeof(_capi.CollectIO)
-        cio.n_steps = int(n_steps)
-        cio.rows_in, cio.rows_out, cio.actions_out = rows_in_ptr or None, rows_out_ptr or None, actions_out_ptr or None
-        cio.terminal_obs, cio.log_prob = terminal_obs_ptr or None, log_prob_ptr or None
-        cio.values, cio.advantages, cio.returns = values_ptr or None, advantages_ptr or None, returns_ptr or None
-        cio.t0, cio.stochastic = int(t0), 1 if stochastic else 0
-        cio.gamma, cio.gae_lambda = float(gamma), float(gae_lambda)
+        cio = self._collect_io(rows_in_ptr, rows_out_ptr, actions_out_ptr, n_steps, gamma, gae_lambda, t0, stochastic, terminal_obs_ptr,
+                               log_prob_ptr, values_ptr, advantages_ptr, returns_ptr)
         tio = None
         if trunc is not None:
             tio = self._truncation_io(n_steps, trunc["n_slots"], rows_out_ptr, terminal_obs_ptr, trunc["length_carry"],

@@ -271,6 +271,11 @@ class TorchDocking3d:
         has_v = value is not None
         values, adv, ret = (bufs["values"], bufs["adv"], bufs["ret"]) if has_v else (None, None, None)
         logp = bufs["logp"] if (policy.has_log_std and policy.shape.out_act == _capi.ACT_NONE) else None
+        ptr = lambda t: 0 if t is None else t.data_ptr()
+        common = dict(rows_in_ptr=rows[0].data_ptr(), rows_out_ptr=rows[1].data_ptr(), actions_out_ptr=bufs["acts"].data_ptr(), n_steps=K,
+                      gamma=gamma, gae_lambda=gae_lambda, t0=self._t, stochastic=stochastic,
+                      stream=torch.cuda.current_stream().cuda_stream, terminal_obs_ptr=ptr(term), log_prob_ptr=ptr(logp),
+                      values_ptr=ptr(values), advantages_ptr=ptr(adv), returns_ptr=ptr(ret))
         ws = None
         if bootstrap_truncated:
             ws = bufs.get("trunc")
@@ -287,28 +292,16 @@ class TorchDocking3d:
             trunc = None if ws is None else dict(n_slots=ws["slots"], length_carry=ws["carry"].data_ptr(),
                                                  trunc_step=ws["step"].data_ptr(), trunc_row=ws["row"].data_ptr(),
                                                  v_terminal=ws["v"].data_ptr())
-            self.batch.collect_normalized_device(policy, value, reward_norm.handle, rows[0].data_ptr(), rows[1].data_ptr(),
-                                                 bufs["acts"].data_ptr(), K, nws["norm"].data_ptr(), nws["disc"].data_ptr(),
-                                                 nws["stats"].data_ptr(), values.data_ptr(), adv.data_ptr(), ret.data_ptr(),
-                                                 training=reward_norm.training, gamma=gamma, gae_lambda=gae_lambda, t0=self._t,
-                                                 stochastic=stochastic, stream=torch.cuda.current_stream().cuda_stream,
-                                                 terminal_obs_ptr=term.data_ptr() if term is not None else 0,
-                                                 log_prob_ptr=0 if logp is None else logp.data_ptr(), trunc=trunc)
+            self.batch.collect_normalized_device(policy, value, reward_norm.handle, reward_norm_ptr=nws["norm"].data_ptr(),
+                                                 discounted_ptr=nws["disc"].data_ptr(), step_stats_ptr=nws["stats"].data_ptr(),
+                                                 training=reward_norm.training, trunc=trunc, **common)
             reward_norm._attach(nws)
         elif bootstrap_truncated:
-            self.batch.collect_truncated_device(policy, value, rows[0].data_ptr(), rows[1].data_ptr(), bufs["acts"].data_ptr(), K,
-                                                ws["slots"], term.data_ptr(), values.data_ptr(), adv.data_ptr(), ret.data_ptr(),
-                                                ws["carry"].data_ptr(), ws["step"].data_ptr(), ws["row"].data_ptr(),
-                                                ws["v"].data_ptr(), gamma=gamma, gae_lambda=gae_lambda, t0=self._t,
-                                                stochastic=stochastic, stream=torch.cuda.current_stream().cuda_stream,
-                                                log_prob_ptr=0 if logp is None else logp.data_ptr())
+            self.batch.collect_truncated_device(policy, value, n_slots=ws["slots"], length_carry_ptr=ws["carry"].data_ptr(),
+                                                trunc_step_ptr=ws["step"].data_ptr(), trunc_row_ptr=ws["row"].data_ptr(),
+                                                v_terminal_ptr=ws["v"].data_ptr(), **common)
         else:
-            self.batch.collect_device(policy, value, rows[0].data_ptr(), rows[1].data_ptr(), bufs["acts"].data_ptr(), K, gamma=gamma,
-                                      gae_lambda=gae_lambda, t0=self._t, stochastic=stochastic,
-                                      stream=torch.cuda.current_stream().cuda_stream,
-                                      terminal_obs_ptr=term.data_ptr() if term is not None else 0, log_prob_ptr=0 if logp is None else logp.data_ptr(),
-                                      values_ptr=values.data_ptr() if has_v else 0, advantages_ptr=adv.data_ptr() if has_v else 0,
-                                      returns_ptr=ret.data_ptr() if has_v else 0)
+            self.batch.collect_device(policy, value, **common)
         self._t += K
         self._gen += 1
         self._last_rows = rows[K]

@@ -517,6 +517,14 @@ def test_refusals_on_a_live_handle():
         # values NULL with a critic; critic buffers without one
         assert collect(pol, val, values=None) == -1 and b"with a critic" in err()
         assert collect(pol, None) == -1 and b"without a critic" in err()
+        # two defects at once: the first in the order of checks is the one reported (tests/test_collect_precedence_host.py has what
+        # is checked before the handle): the block before the actor, the actor before the critic
+        assert collect(o_pol, val, values=None) == -1 and b"with a critic" in err()
+        assert collect(o_pol, None) == -1 and b"without a critic" in err()
+        assert collect(o_pol, o_val) == -1 and b"dockauv_collect: the policy was created for another handle" in err()
+        assert collect(o_pol, pol) == -1 and b"dockauv_collect: the policy was created for another handle" in err()
+        assert collect(val, pol) == -1 and b"dockauv_collect: the policy is a critic" in err()
+        assert collect(val, o_val) == -1 and b"dockauv_collect: the policy is a critic" in err()
         # gamma outside [0, 1]; a critic whose input width is not the handle's; an actor's n_out is still the handle's n_u
         with pytest.raises(capi.DockAUVError, match="gamma"):
             env.gae_device(rows.data_ptr(), values.data_ptr(), K, 1.5, 0.95, adv.data_ptr(), ret.data_ptr())

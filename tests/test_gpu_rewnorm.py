@@ -415,6 +415,55 @@ def test_refusals_on_a_live_handle():
         out = C.c_void_p()
         assert lib.dockauv_rewnorm_create(e1._handle, 0.99, -1.0, 1e-8, C.byref(out)) == -1 and not out.value
         assert b"clip_reward" in lib.dockauv_last_error(e1._handle)
+
+        # two defects at once: the first in the order of checks is the one reported (tests/test_collect_precedence_host.py has what
+        # is checked before the handle).  The blocks' pointers are fake addresses: every call is refused first.
+        c = Cc()
+        h = e1._handle
+        err = lambda: lib.dockauv_last_error(h)
+        rn1 = e1.make_reward_normalizer(GAMMA)
+        mlp = c.P().make_mlp((20, (64, 64), 6, "tanh", "none"), seed=1, log_std=np.full(6, -0.5))
+        pol, val, o_pol = e1.make_policy(mlp), e1.make_value(c.make_critic(20, (64, 64))), e2.make_policy(mlp)
+        ptr = lambda obj: obj.ptr if obj is not None else None
+
+        def blocks(cio=None, tio=None):
+            nb, cb, tb = Hh().ios(_capi, K)
+            for block, over in ((cb, cio), (tb, tio)):
+                for name, value in (over or {}).items():
+                    setattr(block, name, value)
+            return nb, cb, tb
+
+        def collect(actor=pol, crit=val, rn=rn1, with_tio=False, cio=None, tio=None):
+            nb, cb, tb = blocks(cio, tio)
+            return lib.dockauv_collect_normalized(h, ptr(actor), ptr(crit), C.byref(cb), C.byref(tb) if with_tio else None, ptr(rn),
+                                                  C.byref(nb), None)
+        assert collect(rn=None, actor=None) == -1 and b"dockauv_collect_normalized: null normaliser" in err()
+        assert collect(rn=rn2, cio=dict(gamma=0.5)) == -1 and b"the normaliser was created for another handle" in err()
+        assert collect(cio=dict(gamma=0.5), actor=None) == -1 and b"dockauv_collect_io.gamma: 0.5, the normaliser's is 0.99" in err()
+        assert collect(actor=None, crit=None) == -1 and b"dockauv_collect_normalized: null actor" in err()
+        assert collect(crit=None, with_tio=True, tio=dict(n_slots=0)) == -1 and b"dockauv_collect_normalized: null critic" in err()
+        assert collect(with_tio=True, tio=dict(n_slots=0, rows_out=4096)) == -1 and b"dockauv_truncation_io.n_slots: 0" in err()
+        assert collect(with_tio=True, tio=dict(rows_out=4096), actor=o_pol) == -1
+        assert b"dockauv_truncation_io.rows_out is not dockauv_collect_io's" in err()
+        assert collect(with_tio=True, tio=dict(terminal_obs=4096, values=4096)) == -1
+        assert b"dockauv_truncation_io.terminal_obs is not dockauv_collect_io's" in err()
+        assert collect(actor=o_pol, crit=pol) == -1 and b"dockauv_collect_normalized: the policy was created for another handle" in err()
+
+        def gae(crit=val, tio=None):      # dockauv_gae_normalized with a truncation block: what the block must share with the call
+            _, cb, tb = blocks(tio=tio)
+            return lib.dockauv_gae_normalized(h, ptr(crit), C.c_void_p(640), C.byref(tb), C.c_void_p(cb.rows_out), C.c_void_p(cb.values),
+                                              K, 0.99, 0.95, C.c_void_p(cb.advantages), C.c_void_p(cb.returns), None)
+        whose = b"dockauv_gae_normalized's"
+        assert gae(crit=None, tio=dict(n_slots=0)) == -1 and b"dockauv_gae_normalized: null critic" in err()
+        assert gae(tio=dict(n_slots=0, n_steps=K + 1)) == -1 and b"dockauv_truncation_io.n_slots: 0" in err()
+        assert gae(tio=dict(n_steps=K + 1, rows_out=4096)) == -1 and b"dockauv_truncation_io.n_steps: 5, " + whose + b" is 4" in err()
+        assert gae(tio=dict(rows_out=4096, values=4096)) == -1 and b"dockauv_truncation_io.rows_out is not " + whose in err()
+        assert gae(tio=dict(values=4096, advantages=4096)) == -1 and b"dockauv_truncation_io.values is not " + whose in err()
+        assert gae(tio=dict(advantages=4096, returns=4096)) == -1 and b"dockauv_truncation_io.advantages is not " + whose in err()
+        assert gae(tio=dict(returns=4096, gamma=0.5)) == -1 and b"dockauv_truncation_io.returns is not " + whose in err()
+        assert gae(tio=dict(gamma=0.5, gae_lambda=0.5)) == -1 and b"dockauv_truncation_io.gamma: 0.5, " + whose + b" is 0.99" in err()
+        assert gae(tio=dict(gae_lambda=0.5), crit=pol) == -1 and b"dockauv_truncation_io.gae_lambda: 0.5, " + whose + b" is 0.95" in err()
+        assert gae(tio=dict(terminal_obs=4096), crit=pol) == -1 and b"not a critic" in err()   # (the call has no terminal_obs of its own)
         torch.cuda.synchronize()
     finally:
         e1.close()

@@ -432,6 +432,24 @@ def test_refusals_on_a_live_handle():
         assert collect(tio_for(env), values=rows0.data_ptr()) == -1 and b"dockauv_truncation_io.values" in err()
         assert collect(tio_for(env, n_slots=1)) == -1 and b"dockauv_truncation_io.n_slots" in err()
         assert lib.dockauv_collect_truncated(h, pol.ptr, val.ptr, None, C.byref(tio_for(env)), None) == -1 and b"cio is NULL" in err()
+        # two defects at once: the first in the order of checks is the one reported (tests/test_collect_precedence_host.py has what
+        # is checked before the handle)
+        assert collect(tio_for(env), actor=None, crit=None) == -1 and b"dockauv_collect_truncated: null actor" in err()
+        assert collect(tio_for(env), crit=None, struct_size=8) == -1 and b"dockauv_collect_truncated: null critic" in err()
+        assert collect(tio_for(env), struct_size=8, n_steps=0) == -1 and b"dockauv_collect_io.struct_size" in err()
+        assert collect(tio_for(env), n_steps=0, rows_in=None) == -1 and b"dockauv_collect_io.n_steps: 0" in err()
+        assert collect(tio_for(env), rows_in=None, terminal_obs=None) == -1 and b"rows_in/rows_out/actions_out must not be NULL" in err()
+        assert collect(tio_for(env, n_slots=1), terminal_obs=None, values=None) == -1 and b"dockauv_collect_io.terminal_obs is NULL" in err()
+        assert collect(tio_for(env, n_slots=1), values=None) == -1 and b"values/advantages/returns must not be NULL with a critic" in err()
+        assert collect(tio_for(env, n_slots=1), n_steps=K - 1) == -1 and b"dockauv_truncation_io.n_slots: 1" in err()
+        assert collect(tio_for(env, gamma=1.5)) == -1 and b"dockauv_truncation_io: gamma 1.5 outside [0, 1]" in err()
+        assert collect(tio_for(env), n_steps=K - 1, values=rows0.data_ptr()) == -1
+        assert b"dockauv_truncation_io.n_steps: 12, dockauv_collect_io's is 11" in err()
+        assert collect(tio_for(env), values=rows0.data_ptr(), gamma=0.5) == -1 and b"dockauv_truncation_io.values is not dockauv_collect_io's" in err()
+        assert collect(tio_for(env), gamma=0.5, actor=val) == -1 and b"dockauv_truncation_io.gamma: 0.99, dockauv_collect_io's is 0.5" in err()
+        assert collect(tio_for(env), gae_lambda=0.5, actor=val) == -1
+        assert b"dockauv_truncation_io.gae_lambda: 0.95, dockauv_collect_io's is 0.5" in err()
+        assert collect(tio_for(env), actor=val, crit=pol) == -1 and b"dockauv_collect_truncated: the policy is a critic" in err()
         # ... and the handle is usable afterwards
         good = tio_for(env)
         assert collect(good) == 0
