@@ -21,6 +21,9 @@ expression matches and that no traced run launched (why nothing selects the kern
 that launch it in child processes the tracer was not pointed at).
 
   python scripts/kernel_coverage.py --usage usage.txt --traces traces --notes profiles/coverage/notes.txt > profiles/coverage/kernels.txt
+
+--previous FILE: a refresh from traced runs of some test files only -- a kernel that FILE (a copy of the earlier record) lists as
+launched keeps that line's labels, with the labels of the new traces behind them.
 """
 import argparse
 import csv
@@ -59,7 +62,7 @@ def normalise(name: str) -> str:
             cut = i
             break
     name = name[:cut]
-    return re.sub(r"^dockauv::", "", name).strip()
+    return re.sub(r"\bdockauv::", "", name).strip()   # (also inside template arguments: gae_kernel<dockauv::GaeArgs>)
 
 
 def compiled_kernels(usage_text: str):
@@ -93,6 +96,8 @@ def main():
     ap.add_argument("--usage", help="output of `python gym_dockauv_amd/csrc/build.py --usage` (default: run it)")
     ap.add_argument("--traces", required=True, help="directory with one sub-directory of rocprofv3 output per traced run")
     ap.add_argument("--notes", help="file of `<regular expression> | <text>` lines for kernels no traced run launched")
+    ap.add_argument("--previous", help="an earlier record: the labels of its `launched` lines are kept for kernels that this call's "
+                                       "traces do not show (a refresh with traced runs of some test files only)")
     args = ap.parse_args()
     if args.usage:
         usage = open(args.usage).read()
@@ -102,6 +107,12 @@ def main():
         usage = r.stdout + r.stderr
     compiled = compiled_kernels(usage)
     launched = launched_kernels(args.traces)
+    if args.previous:   # (a record's label text is kept as it stands -- some lines carry remarks -- and new labels go behind it)
+        for line in open(args.previous):
+            m = re.match(r"^([^#].*?) (not-launched|launched) (.+)$", line.rstrip("\n"))
+            if m and m.group(2) == "launched":
+                new = [lab for lab in launched.get(m.group(1), []) if lab not in m.group(3).split()]
+                launched[m.group(1)] = [m.group(3)] + new
     notes = []
     if args.notes:
         for line in open(args.notes):

@@ -1,6 +1,7 @@
 """Peer-to-peer gather (include/dockauv.h "Multi-GPU" block, gym_dockauv_amd/parallel.py: P2PGather) on the GPU:
 a single rank, and a rehearsal with two and three rank PROCESSES sharing the box's one GPU (IPC handles, push kernel,
-stamps and bounded waits are what runs across GPUs; only the fabric is missing)."""
+stamps and bounded waits are what runs across GPUs; only the fabric is missing); at the end the copy kernels at the edges of
+their loops through the C entry points (byte tails, the four-chunk loop of a clamped grid, guards behind every destination)."""
 import os
 import subprocess
 import sys
@@ -218,3 +219,100 @@ def test_sharded_env_single_rank_equals_torch_env():
     for e in envs:
         e.close()
     ref.close()
+
+
+# ------------------------------------------------------------------------------------------ the copy kernels at their edges
+# copy_rows (dockauv_p2p.hip) moves n16 = bytes / 16 whole chunks on a grid of bx = min(ceil(n16 / 256), 2048) blocks of 256
+# threads -- four chunks per trip (i, i + stride, i + 2 stride, i + 3 stride; stride = bx * 256) while i + 3 * stride < n16, then
+# one per trip -- and block 0 moves the bytes % 16 tail bytes.  The four-chunk loop runs only on a clamped grid (bx = 2048) with
+# n16 > 3 * 2048 * 256; the smallest size at which it runs at least one trip (threads 0 .. 4 of block 0), leaves chunks to the
+# one-chunk loop (every other thread: three trips) and leaves a byte tail is (3 * 2048 * 256 + 5) chunks + 9 bytes, about 24 MiB.
+COPY_BIG = 2048 * 256 * 16 * 3 + 16 * 5 + 9
+COPY_SIZES = [1, 15, 16, 17, 256 * 16 + 7, COPY_BIG]
+COPY_GUARD = 256
+
+
+def _copy_buffers(nbytes):
+    """(source bytes: an int32 counter pattern, three destinations of nbytes + a guard each, filled with the guard byte)"""
+    import torch
+    dev = torch.device("cuda", 0)
+    src = (torch.arange((nbytes + 3) // 4 + 4, dtype=torch.int32, device=dev) + 0x01020304).view(torch.uint8)
+    dsts = [torch.full((nbytes + COPY_GUARD,), 0xA5, dtype=torch.uint8, device=dev) for _ in range(3)]
+    assert src.data_ptr() % 16 == 0 and all(d.data_ptr() % 16 == 0 for d in dsts)
+    return src, dsts
+
+
+def _check_copies(what, src, dsts, nbytes):
+    import torch
+    for k, d in enumerate(dsts):
+        assert torch.equal(d[:nbytes], src[:nbytes]), f"{what}: destination {k} differs from the source"
+        assert int(d[nbytes]) == 0xA5, f"{what}: destination {k}: the byte behind the end was written"
+        assert bool((d[nbytes:] == 0xA5).all()), f"{what}: destination {k}: the guard was written"
+
+
+@pytest.mark.parametrize("nbytes", COPY_SIZES)
+def test_push_copies_every_byte_and_nothing_more(nbytes):
+    import ctypes as C
+    import torch
+    from gym_dockauv_amd import _capi
+    lib = _capi.load_library()
+    n16 = nbytes // 16
+    bx = min(max((n16 + 255) // 256, 1), 2048)
+    assert (n16 > 3 * bx * 256) == (nbytes == COPY_BIG), "only the last size reaches the four-chunk loop"
+    if nbytes == COPY_BIG:
+        assert bx == 2048 and n16 - 3 * bx * 256 == 5 and nbytes % 16 == 9
+    src, dsts = _copy_buffers(nbytes)
+    ptrs = (C.c_void_p * 3)(*[d.data_ptr() for d in dsts])
+    stream = torch.cuda.current_stream().cuda_stream
+    assert lib.dockauv_p2p_push(src.data_ptr(), nbytes, ptrs, 3, stream) == 0
+    torch.cuda.synchronize()
+    _check_copies(f"push of {nbytes} bytes", src, dsts, nbytes)
+    # misaligned source or destination: refused (DOCKAUV_E_INVALID), nothing launched
+    assert lib.dockauv_p2p_push(src.data_ptr() + 4, nbytes, ptrs, 3, stream) == -1
+    bad = (C.c_void_p * 3)(dsts[0].data_ptr(), dsts[1].data_ptr() + 8, dsts[2].data_ptr())
+    assert lib.dockauv_p2p_push(src.data_ptr(), nbytes, bad, 3, stream) == -1
+    torch.cuda.synchronize()
+    _check_copies(f"refused pushes of {nbytes} bytes", src, dsts, nbytes)
+
+
+@pytest.mark.parametrize("nbytes", COPY_SIZES)
+def test_gather_without_stamps_copies_and_resets_its_counter(nbytes):
+    """dockauv_p2p_gather with stamp = wait_stamp = 0 on a plan of three local destinations that names a peer slot and a rank to
+    wait for: the copy of push, the flags left alone, the counter back at 0 after each of three calls in a row (a counter that is
+    not reset makes the second call's last block go unnoticed -- without stamps only the counter word shows it)."""
+    import ctypes as C
+    import torch
+    from gym_dockauv_amd import _capi
+    from gym_dockauv_amd.parallel import _DevArray
+    lib = _capi.load_library()
+    flags = C.c_void_p()
+    assert lib.dockauv_p2p_alloc(0, 256, 1, C.byref(flags), None) == 0
+    words = torch.as_tensor(_DevArray(flags.value, (64,), "<i4"), device="cuda:0")
+    try:
+        words[:32] = 7                      # flags; status = words 32, 33; counter = word 48
+        src, dsts = _copy_buffers(nbytes)
+        pl = _capi.P2PPlan()
+        for d in range(3):
+            pl.dsts[d] = dsts[d].data_ptr()
+        pl.peer_slots[0] = flags.value + 4
+        pl.my_flags, pl.status, pl.counter = flags.value, flags.value + 128, flags.value + 192
+        pl.bytes, pl.max_spins = nbytes, 2000
+        pl.n_dsts, pl.n_peers, pl.world, pl.my_rank = 3, 1, 2, 0
+        stream = torch.cuda.current_stream().cuda_stream
+        expected = [7] * 32 + [0] * 32
+        for call in range(3):
+            assert lib.dockauv_p2p_gather(C.byref(pl), src.data_ptr(), 0, 0, stream) == 0
+            torch.cuda.synchronize()
+            _check_copies(f"gather {call} of {nbytes} bytes", src, dsts, nbytes)
+            assert words.cpu().tolist() == expected, f"gather {call}: flags, status or counter moved"
+            for d in dsts:
+                d.fill_(0xA5)
+        assert lib.dockauv_p2p_gather(C.byref(pl), src.data_ptr() + 4, 0, 0, stream) == -1     # DOCKAUV_E_INVALID
+        pl.dsts[1] = dsts[1].data_ptr() + 8
+        assert lib.dockauv_p2p_gather(C.byref(pl), src.data_ptr(), 0, 0, stream) == -1
+        torch.cuda.synchronize()
+        assert all(bool((d == 0xA5).all()) for d in dsts), "a refused gather wrote"
+    finally:
+        words = None
+        torch.cuda.synchronize()
+        assert lib.dockauv_p2p_free(flags) == 0
