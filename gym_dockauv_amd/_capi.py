@@ -202,6 +202,22 @@ class EvalIO(C.Structure):
     ]
 
 
+class ReplayPushIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_steps", C.c_int32),
+        ("rows_in", C.c_void_p), ("rows_out", C.c_void_p), ("actions", C.c_void_p), ("terminal_obs", C.c_void_p),
+        ("ep_outcome", C.c_void_p),
+    ]
+
+
+class ReplaySampleIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_batches", C.c_int32), ("batch_size", C.c_longlong),
+        ("obs", C.c_void_p), ("actions", C.c_void_p), ("next_obs", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p),
+        ("index", C.c_void_p),
+    ]
+
+
 # every symbol include/dockauv.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("dockauv_abi_version", C.c_int, []),
@@ -286,6 +302,15 @@ SYMBOLS = [
                                          C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("dockauv_collect_normalized", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CollectIO), C.POINTER(TruncationIO),
                                              C.c_void_p, C.POINTER(RewnormIO), C.c_void_p]),
+    ("dockauv_replay_create", C.c_int, [C.c_void_p, C.c_longlong, C.c_uint64, C.POINTER(C.c_void_p)]),
+    ("dockauv_replay_destroy", C.c_int, [C.c_void_p]),
+    ("dockauv_replay_sync", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("dockauv_replay_push", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ReplayPushIO), C.c_void_p]),
+    ("dockauv_replay_sample", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ReplaySampleIO), C.c_void_p]),
+    ("dockauv_replay_counts", C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_uint64)]),
+    ("dockauv_replay_set_counts", C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.c_uint64]),
+    ("dockauv_replay_state", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong),
+                                       C.POINTER(C.c_int)]),
 ]
 
 _lib: Optional[C.CDLL] = None

@@ -1,5 +1,5 @@
 // dockauv_capi.h -- what the translation units of the C ABI share (dockauv_capi.hip, dockauv_capi_policy.hip,
-// dockauv_capi_eval.hip, dockauv_p2p.hip): the env handle, error reporting, the step launch.  Internal to libdockauv.so.
+// dockauv_capi_eval.hip, dockauv_capi_replay.hip, dockauv_p2p.hip): the env handle, error reporting, the step launch.  Internal to libdockauv.so.
 #pragma once
 #include <hip/hip_runtime.h>
 

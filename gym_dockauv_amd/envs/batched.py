@@ -959,6 +959,73 @@ class BatchedDocking3d:
             self._lib.dockauv_monitor_destroy(monitor.ptr)
             monitor.ptr = C.c_void_p()
 
+    # ------------------------------------------------------------------------------------------ replay buffer
+    def make_replay(self, buffer_size: int, seed: int = 0):
+        """A replay buffer of this handle (dockauv_replay_create): a zero-filled ring of max(buffer_size // num_envs, 1) step
+        slots and the observation carry.  Needs a float32 handle with an auto-reset mode.  ``close`` destroys it before the
+        handle."""
+        from ..replay import DeviceReplay
+        ptr = C.c_void_p()
+        rc = self._lib.dockauv_replay_create(self._handle, int(buffer_size), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(ptr))
+        _capi.check(self._lib, self._handle, rc, "dockauv_replay_create")
+        rb = DeviceReplay(ptr)
+        self._replays = getattr(self, "_replays", []) + [rb]
+        return rb
+
+    def replay_sync_device(self, replay, rows_ptr: int, stream: int = 0) -> None:
+        """The buffer's observation carry <- the observation columns of rows [N][n_obs + 2] (dockauv_replay_sync): the rows
+        the next step reads, after steps the buffer did not see.  Asynchronous."""
+        rc = self._lib.dockauv_replay_sync(self._handle, replay.ptr, C.c_void_p(rows_ptr or None), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_replay_sync")
+
+    def replay_push_device(self, replay, rows_out_ptr: int, actions_ptr: int, terminal_obs_ptr: int, n_steps: int,
+                           rows_in_ptr: int = 0, ep_outcome_ptr: int = 0, stream: int = 0) -> None:
+        """Store the K = n_steps transitions of rows_out [K][N][n_obs + 2], actions [K][N][n_u] and terminal_obs [K][N][n_obs]
+        (dockauv_replay_push); rows_in [N][n_obs + 2] or 0 (the carry); ep_outcome uint8 [K][N] or 0 (no time limits).
+        Asynchronous."""
+        io = _capi.ReplayPushIO()
+        io.struct_size = C.sizeof(_capi.ReplayPushIO)
+        io.n_steps = n_steps
+        io.rows_in, io.rows_out, io.actions = rows_in_ptr or None, rows_out_ptr or None, actions_ptr or None
+        io.terminal_obs, io.ep_outcome = terminal_obs_ptr or None, ep_outcome_ptr or None
+        rc = self._lib.dockauv_replay_push(self._handle, replay.ptr, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_replay_push")
+
+    def replay_sample_device(self, replay, batch_size: int, n_batches: int, obs_ptr: int, actions_ptr: int, next_obs_ptr: int,
+                             rewards_ptr: int, dones_ptr: int, index_ptr: int = 0, stream: int = 0) -> None:
+        """n_batches minibatches of batch_size stored transitions (dockauv_replay_sample): obs / next_obs [G][B][n_obs],
+        actions [G][B][n_u], rewards / dones [G][B], index int64 [G][B] or 0.  Asynchronous."""
+        io = _capi.ReplaySampleIO()
+        io.struct_size = C.sizeof(_capi.ReplaySampleIO)
+        io.n_batches, io.batch_size = n_batches, batch_size
+        io.obs, io.actions, io.next_obs = obs_ptr or None, actions_ptr or None, next_obs_ptr or None
+        io.rewards, io.dones, io.index = rewards_ptr or None, dones_ptr or None, index_ptr or None
+        rc = self._lib.dockauv_replay_sample(self._handle, replay.ptr, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_replay_sample")
+
+    def replay_counts(self, replay):
+        """(pos, size, draws): dockauv_replay_counts"""
+        pos, size, draws = C.c_longlong(), C.c_longlong(), C.c_uint64()
+        rc = self._lib.dockauv_replay_counts(replay.ptr, C.byref(pos), C.byref(size), C.byref(draws))
+        _capi.check(self._lib, self._handle, rc, "dockauv_replay_counts")
+        return int(pos.value), int(size.value), int(draws.value)
+
+    def replay_set_counts(self, replay, pos: int, size: int, draws: int) -> None:
+        rc = self._lib.dockauv_replay_set_counts(replay.ptr, int(pos), int(size), int(draws))
+        _capi.check(self._lib, self._handle, rc, "dockauv_replay_set_counts")
+
+    def replay_state(self, replay):
+        """(device address of the ring, of the current carry, capacity_steps, record_floats): dockauv_replay_state"""
+        st, ca, cap, rf = C.c_void_p(), C.c_void_p(), C.c_longlong(), C.c_int()
+        rc = self._lib.dockauv_replay_state(replay.ptr, C.byref(st), C.byref(ca), C.byref(cap), C.byref(rf))
+        _capi.check(self._lib, self._handle, rc, "dockauv_replay_state")
+        return int(st.value or 0), int(ca.value or 0), int(cap.value), int(rf.value)
+
+    def destroy_replay(self, replay) -> None:
+        if replay.ptr is not None and replay.ptr.value:
+            self._lib.dockauv_replay_destroy(replay.ptr)
+            replay.ptr = C.c_void_p()
+
     # ------------------------------------------------------------------------------------------ policy evaluation
     def make_evaluator(self, max_episodes_per_env: int):
         """An evaluator of this handle (dockauv_eval_create): per-env carries, counts and quotas, ``max_episodes_per_env`` episode
@@ -1137,6 +1204,9 @@ class BatchedDocking3d:
             for mon in getattr(self, "_monitors", []):   # (a monitor goes before its handle)
                 self.destroy_monitor(mon)
             self._monitors = []
+            for rb in getattr(self, "_replays", []):     # (a replay buffer goes before its handle)
+                self.destroy_replay(rb)
+            self._replays = []
             for ev in getattr(self, "_evaluators", []):  # (an evaluator goes before its handle)
                 self.destroy_evaluator(ev)
             self._evaluators = []

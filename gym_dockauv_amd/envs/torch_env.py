@@ -73,14 +73,20 @@ class TorchDocking3d:
         self._packed[self._i % len(self._packed)].zero_()
         return self._packed[self._i % len(self._packed)][:, : self.n_obs]
 
-    def step(self, actions, want_terminal_obs: bool = False):
+    def step(self, actions, want_terminal_obs: bool = False, replay=None):
         """actions: float32 [num_envs, n_u] on this device (contiguous).  Returns (obs, reward, done) views;
         with auto-reset the rows of finished envs already hold the reset observation and, if asked for,
-        ``self.terminal_observation`` the last one of the finished episode."""
+        ``self.terminal_observation`` the last one of the finished episode.
+        ``replay`` (``make_replay_buffer``): forces ``want_terminal_obs`` and stores this step's transition as
+        ``rb.rollout`` stores its K -- the path of a learner whose actor runs in torch.  ``actions`` are read when the push runs
+        on the stream.  Without it not one launch is added or changed."""
         torch = self.torch
         if actions.device != self.device or actions.dtype != torch.float32 or not actions.is_contiguous() \
                 or tuple(actions.shape) != (self.num_envs, self.n_u):
             raise ValueError(f"actions must be a contiguous float32 [{self.num_envs}, {self.n_u}] tensor on {self.device}")
+        if replay is not None:
+            want_terminal_obs = True
+            self._replay_before(replay, self._last_rows if self._last_rows is not None else self._packed[self._i % len(self._packed)])
         self._i += 1
         self._t += 1
         self._gen += 1
@@ -96,6 +102,8 @@ class TorchDocking3d:
         # the kernels' sticky status word (a tail role that gave up waiting: rows since are invalid) is host-coherent
         # memory: looked at every step without a synchronisation; what it shows belongs to steps that have already run
         self.batch.poll_status()
+        if replay is not None:
+            self._replay_after(replay, out.unsqueeze(0), actions.unsqueeze(0), self._terminal.unsqueeze(0))
         return out[:, : self.n_obs], out[:, self.n_obs], out[:, self.n_obs + 1] > 0.5
 
     # ------------------------------------------------------------------------------------------ closed loop
@@ -178,6 +186,33 @@ class TorchDocking3d:
         monitor.scan(rows, terminal_obs=term, values=values, returns=returns)
         monitor.seen = self._gen
 
+    def make_replay_buffer(self, buffer_size: int, seed: int = 0, handle_timeout_termination: bool = True, monitor=None):
+        """A ``DeviceReplayBuffer`` (gym_dockauv_amd/replay.py) of this env for ``rb.rollout(...)``, ``rb.collect(...)``
+        and ``step(..., replay=rb)``: SB3's ``ReplayBuffer(buffer_size, n_envs=num_envs)`` on the device, max(
+        buffer_size // num_envs, 1) steps of every env; ``seed``: of its minibatch indices.  ``handle_timeout_termination``
+        (SB3's default too): a done that is a time limit and nothing else is sampled as ``dones`` = 0; which dones those are
+        comes from ``monitor`` (``make_monitor``; None: one of the buffer's own) through its per-row outcomes."""
+        from ..replay import DeviceReplayBuffer
+        return DeviceReplayBuffer(self, buffer_size, seed=seed, handle_timeout_termination=handle_timeout_termination, monitor=monitor)
+
+    def _replay_before(self, replay, cur) -> None:
+        """before a call with ``replay=`` queues its steps: ``cur`` are the rows the first step's actor reads; they become the
+        buffer's observation carry unless its last push ended where the trajectory is"""
+        if replay.env is not self:
+            raise ValueError("the replay buffer belongs to another env")
+        if replay.monitor is not None:
+            self._monitor_before(replay.monitor)
+        if replay.seen != self._gen:
+            replay.sync(cur)
+
+    def _replay_after(self, replay, rows, acts, term, values=None, returns=None) -> None:
+        ep_outcome = None
+        if replay.monitor is not None:
+            ep_outcome = replay.monitor.scan(rows, terminal_obs=term, values=values, returns=returns, per_row=True)[3]
+            replay.monitor.seen = self._gen
+        replay.push(rows, acts, term, ep_outcome=ep_outcome)
+        replay.seen = self._gen
+
     def rollout(self, policy, n_steps: int, stochastic: bool = False, want_terminal_obs: bool = False, monitor=None):
         """``n_steps`` x (policy, step) queued by ONE host call (dockauv_rollout) on the current stream, starting from the rows
         the env last wrote (``reset``, ``step`` or an earlier ``rollout``: one trajectory).  Returns
@@ -185,14 +220,27 @@ class TorchDocking3d:
         returned for actions[k].  Views of buffers the env owns, reused by the next ``rollout`` of the same K; with
         ``want_terminal_obs`` ``self.rollout_terminal_observation`` [K, N, n_obs] holds the last observation where done.
         ``monitor`` (``make_monitor``): forces ``want_terminal_obs`` and queues the episode scan of these K steps behind them on
-        the same stream; ``monitor.stats`` holds the result.  Without it no launch is added and none is changed."""
+        the same stream; ``monitor.stats`` holds the result.  Without it no launch is added and none is changed.
+        The same call that also stores its K transitions in a replay buffer: ``DeviceReplayBuffer.rollout``."""
+        return self._rollout(policy, n_steps, stochastic, want_terminal_obs, monitor, None)
+
+    def _rollout(self, policy, n_steps, stochastic, want_terminal_obs, monitor, replay):
+        """``rollout``; ``replay`` (None or a ``DeviceReplayBuffer``: ``rb.rollout``) forces ``want_terminal_obs``; in front of the
+        steps, if the buffer has not seen the env's current generation, the copy of the rows the first step reads into its
+        carry; behind the steps its monitor's scan and the push of these K transitions (K at most ``replay.capacity_steps``).
+        When ``monitor`` is the buffer's own monitor the one scan serves both.  With None not one launch is added or changed."""
         torch = self.torch
         K = int(n_steps)
         if K < 1:
             raise ValueError("n_steps must be >= 1")
+        if replay is not None and K > replay.capacity_steps:
+            raise ValueError(f"n_steps {K} exceeds the replay buffer's capacity_steps {replay.capacity_steps}")
         if monitor is not None:
             want_terminal_obs = True
             self._monitor_before(monitor)
+        if replay is not None:
+            want_terminal_obs = True
+            self._replay_before(replay, self._last_rows if self._last_rows is not None else self._packed[self._i % len(self._packed)])
         bufs = self._rollout_bufs.get(K)
         if bufs is None:
             bufs = self._rollout_bufs[K] = [torch.zeros((K, self.num_envs, self.n_obs + 2), device=self.device, dtype=torch.float32),
@@ -210,8 +258,10 @@ class TorchDocking3d:
         self._gen += 1
         self._last_rows = rows[K - 1]
         self.rollout_terminal_observation = term if want_terminal_obs else None
-        if monitor is not None:
+        if monitor is not None and not (replay is not None and replay.monitor is monitor):
             self._monitor_after(monitor, rows, term)
+        if replay is not None:
+            self._replay_after(replay, rows, acts, term)
         return rows[:, :, : self.n_obs], acts, rows[:, :, self.n_obs], rows[:, :, self.n_obs + 1] > 0.5
 
     def collect(self, policy, value, n_steps: int, gamma: float, gae_lambda: float, stochastic: bool = True,
@@ -237,11 +287,21 @@ class TorchDocking3d:
         are those of the normalised rewards, with ``bootstrap_truncated`` of normalised reward + gamma * V(terminal
         observation).  ``reward`` stays the raw column (the monitor's returns stay sums of raw rewards), values and log_prob are
         what they are without it; the tuple keeps its fields.  Needs a critic and ``rn.gamma == gamma``.  With the default
-        not one launch is added or changed."""
+        not one launch is added or changed.
+        The same call that also stores its K transitions in a replay buffer: ``DeviceReplayBuffer.collect``."""
+        return self._collect(policy, value, n_steps, gamma, gae_lambda, stochastic, want_terminal_obs, monitor, bootstrap_truncated,
+                             reward_norm, None)
+
+    def _collect(self, policy, value, n_steps, gamma, gae_lambda, stochastic, want_terminal_obs, monitor, bootstrap_truncated,
+                 reward_norm, replay):
+        """``collect``; ``replay`` (None or a ``DeviceReplayBuffer``: ``rb.collect``) stores these K transitions (raw rewards)
+        exactly as ``_rollout`` does.  With None not one launch is added or changed."""
         torch = self.torch
         K = int(n_steps)
         if K < 1:
             raise ValueError("n_steps must be >= 1")
+        if replay is not None and K > replay.capacity_steps:
+            raise ValueError(f"n_steps {K} exceeds the replay buffer's capacity_steps {replay.capacity_steps}")
         if reward_norm is not None:
             if value is None:
                 raise ValueError("reward_norm needs a critic: it changes advantages and returns only")
@@ -256,6 +316,9 @@ class TorchDocking3d:
         if monitor is not None:
             want_terminal_obs = True
             self._monitor_before(monitor)
+        if replay is not None:
+            want_terminal_obs = True
+            self._replay_before(replay, self._last_rows if self._last_rows is not None else self._packed[self._i % len(self._packed)])
         N = self.num_envs
         bufs = self._collect_bufs.get(K)
         if bufs is None:
@@ -306,8 +369,11 @@ class TorchDocking3d:
         self._gen += 1
         self._last_rows = rows[K]
         self.rollout_terminal_observation = term
-        if monitor is not None:
+        same = replay is not None and monitor is not None and replay.monitor is monitor
+        if monitor is not None and not same:
             self._monitor_after(monitor, rows[1:], term, values, ret)
+        if replay is not None:
+            self._replay_after(replay, rows[1:], bufs["acts"], term, *((values, ret) if same else ()))
         return Collected(rows[:, :, : self.n_obs], bufs["acts"], rows[1:, :, self.n_obs], rows[1:, :, self.n_obs + 1] > 0.5,
                          logp, values, adv, ret)
 

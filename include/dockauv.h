@@ -1027,6 +1027,94 @@ int dockauv_collect_normalized(dockauv_handle h, dockauv_policy actor, dockauv_p
                                const dockauv_truncation_io* tio, dockauv_rewnorm rn, const dockauv_rewnorm_io* nio,
                                void* hip_stream);
 
+/*
+ * The replay buffer: what the reference's train() needs between the env and the learner with MODEL = SAC (or DDPG; train.py
+ * with SAC_HYPER_PARAMS_*, config/DRL_hyperparams.py) -- SB3 1.5's ReplayBuffer.add / ReplayBuffer.sample -- as a ring of
+ * transitions (obs, action, reward, next_obs, done) in device memory, filled from the buffers a step, dockauv_rollout or
+ * dockauv_collect already writes, and sampled in minibatches whose indices the kernel derives from Philox.  Opt-in: without these
+ * calls every other call queues exactly what it queued before.  All pointers are device pointers; sync, push and sample are
+ * asynchronous on the stream and do not synchronise.
+ *
+ * A dockauv_replay belongs to one float32 handle with an auto-reset mode (with DOCKAUV_RESET_NONE an episode does not restart at
+ * the row after a done).  capacity_steps = max(buffer_size / n_envs, 1) step slots of n_envs records each (SB3's rule).  It owns
+ * the ring, zero-filled at create, and the observation carry, float32 [n_envs][n_obs]: the observation the next transition of
+ * every env starts from.  Everything is allocated at create, later calls allocate nothing.  Destroy it before its handle.  The
+ * calls on one buffer must be ordered on one stream (or by events).
+ *
+ * Layout (public: a checkpoint is a copy of the ring and the carry out and in, with the counts).  The record of (step slot s,
+ * env i) starts at float  (s * n_envs + i) * record_floats  of the ring -- a 64-bit product: the ring may exceed 4 GiB -- and is
+ *   [ obs n_obs | next_obs n_obs | action n_u | reward | done | timeout | zero padding ]
+ * with record_floats = 2 n_obs + n_u + 3 rounded up to a multiple of 4 (every record starts on a 16-byte boundary).  done and
+ * timeout are exactly 0.0f or 1.0f, the padding is written as 0.0f: the ring's bits are a function of what was pushed.
+ *
+ * dockauv_replay_sync: carry[i] <- rows[i][0 .. n_obs) of rows [n_envs][n_obs + 2]: the rows the next step is about to read,
+ *   after steps the buffer did not see.  One launch.
+ *
+ * dockauv_replay_push (one launch) stores the K = n_steps transitions of every env.  That of step k, env i:
+ *   obs       k = 0: rows_in[i][0 .. n_obs), or carry[i] when rows_in is NULL;  k > 0: rows_out[k - 1][i][0 .. n_obs)
+ *   action    actions[k][i]
+ *   reward    rows_out[k][i][n_obs]
+ *   done      rows_out[k][i][n_obs + 1] > 0.5f
+ *   next_obs  terminal_obs[k][i] where done, else rows_out[k][i][0 .. n_obs)
+ *   timeout   done and ep_outcome[k][i] == 3 (dockauv_monitor_scan's per-row outcome: a time limit and nothing else); 0
+ *             everywhere when ep_outcome is NULL
+ * terminal_obs and ep_outcome are read ONLY where done (elsewhere they hold whatever they held before).  Every value is a copy:
+ * no arithmetic touches it.  The transition goes to step slot (pos + k) mod capacity_steps; afterwards
+ *   carry <- rows_out[K - 1][.][0 .. n_obs);   pos <- (pos + K) mod capacity_steps;   size <- min(size + K, capacity_steps)
+ * so the ring after one push of K steps is bit for bit what K pushes of one step leave.  The carry is two buffers that
+ * alternate: a push reads one and writes the other, so no lane reads what another writes in the same launch;
+ * dockauv_replay_state hands out the current one, which changes with every push.
+ *
+ * dockauv_replay_sample (one launch) draws n_batches = G minibatches of batch_size = B transitions, uniformly over what is
+ * stored, with replacement, independently in step and env, as SB3 samples.  For (g, b):
+ *   (x0, x1, ..) = Philox4x32-10 of counter (b, lo32(draws + g), hi32(draws + g), 4), key = seed
+ *     (word 3 of the counter names the stream: 0 the episode generator, 1 the current noise, 2 the policy's normals, 3 the
+ *     minibatch permutation, 4 this one)
+ *   step = (x0 * size) >> 32;   env = (x1 * n_envs) >> 32;   index = step * n_envs + env
+ * The multiply-shift gives every value floor(2^32 / size) or one more of the 2^32 words: a relative bias of at most size / 2^32
+ * (n_envs / 2^32 for env).  obs, actions, next_obs and rewards are copies of the record's fields; dones = done * (1 - timeout),
+ * exactly 0.0f or 1.0f: SB3's handle_timeout_termination.  Afterwards draws <- draws + G.  No index buffer, no workspace.
+ *
+ * pos, size and draws are host-side members, read when a call is made and updated by it: a captured graph would replay one
+ * call's values.  dockauv_replay_counts reads them (each output nullable), dockauv_replay_set_counts writes them (a checkpoint's;
+ * 0 <= pos < capacity_steps, 0 <= size <= capacity_steps).
+ * dockauv_replay_state: device pointers to the ring and the current carry, capacity_steps and record_floats; each output nullable.
+ *
+ * Refused before any device call (DOCKAUV_E_INVALID, the message naming the field): a NULL handle, buffer, io or required
+ * pointer; a wrong struct_size; buffer_size < 1; capacity_steps >= 2^31; n_steps < 1 or > capacity_steps; batch_size < 1,
+ * n_batches < 1, or a product of 2^31 or more; a sample while size == 0; counts out of range; a float64 handle; a handle with
+ * DOCKAUV_RESET_NONE; a buffer of another handle.
+ */
+typedef struct dockauv_replay_s* dockauv_replay;
+typedef struct dockauv_replay_push_io {
+    uint32_t struct_size;          /* sizeof(dockauv_replay_push_io): ABI check */
+    int32_t n_steps;               /* K, 1 .. capacity_steps */
+    const float* rows_in;          /* nullable [n_envs][n_obs + 2]: what step 0 read; NULL: the carry */
+    const float* rows_out;         /* [K][n_envs][n_obs + 2] */
+    const float* actions;          /* [K][n_envs][n_u] */
+    const float* terminal_obs;     /* [K][n_envs][n_obs]: read where done */
+    const uint8_t* ep_outcome;     /* nullable [K][n_envs] (dockauv_monitor_io.ep_outcome): read where done */
+} dockauv_replay_push_io;
+typedef struct dockauv_replay_sample_io {
+    uint32_t struct_size;          /* sizeof(dockauv_replay_sample_io): ABI check */
+    int32_t n_batches;             /* G >= 1 */
+    long long batch_size;          /* B >= 1 */
+    float* obs;                    /* [G][B][n_obs] */
+    float* actions;                /* [G][B][n_u] */
+    float* next_obs;               /* [G][B][n_obs] */
+    float* rewards;                /* [G][B] */
+    float* dones;                  /* [G][B] */
+    long long* index;              /* nullable [G][B] */
+} dockauv_replay_sample_io;
+int dockauv_replay_create(dockauv_handle h, long long buffer_size, uint64_t seed, dockauv_replay* out);
+int dockauv_replay_destroy(dockauv_replay rb);   /* NULL: 0 */
+int dockauv_replay_sync(dockauv_handle h, dockauv_replay rb, const float* rows, void* hip_stream);
+int dockauv_replay_push(dockauv_handle h, dockauv_replay rb, const dockauv_replay_push_io* io, void* hip_stream);
+int dockauv_replay_sample(dockauv_handle h, dockauv_replay rb, const dockauv_replay_sample_io* io, void* hip_stream);
+int dockauv_replay_counts(dockauv_replay rb, long long* pos, long long* size, uint64_t* draws);
+int dockauv_replay_set_counts(dockauv_replay rb, long long pos, long long size, uint64_t draws);
+int dockauv_replay_state(dockauv_replay rb, float** storage, float** carry, long long* capacity_steps, int* record_floats);
+
 #ifdef __cplusplus
 }
 #endif
