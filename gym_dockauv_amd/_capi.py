@@ -218,6 +218,35 @@ class ReplaySampleIO(C.Structure):
     ]
 
 
+class SacActorDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("precision", C.c_int32),
+        ("n_in", C.c_int32), ("n_hidden", C.c_int32 * 2), ("n_out", C.c_int32),
+        ("hidden_act", C.c_int32), ("pointers_on_device", C.c_int32), ("reserved", C.c_int32 * 2),
+        ("W1", C.c_void_p), ("b1", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p),
+        ("W_mu", C.c_void_p), ("b_mu", C.c_void_p), ("W_ls", C.c_void_p), ("b_ls", C.c_void_p),
+        ("seed", C.c_uint64), ("env_id_offset", C.c_uint64),
+    ]
+
+
+class QIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("obs_stride", C.c_int32), ("act_stride", C.c_int32), ("reserved", C.c_int32),
+        ("obs", C.c_void_p), ("actions", C.c_void_p), ("row_index", C.c_void_p), ("n_rows", C.c_longlong), ("q", C.c_void_p),
+    ]
+
+
+class SacTargetIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("next_obs_stride", C.c_int32), ("column_stride", C.c_int32),
+        ("gamma", C.c_float), ("ent_coef", C.c_float), ("reserved", C.c_int32),
+        ("next_obs", C.c_void_p), ("row_index", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p),
+        ("timeouts", C.c_void_p), ("log_ent_coef", C.c_void_p),
+        ("n_rows", C.c_longlong), ("t", C.c_uint64), ("row_offset", C.c_uint64),
+        ("a2", C.c_void_p), ("logp2", C.c_void_p), ("q1", C.c_void_p), ("q2", C.c_void_p), ("y", C.c_void_p),
+    ]
+
+
 # every symbol include/dockauv.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("dockauv_abi_version", C.c_int, []),
@@ -302,6 +331,12 @@ SYMBOLS = [
                                          C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("dockauv_collect_normalized", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CollectIO), C.POINTER(TruncationIO),
                                              C.c_void_p, C.POINTER(RewnormIO), C.c_void_p]),
+    # (the SAC forward half; the replay entries stay the last ones, which tests/test_replay_host.py pins)
+    ("dockauv_sac_actor_create", C.c_int, [C.c_void_p, C.POINTER(SacActorDesc), C.POINTER(C.c_void_p)]),
+    ("dockauv_sac_actor_load", C.c_int, [C.c_void_p, C.POINTER(SacActorDesc), C.c_void_p]),
+    ("dockauv_q_create", C.c_int, [C.c_void_p, C.POINTER(PolicyDesc), C.POINTER(C.c_void_p)]),
+    ("dockauv_q_forward", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QIO), C.c_void_p]),
+    ("dockauv_sac_target", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SacTargetIO), C.c_void_p]),
     ("dockauv_replay_create", C.c_int, [C.c_void_p, C.c_longlong, C.c_uint64, C.POINTER(C.c_void_p)]),
     ("dockauv_replay_destroy", C.c_int, [C.c_void_p]),
     ("dockauv_replay_sync", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,6 +1,6 @@
 // dockauv_capi_policy.hip -- C ABI of libdockauv.so (include/dockauv.h), second part: MLP policy and critic, closed-loop
-// rollout, PPO collector, backward, head, optimiser, episode monitor and reward normaliser.  The kernels are in dockauv_policy /
-// _collect / _backward / _head / _optim / _monitor / _update / _rewnorm.hip.
+// rollout, PPO collector, backward, head, optimiser, episode monitor and reward normaliser, and (at the end) SAC's forward half.
+// The kernels are in dockauv_policy / _collect / _backward / _head / _optim / _monitor / _update / _rewnorm / _sac.hip.
 #include <cmath>
 #include <cstring>
 
@@ -16,6 +16,8 @@ struct dockauv_policy_s {
     float* log_std = nullptr;     // the raw log_std [DOCKAUV_MAX_U] (the packed image keeps exp(log_std)): read by the log-prob epilogue
     bool has_log_std = false;
     bool value_role = false;      // a critic (dockauv_value_create): n_out == 1, raw output
+    bool sac_role = false;        // a squashed-Gaussian actor (dockauv_sac_actor_create): both heads in the output tile, out_act TANH
+    bool q_role = false;          // a Q critic (dockauv_q_create): n_in == n_obs + n_u, n_out == 1, raw output
     uint64_t seed = 0, env_id_offset = 0;
     float* bwd_partial = nullptr; // dockauv_policy_backward's per-group partial sums, allocated by the first backward
     double* head_ws = nullptr;    // dockauv_ppo_head's moment and row-sum partials (kHeadWorkspaceBytes), allocated by the first head call
@@ -111,14 +113,14 @@ int upload_policy(dockauv_policy p, const dockauv_policy_desc* d, hipStream_t st
     } else {
         size_t off = 0;
         for (int i = 0; i < 7; ++i) {
-            dev[i] = (src[i] && cnt[i] && !(i == 6 && p->value_role)) ? p->raw + off : nullptr;
+            dev[i] = (src[i] && cnt[i] && !(i == 6 && (p->value_role || p->q_role))) ? p->raw + off : nullptr;
             if (dev[i]) HIP_TRY(h, hipMemcpyAsync(p->raw + off, src[i], cnt[i] * sizeof(float), hipMemcpyHostToDevice, stream));
             off += cnt[i];
         }
         HIP_TRY(h, hipStreamSynchronize(stream));   // the caller's host arrays are free on return
     }
     if (!S.n_h2) dev[2] = dev[3] = nullptr;
-    if (p->value_role) dev[6] = nullptr;   // (a critic has no exploration noise)
+    if (p->value_role || p->q_role) dev[6] = nullptr;   // (a critic has no exploration noise)
     if (dev[6]) HIP_TRY(h, hipMemcpyAsync(p->log_std, dev[6], cnt[6] * sizeof(float), hipMemcpyDeviceToDevice, stream));
     const PolicyRaw raw{dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6]};
     const int rc = launch_policy_pack(S, raw, p->packed, stream);
@@ -131,6 +133,15 @@ int upload_policy(dockauv_policy p, const dockauv_policy_desc* d, hipStream_t st
 
 int policy_forward(dockauv_handle h, dockauv_policy p, const float* rows, float* actions, uint64_t t, int stochastic, hipStream_t stream,
                    float* log_prob = nullptr) {
+    if (p->sac_role) {
+        // the per-env form of the squashed-Gaussian actor: the plain actor's rows, counter and noise stream
+        SacActorLaunch l{rows, nullptr, actions, log_prob, (long)h->cfg.n_envs, h->n_obs + 2, h->n_u_max, stochastic ? 1 : 0,
+                         t, p->env_id_offset, p->seed, 2u};
+        const int rc = launch_sac_actor(p->S, p->packed, l, stream);
+        if (rc != 0) return fail(h, DOCKAUV_E_HIP, "SAC actor kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        h->last_stream = stream;
+        return 0;
+    }
     const int rc = launch_policy_forward(p->S, p->packed, rows, actions, h->cfg.n_envs, h->n_obs + 2, h->n_u_max, t,
                                          (stochastic && p->has_log_std) ? 1 : 0, p->seed, p->env_id_offset, stream, log_prob,
                                          log_prob ? p->log_std : nullptr);
@@ -147,10 +158,16 @@ int value_forward(dockauv_handle h, dockauv_policy c, const float* rows, long lo
     return 0;
 }
 
-// what the actor argument of `fn` must be: of this handle, not a critic; with want_logp also a log_std and a raw output
-int check_actor(dockauv_handle h, dockauv_policy p, const char* fn, bool want_logp) {
+// what the actor argument of `fn` must be: of this handle, not a critic; with want_logp also a log_std and a raw output.
+// ppo (everything but forward / forward_logp / rollout): a squashed-Gaussian actor is refused by name
+int check_actor(dockauv_handle h, dockauv_policy p, const char* fn, bool want_logp, bool ppo = true) {
     if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "%s: the policy was created for another handle", fn);
     if (p->value_role) return fail(h, DOCKAUV_E_INVALID, "%s: the policy is a critic (dockauv_value_create), an actor is needed", fn);
+    if (p->q_role) return fail(h, DOCKAUV_E_INVALID, "%s: the policy is a Q critic (dockauv_q_create), an actor is needed", fn);
+    if (p->sac_role && ppo)
+        return fail(h, DOCKAUV_E_INVALID, "%s: the policy is a squashed-Gaussian actor (dockauv_sac_actor_create); this call is PPO's and "
+                    "takes a plain actor (dockauv_policy_create)", fn);
+    if (p->sac_role) return 0;   // (its log-probability carries the squashing correction)
     if (want_logp && !p->has_log_std) return fail(h, DOCKAUV_E_INVALID, "%s: log_prob needs a policy with a log_std", fn);
     if (want_logp && p->S.out_act == DOCKAUV_ACT_TANH)
         return fail(h, DOCKAUV_E_INVALID, "%s: log_prob of a policy with out_act DOCKAUV_ACT_TANH needs the squashing correction, "
@@ -158,8 +175,19 @@ int check_actor(dockauv_handle h, dockauv_policy p, const char* fn, bool want_lo
     return 0;
 }
 
+// the SAC roles by name, for the calls whose arithmetic is the plain MLP's or PPO's
+int refuse_sac_roles(dockauv_handle h, dockauv_policy p, const char* fn) {
+    if (p->sac_role)
+        return fail(h, DOCKAUV_E_INVALID, "%s: the policy is a squashed-Gaussian actor (dockauv_sac_actor_create), which this call does not take", fn);
+    if (p->q_role) return fail(h, DOCKAUV_E_INVALID, "%s: the policy is a Q critic (dockauv_q_create), which this call does not take", fn);
+    return 0;
+}
+
 int check_critic(dockauv_handle h, dockauv_policy c, const char* fn) {
     if (c->h != h) return fail(h, DOCKAUV_E_INVALID, "%s: the critic was created for another handle", fn);
+    if (c->q_role) return fail(h, DOCKAUV_E_INVALID, "%s: the critic argument is a Q critic (dockauv_q_create), a value critic is needed", fn);
+    if (c->sac_role)
+        return fail(h, DOCKAUV_E_INVALID, "%s: the critic argument is a squashed-Gaussian actor (dockauv_sac_actor_create), not a critic", fn);
     if (!c->value_role) return fail(h, DOCKAUV_E_INVALID, "%s: the critic argument is an actor (dockauv_policy_create), not a critic", fn);
     return 0;
 }
@@ -360,18 +388,21 @@ int queue_collect(dockauv_handle h, dockauv_policy actor, dockauv_policy critic,
 }
 
 // actor (dockauv_policy_create) or critic (dockauv_value_create): `fn` names the entry point in the messages
-int create_policy(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out, bool value_role, const char* fn) {
+int create_policy(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out, bool value_role, const char* fn, bool q_role = false) {
     if (!d || !out) return fail(h, DOCKAUV_E_INVALID, "%s: null argument", fn);
     *out = nullptr;
     int rc = validate_policy_desc(h, d, nullptr);
     if (rc) return rc;
-    if (value_role && d->n_out != 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_out: %d, a critic has one output", d->n_out);
-    if (value_role && d->out_act != DOCKAUV_ACT_NONE)
+    if ((value_role || q_role) && d->n_out != 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_out: %d, a critic has one output", d->n_out);
+    if ((value_role || q_role) && d->out_act != DOCKAUV_ACT_NONE)
         return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.out_act: %d, a critic's output is raw (DOCKAUV_ACT_NONE)", d->out_act);
     if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
     if (h->f64) return fail(h, DOCKAUV_E_INVALID, "%s: the policy kernel is float32; the handle's precision is DOCKAUV_F64", fn);
-    if (d->n_in != h->n_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_in: %d, the handle's n_obs is %d", d->n_in, h->n_obs);
-    if (!value_role && d->n_out != h->n_u_max)
+    if (q_role && d->n_in != h->n_obs + h->n_u_max)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_in: %d, a Q critic reads [obs | action]: the handle's n_obs + n_u is %d + %d", d->n_in,
+                    h->n_obs, h->n_u_max);
+    if (!q_role && d->n_in != h->n_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_in: %d, the handle's n_obs is %d", d->n_in, h->n_obs);
+    if (!value_role && !q_role && d->n_out != h->n_u_max)
         return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_desc.n_out: %d, the handle's n_u is %d", d->n_out, h->n_u_max);
     PolicyShape S{};
     S.n_in = d->n_in;
@@ -389,6 +420,7 @@ int create_policy(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy
     p->h = h;
     p->S = S;
     p->value_role = value_role;
+    p->q_role = q_role;
     const int n_last = S.n_h2 ? S.n_h2 : S.n_h1;
     const size_t raw_floats = (size_t)S.n_h1 * S.n_in + S.n_h1 + (size_t)S.n_h2 * S.n_h1 + S.n_h2 + (size_t)S.n_out * n_last + 2 * (size_t)S.n_out;
     hipError_t e = hipMalloc((void**)&p->packed, (size_t)S.total * sizeof(float));
@@ -538,6 +570,9 @@ int dockauv_value_create(dockauv_handle h, const dockauv_policy_desc* d, dockauv
 int dockauv_policy_load(dockauv_policy p, const dockauv_policy_desc* d, void* hip_stream) {
     if (!p) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_load: null policy");
     if (!d) return fail(p->h, DOCKAUV_E_INVALID, "dockauv_policy_load: null descriptor");
+    if (p->sac_role)
+        return fail(p->h, DOCKAUV_E_INVALID, "dockauv_policy_load: the policy is a squashed-Gaussian actor (dockauv_sac_actor_create): "
+                    "its weights come through dockauv_sac_actor_load");
     int rc = validate_policy_desc(p->h, d, &p->S);
     if (rc) return rc;
     HIP_TRY(p->h, hipSetDevice(p->h->device));
@@ -561,7 +596,7 @@ int dockauv_policy_forward(dockauv_handle h, dockauv_policy p, const float* rows
                            void* hip_stream) {
     if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_forward: null handle");
     if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward: null policy");
-    if (int rc = check_actor(h, p, "dockauv_policy_forward", false)) return rc;
+    if (int rc = check_actor(h, p, "dockauv_policy_forward", false, false)) return rc;
     if (!rows || !actions) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward: rows/actions must not be NULL");
     HIP_TRY(h, hipSetDevice(h->device));
     return policy_forward(h, p, rows, actions, t, stochastic, (hipStream_t)hip_stream);
@@ -572,7 +607,7 @@ int dockauv_policy_forward_logp(dockauv_handle h, dockauv_policy p, const float*
     if (!rows || !actions || !log_prob) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_logp: rows/actions/log_prob must not be NULL");
     if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_logp: null policy");
     if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_forward_logp: null handle");
-    if (int rc = check_actor(h, p, "dockauv_policy_forward_logp", true)) return rc;
+    if (int rc = check_actor(h, p, "dockauv_policy_forward_logp", true, false)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     return policy_forward(h, p, rows, actions, t, stochastic, (hipStream_t)hip_stream, log_prob);
 }
@@ -594,6 +629,7 @@ int dockauv_policy_forward_rows(dockauv_handle h, dockauv_policy p, const float*
     if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: null policy");
     if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: null handle");
     if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_forward_rows: the policy was created for another handle");
+    if (int rc = refuse_sac_roles(h, p, "dockauv_policy_forward_rows")) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const int rc = launch_policy_forward_rows(p->S, p->packed, rows, (const long long*)row_index, (long)n_rows, h->n_obs + 2, out,
                                               (hipStream_t)hip_stream);
@@ -613,6 +649,7 @@ int dockauv_policy_backward(dockauv_handle h, dockauv_policy p, const float* row
     if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: null policy");
     if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_backward: null handle");
     if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_backward: the policy was created for another handle");
+    if (int rc = refuse_sac_roles(h, p, "dockauv_policy_backward")) return rc;
     if (p->S.n_h2 > 0 && (!grads->dW2 || !grads->db2))
         return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_grads: dW2/db2 are NULL, the policy has two hidden layers");
     BackwardLayout L;
@@ -735,7 +772,7 @@ int dockauv_rollout(dockauv_handle h, dockauv_policy p, const float* rows_in, fl
                     float* terminal_obs, int n_steps, uint64_t t0, int stochastic, void* hip_stream) {
     if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_rollout: null handle");
     if (!p) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: null policy");
-    if (int rc = check_actor(h, p, "dockauv_rollout", false)) return rc;
+    if (int rc = check_actor(h, p, "dockauv_rollout", false, false)) return rc;
     if (n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: n_steps %d must be >= 1", n_steps);
     if (!rows_in || !rows_out || !actions_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_rollout: rows_in/rows_out/actions_out must not be NULL");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -754,6 +791,7 @@ int dockauv_optim_create(dockauv_handle h, dockauv_policy actor, dockauv_policy 
         return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_desc.struct_size: got %u, library has %zu", d->struct_size, sizeof(dockauv_optim_desc));
     if (actor->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_create: the actor was created for another handle");
     if (actor->value_role) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_create: the actor argument is a critic (dockauv_value_create)");
+    if (int rc = refuse_sac_roles(h, actor, "dockauv_optim_create")) return rc;
     if (!actor->has_log_std) return fail(h, DOCKAUV_E_INVALID, "dockauv_optim_create: the actor has no log_std (its gradient is part of the index space)");
     if (critic)
         if (int rc = check_critic(h, critic, "dockauv_optim_create")) return rc;
@@ -1194,6 +1232,213 @@ int dockauv_collect_normalized(dockauv_handle h, dockauv_policy actor, dockauv_p
     if (int rc = check_actor(h, actor, fn, cio->log_prob != nullptr)) return rc;
     if (int rc = check_critic(h, critic, fn)) return rc;
     return queue_collect(h, actor, critic, cio, tio, rn, nio, (hipStream_t)hip_stream);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ SAC: the forward half (dockauv_sac.hip)
+namespace {
+
+constexpr int kSacHeadRows = 16;   // the [8 + n_u][n_last] array both heads are packed from, padded to the two register groups
+
+int validate_sac_desc(dockauv_handle h, const dockauv_sac_actor_desc* d, const PolicyShape* like) {
+    if (d->struct_size != sizeof(dockauv_sac_actor_desc))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.struct_size: got %u, library has %zu", d->struct_size, sizeof(dockauv_sac_actor_desc));
+    if (d->precision != DOCKAUV_F32) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.precision: %d, only DOCKAUV_F32 is implemented", d->precision);
+    if (d->n_in < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.n_in: %d must be >= 1", d->n_in);
+    if (d->n_hidden[0] < 1 || d->n_hidden[0] > DOCKAUV_POLICY_MAX_WIDTH)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.n_hidden[0]: %d outside 1..%d", d->n_hidden[0], DOCKAUV_POLICY_MAX_WIDTH);
+    if (d->n_hidden[1] < 0 || d->n_hidden[1] > DOCKAUV_POLICY_MAX_WIDTH)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.n_hidden[1]: %d outside 0..%d (0 = one hidden layer)", d->n_hidden[1], DOCKAUV_POLICY_MAX_WIDTH);
+    if (d->n_out < 1 || d->n_out > DOCKAUV_MAX_U) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.n_out: %d outside 1..%d", d->n_out, DOCKAUV_MAX_U);
+    if (d->hidden_act != DOCKAUV_ACT_TANH && d->hidden_act != DOCKAUV_ACT_RELU)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.hidden_act: %d is neither DOCKAUV_ACT_TANH nor DOCKAUV_ACT_RELU", d->hidden_act);
+    if (d->pointers_on_device != 0 && d->pointers_on_device != 1)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.pointers_on_device: %d must be 0 or 1", d->pointers_on_device);
+    if (!d->W1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.W1 is NULL");
+    if (!d->b1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.b1 is NULL");
+    if (d->n_hidden[1] > 0 && !d->W2) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.W2 is NULL (n_hidden[1] > 0)");
+    if (d->n_hidden[1] > 0 && !d->b2) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.b2 is NULL (n_hidden[1] > 0)");
+    if (!d->W_mu) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.W_mu is NULL");
+    if (!d->b_mu) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.b_mu is NULL");
+    if (!d->W_ls) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.W_ls is NULL");
+    if (!d->b_ls) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.b_ls is NULL");
+    if (like && (d->n_in != like->n_in || d->n_hidden[0] != like->n_h1 || d->n_hidden[1] != like->n_h2 || d->n_out != like->n_out ||
+                 d->hidden_act != like->hidden_act))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_load: n_in / n_hidden / n_out / hidden_act differ from the actor's (%d-%d-%d-%d)",
+                    like->n_in, like->n_h1, like->n_h2, like->n_out);
+    return 0;
+}
+
+// p->raw of a squashed-Gaussian actor: W1 b1 W2 b2, then the head array [16][n_last] and its bias [16] (rows 0 .. n_u - 1: mu,
+// rows 8 .. 8 + n_u - 1: log_std, the rest zero since create).  Both heads are always copied there, host or device arrays.
+int upload_sac_actor(dockauv_policy p, const dockauv_sac_actor_desc* d, hipStream_t stream) {
+    dockauv_handle h = p->h;
+    const PolicyShape& S = p->S;
+    const int n_last = S.n_h2 ? S.n_h2 : S.n_h1;
+    const hipMemcpyKind kind = d->pointers_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const float* src[4] = {d->W1, d->b1, d->W2, d->b2};
+    const size_t cnt[4] = {(size_t)S.n_h1 * S.n_in, (size_t)S.n_h1, (size_t)S.n_h2 * S.n_h1, (size_t)S.n_h2};
+    const float* dev[4];
+    size_t off = 0;
+    for (int i = 0; i < 4; ++i) {
+        dev[i] = cnt[i] ? (d->pointers_on_device ? src[i] : p->raw + off) : nullptr;
+        if (cnt[i] && !d->pointers_on_device) HIP_TRY(h, hipMemcpyAsync(p->raw + off, src[i], cnt[i] * sizeof(float), kind, stream));
+        off += cnt[i];
+    }
+    float* heads = p->raw + off;
+    float* head_b = heads + (size_t)kSacHeadRows * n_last;
+    HIP_TRY(h, hipMemcpyAsync(heads, d->W_mu, (size_t)S.n_out * n_last * sizeof(float), kind, stream));
+    HIP_TRY(h, hipMemcpyAsync(heads + (size_t)8 * n_last, d->W_ls, (size_t)S.n_out * n_last * sizeof(float), kind, stream));
+    HIP_TRY(h, hipMemcpyAsync(head_b, d->b_mu, (size_t)S.n_out * sizeof(float), kind, stream));
+    HIP_TRY(h, hipMemcpyAsync(head_b + 8, d->b_ls, (size_t)S.n_out * sizeof(float), kind, stream));
+    if (!d->pointers_on_device) HIP_TRY(h, hipStreamSynchronize(stream));   // the caller's host arrays are free on return
+    PolicyShape both = S;
+    both.n_out = 8 + S.n_out;              // (the layout does not depend on n_out: the pack kernel's bound on the output units)
+    const PolicyRaw raw{dev[0], dev[1], dev[2], dev[3], heads, head_b, nullptr};
+    const int rc = launch_policy_pack(both, raw, p->packed, stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "policy weight packing launch failed: %s", hipGetErrorString((hipError_t)rc));
+    p->has_log_std = true;
+    p->seed = d->seed;
+    p->env_id_offset = d->env_id_offset;
+    return 0;
+}
+
+int check_q(dockauv_handle h, dockauv_policy c, const char* fn, const char* arg) {
+    if (c->h != h) return fail(h, DOCKAUV_E_INVALID, "%s: %s was created for another handle", fn, arg);
+    if (!c->q_role) return fail(h, DOCKAUV_E_INVALID, "%s: %s is not a Q critic (dockauv_q_create)", fn, arg);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dockauv_sac_actor_create(dockauv_handle h, const dockauv_sac_actor_desc* d, dockauv_policy* out) {
+    const char* fn = "dockauv_sac_actor_create";
+    if (!d || !out) return fail(h, DOCKAUV_E_INVALID, "%s: null argument", fn);
+    *out = nullptr;
+    if (int rc = validate_sac_desc(h, d, nullptr)) return rc;
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
+    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "%s: the policy kernel is float32; the handle's precision is DOCKAUV_F64", fn);
+    if (d->n_in != h->n_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.n_in: %d, the handle's n_obs is %d", d->n_in, h->n_obs);
+    if (d->n_out != h->n_u_max) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc.n_out: %d, the handle's n_u is %d", d->n_out, h->n_u_max);
+    PolicyShape S{};
+    S.n_in = d->n_in;
+    S.n_h1 = d->n_hidden[0];
+    S.n_h2 = d->n_hidden[1];
+    S.n_out = d->n_out;
+    S.hidden_act = d->hidden_act;
+    S.out_act = DOCKAUV_ACT_TANH;
+    policy_layout(S);
+    if (policy_lds_bytes(S) > kPolMaxLds)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_desc: the padded weights (%zu B for n_in %d, n_hidden %d / %d) exceed "
+                    "the 160 KiB of LDS the policy kernel keeps them in: narrower layers", policy_lds_bytes(S), S.n_in, S.n_h1, S.n_h2);
+    HIP_TRY(h, hipSetDevice(h->device));
+    dockauv_policy p = new dockauv_policy_s();
+    p->h = h;
+    p->S = S;
+    p->sac_role = true;
+    const int n_last = S.n_h2 ? S.n_h2 : S.n_h1;
+    const size_t raw_floats = (size_t)S.n_h1 * S.n_in + S.n_h1 + (size_t)S.n_h2 * S.n_h1 + S.n_h2 + (size_t)kSacHeadRows * (n_last + 1);
+    hipError_t e = hipMalloc((void**)&p->packed, (size_t)S.total * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->raw, raw_floats * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(p->raw, 0, raw_floats * sizeof(float));
+    if (e != hipSuccess) {
+        dockauv_policy_destroy(p);
+        return fail(h, DOCKAUV_E_HIP, "policy buffers: %s", hipGetErrorString(e));
+    }
+    if (int rc = upload_sac_actor(p, d, nullptr)) {
+        dockauv_policy_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return 0;
+}
+
+int dockauv_sac_actor_load(dockauv_policy p, const dockauv_sac_actor_desc* d, void* hip_stream) {
+    if (!p) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_sac_actor_load: null policy");
+    if (!d) return fail(p->h, DOCKAUV_E_INVALID, "dockauv_sac_actor_load: null descriptor");
+    if (!p->sac_role) return fail(p->h, DOCKAUV_E_INVALID, "dockauv_sac_actor_load: the policy is not a squashed-Gaussian actor (dockauv_sac_actor_create)");
+    if (int rc = validate_sac_desc(p->h, d, &p->S)) return rc;
+    HIP_TRY(p->h, hipSetDevice(p->h->device));
+    return upload_sac_actor(p, d, (hipStream_t)hip_stream);
+}
+
+int dockauv_q_create(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out) {
+    return create_policy(h, d, out, false, "dockauv_q_create", true);
+}
+
+int dockauv_q_forward(dockauv_handle h, dockauv_policy critic, const dockauv_q_io* io, void* hip_stream) {
+    const char* fn = "dockauv_q_forward";
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "%s: io is NULL", fn);
+    if (io->struct_size != sizeof(dockauv_q_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_q_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_q_io));
+    if (io->n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_q_io.n_rows: %lld must be >= 1", io->n_rows);
+    if (!io->obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_q_io.obs is NULL");
+    if (!io->actions) return fail(h, DOCKAUV_E_INVALID, "dockauv_q_io.actions is NULL");
+    if (!io->q) return fail(h, DOCKAUV_E_INVALID, "dockauv_q_io.q is NULL");
+    if (!critic) return fail(h, DOCKAUV_E_INVALID, "%s: null critic", fn);
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
+    if (int rc = check_q(h, critic, fn, "the critic")) return rc;
+    if (io->obs_stride < h->n_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_q_io.obs_stride: %d is below the handle's n_obs %d", io->obs_stride, h->n_obs);
+    if (io->act_stride < h->n_u_max) return fail(h, DOCKAUV_E_INVALID, "dockauv_q_io.act_stride: %d is below the handle's n_u %d", io->act_stride, h->n_u_max);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const QLaunch l{io->obs, io->actions, (const long long*)io->row_index, (const long long*)io->row_index, io->q, (long)io->n_rows,
+                    io->obs_stride, io->act_stride, h->n_obs};
+    const int rc = launch_q_forward(critic->S, critic->packed, l, hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "Q kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
+    return 0;
+}
+
+int dockauv_sac_target(dockauv_handle h, dockauv_policy actor, dockauv_policy q1_target, dockauv_policy q2_target,
+                       const dockauv_sac_target_io* io, void* hip_stream) {
+    const char* fn = "dockauv_sac_target";
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "%s: io is NULL", fn);
+    if (io->struct_size != sizeof(dockauv_sac_target_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_target_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_sac_target_io));
+    if (io->n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_target_io.n_rows: %lld must be >= 1", io->n_rows);
+    if (!(io->gamma >= 0.0f && io->gamma <= 1.0f)) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_target_io.gamma: %g outside [0, 1]", (double)io->gamma);
+    if (!io->log_ent_coef && std::isnan(io->ent_coef)) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_target_io.ent_coef is NaN (and log_ent_coef is NULL)");
+    if (!io->next_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_target_io.next_obs is NULL");
+    if (!io->rewards) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_target_io.rewards is NULL");
+    if (!io->dones) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_target_io.dones is NULL");
+    if (!io->a2) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_target_io.a2 is NULL");
+    if (!io->logp2) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_target_io.logp2 is NULL");
+    if (!io->q1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_target_io.q1 is NULL");
+    if (!io->q2) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_target_io.q2 is NULL");
+    if (!io->y) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_target_io.y is NULL");
+    if (io->column_stride < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_target_io.column_stride: %d must be >= 1", io->column_stride);
+    if (!actor) return fail(h, DOCKAUV_E_INVALID, "%s: null actor", fn);
+    if (!q1_target || !q2_target) return fail(h, DOCKAUV_E_INVALID, "%s: null critic", fn);
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
+    if (actor->h != h) return fail(h, DOCKAUV_E_INVALID, "%s: the actor was created for another handle", fn);
+    if (!actor->sac_role) return fail(h, DOCKAUV_E_INVALID, "%s: the actor is not a squashed-Gaussian actor (dockauv_sac_actor_create)", fn);
+    if (int rc = check_q(h, q1_target, fn, "q1_target")) return rc;
+    if (int rc = check_q(h, q2_target, fn, "q2_target")) return rc;
+    if (io->next_obs_stride < h->n_obs)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_target_io.next_obs_stride: %d is below the handle's n_obs %d", io->next_obs_stride, h->n_obs);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const long n = (long)io->n_rows;
+    const long long* index = (const long long*)io->row_index;
+    const int n_u = h->n_u_max;
+    const SacActorLaunch al{io->next_obs, index, io->a2, io->logp2, n, io->next_obs_stride, n_u, 1, io->t, io->row_offset, actor->seed, 5u};
+    int rc = launch_sac_actor(actor->S, actor->packed, al, hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "SAC actor kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    float* q_out[2] = {io->q1, io->q2};
+    dockauv_policy qs[2] = {q1_target, q2_target};
+    for (int i = 0; i < 2; ++i) {
+        const QLaunch ql{io->next_obs, io->a2, index, nullptr, q_out[i], n, io->next_obs_stride, n_u, h->n_obs};
+        if ((rc = launch_q_forward(qs[i]->S, qs[i]->packed, ql, hip_stream)) != 0)
+            return fail(h, DOCKAUV_E_HIP, "Q kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    const SacTargetLaunch tl{io->rewards, io->dones, io->timeouts, index, io->logp2, io->q1, io->q2, io->log_ent_coef, io->y, n,
+                             io->column_stride, io->gamma, io->ent_coef};
+    if ((rc = launch_sac_target_rows(tl, hip_stream)) != 0)
+        return fail(h, DOCKAUV_E_HIP, "SAC target kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
+    return 0;
 }
 
 }  // extern "C"

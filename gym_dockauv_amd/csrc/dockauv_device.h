@@ -478,7 +478,8 @@ int launch_sequence_f32(const KernelArgs<float, 2>& a, const StepRequest& r, con
 #ifdef __HIPCC__
 // Philox4x32-10 (Salmon et al., SC'11): counter-based, integer only -> bit-exact against the NumPy restatement in
 // oracle/philox_ref.py.  Counter slot 3 names the stream: 0 = episode generator, 1 = current noise (dockauv_step.hip.inc),
-// 2 = policy exploration noise (dockauv_policy.hip), 3 = round keys of the minibatch permutation (dockauv_update.hip).
+// 2 = policy exploration noise (dockauv_policy.hip), 3 = round keys of the minibatch permutation (dockauv_update.hip),
+// 4 = replay minibatch indices (dockauv_replay.hip), 5 = the squashed-Gaussian actor's normals on rows (dockauv_sac.hip).
 __device__ __forceinline__ void philox4x32_10_(uint32_t c[4], uint32_t k0, uint32_t k1) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
@@ -550,6 +551,46 @@ int launch_policy_forward(const PolicyShape& s, const float* packed, const float
 // body of launch_policy_forward with a gathered row, so the same bits.  out: [n][n_out].  Returns a hipError_t as int.
 int launch_policy_forward_rows(const PolicyShape& s, const float* packed, const float* rows, const long long* row_index, long n,
                                int row_stride, float* out, void* stream);
+
+// ------------------------------------------------------------------------------------------ SAC forward half (dockauv_sac.hip)
+// The squashed-Gaussian actor keeps both heads in the output tile of the packed image: W_mu / b_mu in output units 0 .. n_u - 1,
+// W_ls / b_ls in units 8 .. 8 + n_u - 1 (packed by launch_policy_pack from a [8 + n_u][n_last] array with a shape whose n_out is
+// 8 + n_u; the shape the kernels get has n_out = n_u).  The std slot of the image is unused.  include/dockauv.h states the float32
+// expressions of the epilogue.
+struct SacActorLaunch {
+    const float* rows;                    // [..][row_stride], the first n_in columns are read
+    const long long* row_index;           // nullable [n]
+    float* actions;                       // [n][act_stride]
+    float* log_prob;                      // nullable [n]: the form with the log-probability epilogue
+    long n;
+    int row_stride, act_stride, stochastic;
+    unsigned long long t, row_offset, seed;   // the normal of (row, j): Philox counter (row_offset + i, t mod 2^32, j, slot)
+    unsigned int slot;                    // 2: the per-env calls (the plain actor's stream), 5: the rows form
+};
+int launch_sac_actor(const PolicyShape& s, const float* packed, const SacActorLaunch& l, void* stream);
+// q[i] = Q([obs row | action row]) of a critic with n_in = n_obs + n_u: layer-1 column k < n_obs from obs[oi * obs_stride + k],
+// k >= n_obs from actions[ai * act_stride + k - n_obs], oi / ai = the index's entry or i.  Returns a hipError_t as int.
+struct QLaunch {
+    const float *obs, *actions;
+    const long long *obs_index, *act_index;   // nullable [n] each
+    float* q;                             // [n]
+    long n;
+    int obs_stride, act_stride, n_obs;
+};
+int launch_q_forward(const PolicyShape& s, const float* packed, const QLaunch& l, void* stream);
+// y[i] = fmaf(gamma * (1 - d), fmaf(-alpha, logp2[i], fminf(q1[i], q2[i])), r) with r / d / timeout read at
+// (row_index ? row_index[i] : i) * column_stride; d <- d * (1 - timeout) when timeouts is given; alpha = log_ent_coef ?
+// expf(*log_ent_coef) : ent_coef.  One launch.
+struct SacTargetLaunch {
+    const float *rewards, *dones, *timeouts;
+    const long long* row_index;
+    const float *logp2, *q1, *q2, *log_ent_coef;
+    float* y;
+    long n;
+    int column_stride;
+    float gamma, ent_coef;
+};
+int launch_sac_target_rows(const SacTargetLaunch& l, void* stream);
 
 // ------------------------------------------------------------------------------------------ MLP backward (dockauv_backward.hip)
 // Parameter gradients of the MLP for upstream gradients on its raw output (include/dockauv.h: dockauv_policy_backward).  A

@@ -29,11 +29,10 @@
 
 #include "../../include/dockauv.h"
 #include "dockauv_device.h"
+#include "dockauv_policy_tile.h"
 
 namespace dockauv {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct PolicyArgs {
     PolicyShape S;
@@ -49,69 +48,6 @@ struct PolicyArgs {
     unsigned int env_off_lo;           // env_id_offset mod 2^32 (the counter word is 32 bits wide)
     unsigned long long seed;
 };
-
-// tanh(x) = 1 - 2 / (exp(2 x) + 1): v_exp_f32 and v_rcp_f32 are good to 1 ulp, the form has no cancellation beyond the final
-// subtraction, so the absolute error stays below ~3e-7 everywhere (+-1 at the ends, exactly 0 at 0: padded units stay 0).
-__device__ __forceinline__ float tanh_(float x) {
-    const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);   // exp(2 x)
-    return fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
-}
-
-__device__ __forceinline__ float act_(float x, int kind) {
-    if (kind == DOCKAUV_ACT_TANH) return tanh_(x);
-    if (kind == DOCKAUV_ACT_RELU) return fmaxf(x, 0.0f);
-    return x;
-}
-
-// standard normal of Philox counter (env, t, j, 2): Box-Muller cos branch on the first two words, u1 / u2 as the current
-// noise of the step kernel draws them (oracle/philox_ref.py: philox_normal).  u1 is formed in float32: the + 0.5 is held while
-// c[0] >> 8 < 2^23 and rounded to even above, so u1 lies in (0, 1] -- the log is finite, and the top value gives z = 0.
-__device__ __forceinline__ float policy_normal_(unsigned long long seed, uint32_t env, uint32_t t, uint32_t j) {
-    uint32_t c[4] = {env, t, j, 2u};
-    philox4x32_10_(c, (uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32));
-    const float u1 = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = (float)(c[1] >> 8) * (1.0f / 16777216.0f);
-    return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);                   // cos(2 pi u2), argument reduction exact
-}
-
-template <int MT>
-__device__ __forceinline__ void load_bias_(f32x16 (&acc)[MT], const float* lds_b, int half) {
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[m][r] = lds_b[(m * 16 + r) * 2 + half];
-}
-
-template <int MT>
-__device__ __forceinline__ void activate_(f32x16 (&acc)[MT], int kind) {
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[m][r] = act_(acc[m][r], kind);
-}
-
-// out[mo] += W[.. , k] h[k] over the units the accumulators `in` hold: k step (mi, r) takes register r of tile mi as it stands
-template <int MI, int MO>
-__device__ __forceinline__ void dense_(f32x16 (&out)[MO], const f32x16 (&in)[MI], const float* lds_w, int lane) {
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-#pragma unroll
-            for (int mo = 0; mo < MO; ++mo)
-                out[mo] = __builtin_amdgcn_mfma_f32_32x32x2f32(lds_w[((mi * 16 + r) * MO + mo) * 64 + lane], in[mi][r], out[mo], 0, 0, 0);
-}
-
-constexpr float kHalfLog2Pi = 0.91893853320467274f;   // log(2 pi) / 2
-constexpr int kChunk = 16;   // layer-1 k steps whose row words are requested together
-
-// the packed weights -> LDS, all threads of the group; the barrier behind it is the kernel's only one
-__device__ __forceinline__ void stage_weights_(const PolicyArgs& a, float* lds) {
-    const float4* src = reinterpret_cast<const float4*>(a.packed);
-    float4* dst = reinterpret_cast<float4*>(lds);
-    for (int i = threadIdx.x; i < a.S.total / 4; i += kPolThreads) dst[i] = src[i];
-    __syncthreads();
-}
 
 // one tile of 32 envs through all layers, by one wave (tile * 32 < a.n); LOGP: also a.log_prob; ROWS: the row of slot i is
 // a.row_index[i] when an index is given (dockauv_policy_forward_rows) -- the arithmetic is the same instruction sequence
@@ -192,7 +128,7 @@ __device__ __forceinline__ void policy_tile_(const PolicyArgs& a, const float* l
 template <int MT1, int MT2>
 __global__ __launch_bounds__(kPolThreads) void policy_mlp_kernel(const PolicyArgs a) {
     extern __shared__ float lds[];
-    stage_weights_(a, lds);
+    stage_weights_(a.packed, a.S.total, lds);
     const long tile = (long)blockIdx.x * (kPolThreads / 64) + (threadIdx.x >> 6);
     if (tile * 32 >= a.n) return;                       // (no barrier below)
     policy_tile_<MT1, MT2, false>(a, lds, tile);
@@ -203,7 +139,7 @@ __global__ __launch_bounds__(kPolThreads) void policy_mlp_kernel(const PolicyArg
 template <int MT1, int MT2>
 __global__ __launch_bounds__(kPolThreads) void policy_logp_kernel(const PolicyArgs a) {
     extern __shared__ float lds[];
-    stage_weights_(a, lds);
+    stage_weights_(a.packed, a.S.total, lds);
     const long tile = (long)blockIdx.x * (kPolThreads / 64) + (threadIdx.x >> 6);
     if (tile * 32 >= a.n) return;                       // (no barrier below)
     policy_tile_<MT1, MT2, true>(a, lds, tile);
@@ -213,7 +149,7 @@ __global__ __launch_bounds__(kPolThreads) void policy_logp_kernel(const PolicyAr
 template <int MT1, int MT2>
 __global__ __launch_bounds__(kPolThreads) void policy_rows_kernel(const PolicyArgs a) {
     extern __shared__ float lds[];
-    stage_weights_(a, lds);
+    stage_weights_(a.packed, a.S.total, lds);
     const long tile = (long)blockIdx.x * (kPolThreads / 64) + (threadIdx.x >> 6);
     if (tile * 32 >= a.n) return;                       // (no barrier below)
     policy_tile_<MT1, MT2, false, true>(a, lds, tile);
@@ -224,9 +160,6 @@ struct PackArgs {
     PolicyRaw raw;
     float* packed;
 };
-
-// unit of accumulator register r in lane half `half` of a tile (C/D layout of v_mfma_f32_32x32x2_f32)
-__device__ __forceinline__ int unit_of_(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 __global__ void policy_pack_kernel(const PackArgs a) {
     const PolicyShape& S = a.S;

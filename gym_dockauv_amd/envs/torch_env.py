@@ -115,11 +115,138 @@ class TorchDocking3d:
         """The on-device critic of an ``MLPPolicy`` with one raw output (``MLPPolicy.value_from_torch``) for ``collect``."""
         return self.batch.make_value(mlp)
 
+    # ------------------------------------------------------------------------------------------ SAC: the forward half
+    def make_sac_actor(self, mlp_or_module, seed: int = 0):
+        """The on-device squashed-Gaussian actor (SAC's) of a ``SquashedGaussianMLP`` or of an SB3-style actor module
+        (``latent_pi``, ``mu``, ``log_std``; read through the host once): ``rollout`` / ``rb.rollout`` / ``evaluate`` take it as
+        they take a plain actor, ``sac_target`` samples it on minibatch rows.  Widths up to 128 (net_arch=[128, 128] or narrower)."""
+        from ..policy import SquashedGaussianMLP
+        mlp = mlp_or_module if isinstance(mlp_or_module, SquashedGaussianMLP) else SquashedGaussianMLP.from_torch(mlp_or_module)
+        return self.batch.make_sac_actor(mlp, seed=seed)
+
+    def make_q(self, mlp_or_module):
+        """An on-device Q critic on [obs | action]: an ``MLPPolicy`` with n_in = n_obs + n_u and one raw output, or an
+        ``nn.Sequential`` ending in ``Linear(.., 1)`` (SB3's ``ContinuousCritic.q_networks[i]``)."""
+        from ..policy import MLPPolicy
+        mlp = mlp_or_module if isinstance(mlp_or_module, MLPPolicy) else MLPPolicy.value_from_torch(mlp_or_module)
+        return self.batch.make_q(mlp)
+
+    def _rows_view(self, t, width: int, what: str):
+        """(pointer, row stride) of a float32 [n, width] view on this device whose rows are a fixed number of floats apart"""
+        torch = self.torch
+        if t.device != self.device or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != width or t.stride(1) != 1 \
+                or t.stride(0) < width:
+            raise ValueError(f"{what} must be a float32 [n, {width}] tensor (or strided view) on {self.device}")
+        return t.data_ptr(), int(t.stride(0))
+
+    def _index_ok(self, index) -> int:
+        torch = self.torch
+        if index.device != self.device or index.dtype != torch.int64 or not index.is_contiguous() or index.numel() < 1:
+            raise ValueError(f"index must be a contiguous int64 tensor on {self.device}")
+        return int(index.numel())
+
+    def q_values(self, critic, obs, actions, index=None):
+        """[B] float32 (a fresh tensor): Q(obs[r], actions[r]) of a ``make_q`` critic on the current stream (dockauv_q_forward),
+        r = index[i] (``index`` int64 [B]) or i.  ``obs`` [n, n_obs] and ``actions`` [n, n_u] may be strided views, so the replay
+        ring serves as it stands: with R = rb.storage.view(-1, rb.record_floats), ``q_values(q, R[:, :n_obs], R[:, 2 * n_obs:
+        2 * n_obs + n_u], rb.index)`` (next_obs: R[:, n_obs:2 * n_obs])."""
+        torch = self.torch
+        optr, ostride = self._rows_view(obs, self.n_obs, "obs")
+        aptr, astride = self._rows_view(actions, self.n_u, "actions")
+        if index is None and obs.shape[0] != actions.shape[0]:
+            raise ValueError("obs and actions need the same number of rows")
+        B = obs.shape[0] if index is None else self._index_ok(index)
+        q = torch.empty((B,), device=self.device, dtype=torch.float32)
+        self.batch.q_forward_device(critic, optr, aptr, B, q.data_ptr(), obs_stride=ostride, act_stride=astride,
+                                    index_ptr=0 if index is None else index.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+        return q
+
+    def sac_target(self, actor, q1_target, q2_target, samples_or_buffer, gamma: float, ent_coef=None, log_ent_coef=None, t=None):
+        """SB3's ``SAC.train`` target block in ONE host call (dockauv_sac_target: four launches on the current stream, no
+        synchronisation): a2, logp2 = actor.sample(next_obs); y = r + gamma (1 - d) (min(Q1', Q2')(next_obs, a2) - alpha logp2).
+        ``samples_or_buffer``: the ``ReplaySamples`` of ``rb.sample(...)``, or the ``DeviceReplayBuffer`` itself after
+        ``rb.sample(..., want_index=True)`` -- then next_obs, reward, done and timeout are read from the ring through ``rb.index``
+        and the sampled copies are not touched: the same bits.  alpha: ``ent_coef`` (a float) or ``log_ent_coef`` (a float32 device
+        tensor of one element, read when the kernel runs: no read-back of a learned coefficient).  ``t``: the counter of the
+        normals (default: one per call).  Returns y shaped as the sample's rewards, a view of buffers the env owns and reuses for
+        the same number of rows; ``self.sac_buffers``: dict(a2 [n, n_u], logp2, q1, q2, y [n]) of this call."""
+        torch = self.torch
+        if (ent_coef is None) == (log_ent_coef is None):
+            raise ValueError("give either ent_coef or log_ent_coef")
+        if log_ent_coef is not None and (log_ent_coef.device != self.device or log_ent_coef.dtype != torch.float32 or log_ent_coef.numel() != 1):
+            raise ValueError(f"log_ent_coef must be a float32 tensor of one element on {self.device}")
+        kw = dict(ent_coef=0.0 if ent_coef is None else float(ent_coef), log_ent_coef_ptr=0 if log_ent_coef is None else log_ent_coef.data_ptr())
+        if hasattr(samples_or_buffer, "storage"):
+            rb = samples_or_buffer
+            if rb.env is not self or rb.index is None:
+                raise ValueError("the buffer must be this env's, after rb.sample(..., want_index=True)")
+            shape, n = tuple(rb.index.shape) + (1,), self._index_ok(rb.index)
+            base, R, o3 = rb.storage.data_ptr(), rb.record_floats, 2 * self.n_obs + self.n_u
+            kw.update(next_obs_ptr=base + 4 * self.n_obs, rewards_ptr=base + 4 * o3, dones_ptr=base + 4 * (o3 + 1),
+                      timeouts_ptr=(base + 4 * (o3 + 2)) if rb.monitor is not None else 0, next_obs_stride=R, column_stride=R,
+                      index_ptr=rb.index.data_ptr())
+        else:
+            sm = samples_or_buffer
+            nxt, rew, done = sm.next_observations, sm.rewards, sm.dones
+            for x in (nxt, rew, done):
+                if x.device != self.device or x.dtype != torch.float32 or not x.is_contiguous():
+                    raise ValueError(f"the samples must be contiguous float32 tensors on {self.device}")
+            shape, n = tuple(rew.shape), int(rew.numel())
+            if nxt.numel() != n * self.n_obs or done.numel() != n:
+                raise ValueError("next_observations [.., n_obs], rewards and dones [.., 1] of one minibatch shape")
+            kw.update(next_obs_ptr=nxt.data_ptr(), rewards_ptr=rew.data_ptr(), dones_ptr=done.data_ptr())
+        bufs = getattr(self, "_sac_bufs", None)
+        if bufs is None:
+            bufs = self._sac_bufs = {}
+            self._sac_t = 0
+        b = bufs.get(n)
+        if b is None:
+            z = lambda *sh: torch.zeros(sh, device=self.device, dtype=torch.float32)
+            b = bufs[n] = dict(a2=z(n, self.n_u), logp2=z(n), q1=z(n), q2=z(n), y=z(n))
+        if t is None:
+            t, self._sac_t = self._sac_t, self._sac_t + 1
+        self.batch.sac_target_device(actor, q1_target, q2_target, n_rows=n, gamma=gamma, a2_ptr=b["a2"].data_ptr(),
+                                     logp2_ptr=b["logp2"].data_ptr(), q1_ptr=b["q1"].data_ptr(), q2_ptr=b["q2"].data_ptr(),
+                                     y_ptr=b["y"].data_ptr(), t=int(t), stream=torch.cuda.current_stream().cuda_stream, **kw)
+        self.sac_buffers = b
+        return b["y"].view(shape)
+
+    def _load_sac_actor(self, policy, module_or_tensors) -> None:
+        torch = self.torch
+        m = module_or_tensors
+        if isinstance(m, torch.nn.Module):
+            ts = [t for sub in m.latent_pi if isinstance(sub, torch.nn.Linear) for t in (sub.weight, sub.bias)]
+            ts += [m.mu.weight, m.mu.bias, m.log_std.weight, m.log_std.bias]
+        else:
+            ts = list(m)
+        ts = [t.detach() for t in ts]
+        if len(ts) == 6:
+            ts[2:2] = [None, None]
+        if len(ts) != 8:
+            raise ValueError("expected (W1, b1[, W2, b2], W_mu, b_mu, W_ls, b_ls)")
+        widths = [policy.n_in] + policy.n_hidden
+        want = [s for i in range(len(widths) - 1) for s in ((widths[i + 1], widths[i]), (widths[i + 1],))]
+        if len(policy.n_hidden) == 1:
+            want += [None, None]
+        want += [(policy.n_out, widths[-1]), (policy.n_out,)] * 2
+        for t, w in zip(ts, want):
+            if (t is None) != (w is None) or (t is not None and (t.device != self.device or t.dtype != torch.float32
+                                                                 or not t.is_contiguous() or tuple(t.shape) != w)):
+                raise ValueError(f"actor tensors must be contiguous float32 on {self.device} with shapes {want}")
+        self.batch.load_policy(policy, device_ptrs=[0 if t is None else t.data_ptr() for t in ts],
+                               stream=torch.cuda.current_stream().cuda_stream)
+
     def load_policy(self, policy, module_or_tensors, log_std=None) -> None:
         """New weights (an actor's or a critic's) from DEVICE tensors, without a host copy and ordered on the current stream: an ``nn.Sequential`` whose
         Linear layers live on this device, or a sequence (W1, b1[, W2, b2], W3, b3) of contiguous float32 tensors;
-        ``log_std``: device tensor [n_u] or None.  The tensors are read when the copy runs on the stream."""
+        ``log_std``: device tensor [n_u] or None.  The tensors are read when the copy runs on the stream.
+        A Q critic (``make_q``) loads as a critic does -- a target network after its Polyak step.  A squashed-Gaussian actor
+        (``make_sac_actor``) takes an SB3-style actor module on this device or (W1, b1[, W2, b2], W_mu, b_mu, W_ls, b_ls)."""
         torch = self.torch
+        if getattr(policy, "role", None) == "sac":
+            if log_std is not None:
+                raise ValueError("a squashed-Gaussian actor has a log_std head, not a log_std vector")
+            return self._load_sac_actor(policy, module_or_tensors)
         if isinstance(module_or_tensors, torch.nn.Module):
             # a Linear without a bias loads zeros, as MLPPolicy.from_torch does (the allocator keeps the temporary's memory
             # ordered on the current stream, which is the stream the copy runs on)
@@ -333,7 +460,7 @@ class TorchDocking3d:
         rows[0].copy_(cur)
         has_v = value is not None
         values, adv, ret = (bufs["values"], bufs["adv"], bufs["ret"]) if has_v else (None, None, None)
-        logp = bufs["logp"] if (policy.has_log_std and policy.shape.out_act == _capi.ACT_NONE) else None
+        logp = bufs["logp"] if (policy.has_log_std and getattr(policy.shape, "out_act", None) == _capi.ACT_NONE) else None
         ptr = lambda t: 0 if t is None else t.data_ptr()
         common = dict(rows_in_ptr=rows[0].data_ptr(), rows_out_ptr=rows[1].data_ptr(), actions_out_ptr=bufs["acts"].data_ptr(), n_steps=K,
                       gamma=gamma, gae_lambda=gae_lambda, t0=self._t, stochastic=stochastic,

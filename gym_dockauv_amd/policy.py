@@ -6,6 +6,8 @@ is SB3's ``MlpPolicy``, which train.py:64 instantiates and train.py:64-71 / 86-1
 ``MLPPolicy`` is a plain host object that holds the arrays; ``BatchedDocking3d.make_policy`` / ``TorchDocking3d.make_policy``
 put it on the device.  An ``MLPPolicy`` with one raw output is a critic (SB3's ``mlp_extractor.value_net`` + ``value_net``;
 ``value_from_torch``, ``make_value``): the PPO collector (dockauv_collect) evaluates it on the rollout's rows.
+``SquashedGaussianMLP`` is SAC's actor (two heads, a state-dependent log_std, tanh squashing; ``make_sac_actor``), an ``MLPPolicy``
+on [obs | action] with one raw output a Q critic (``make_q``); ``sac_target_reference`` states the TD target's last kernel.
 ``forward_reference``, ``backward_reference``, ``normals_reference``, ``log_prob_reference``, ``gae_reference``,
 ``ppo_head_reference``, ``adam_reference`` and ``permutation_reference`` (exact integers) are float64
 NumPy statements of what the kernels compute (for tests and for callers who want to check a port); they are never used as a compute path.
@@ -294,9 +296,10 @@ class MLPPolicy:
         return tuple(grads)
 
     @staticmethod
-    def normals_reference(seed: int, env_ids, t: int, n_out: int) -> np.ndarray:
+    def normals_reference(seed: int, env_ids, t: int, n_out: int, slot: int = 2) -> np.ndarray:
         """The standard normals the kernel draws for step counter ``t``: Philox4x32-10 counter (env id mod 2^32, t mod 2^32,
-        j, 2), key = seed; Box-Muller cos branch on the first two words with u1 = ((x0 >> 8) + 0.5) 2^-24, u2 = (x1 >> 8) 2^-24.
+        j, slot), key = seed (``slot`` 2: the per-env actors; ``SAC_ROWS_STREAM`` = 5: the rows form of the squashed-Gaussian
+        actor, where ``env_ids`` are row_offset + the position in the batch); Box-Muller cos branch on the first two words with u1 = ((x0 >> 8) + 0.5) 2^-24, u2 = (x1 >> 8) 2^-24.
         ``env_ids`` already include the policy's env_id_offset.  Returns float64 [len(env_ids), n_out].
 
         This is the exact statement.  The kernel forms u1 in float32 (as the step kernel's current noise does), which holds
@@ -308,7 +311,7 @@ class MLPPolicy:
         ctr[..., 0] = env[:, None]
         ctr[..., 1] = np.uint64(int(t) & 0xFFFFFFFF)
         ctr[..., 2] = np.arange(n_out, dtype=np.uint64)[None, :]
-        ctr[..., 3] = np.uint64(2)
+        ctr[..., 3] = np.uint64(int(slot))
         x = _philox4x32_10(ctr, (int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF))
         u1 = ((x[..., 0] >> np.uint64(8)).astype(np.float64) + 0.5) / 16777216.0
         u2 = (x[..., 1] >> np.uint64(8)).astype(np.float64) / 16777216.0
@@ -375,15 +378,178 @@ class MLPPolicy:
         return d
 
 
-class DevicePolicy:
-    """A dockauv_policy of one BatchedDocking3d handle (made by ``make_policy``): the handle plus what a reload needs."""
+SAC_ROWS_STREAM = 5        # word 3 of the Philox counter of the squashed-Gaussian actor's normals on rows (dockauv_sac_target)
+_F32 = np.float32
 
-    def __init__(self, ptr: C.c_void_p, mlp: MLPPolicy, seed: int, env_id_offset: int, value_role: bool = False):
+
+def _fmaf(a, b, c) -> np.ndarray:
+    """fmaf on float32 arrays, one rounding: the product of two float32 is exact in float64; its sum with c is rounded to
+    float64 and then to float32, and where that first rounding lands on a float32 tie it is undone by the sum's exact error
+    (round to odd), so the result is the correctly rounded a * b + c."""
+    a, b, c = (np.asarray(x, dtype=np.float32).astype(np.float64) for x in (a, b, c))
+    a, b, c = np.broadcast_arrays(a, b, c)
+    p = a * b
+    s = p + c
+    bb = s - p
+    err = (p - (s - bb)) + (c - bb)
+    tie = (np.ascontiguousarray(s).view(np.int64) & np.int64(0x1FFFFFFF)) == np.int64(0x10000000)
+    adj = tie & (err != 0.0) & np.isfinite(s)
+    s = np.where(adj, np.nextafter(s, np.where(err > 0.0, np.inf, -np.inf)), s)
+    return s.astype(np.float32)
+
+
+def sac_target_reference(q1, q2, logp2, rewards, dones, gamma: float, ent_coef=None, log_ent_coef=None) -> np.ndarray:
+    """The exact float32 statement of the last kernel of dockauv_sac_target on arrays of one shape:
+    v = fmaf(-alpha, logp2, fminf(q1, q2)); y = fmaf(gamma * (1.0f - d), v, r), with alpha = ``ent_coef`` or, given
+    ``log_ent_coef``, float32(exp(log_ent_coef)) (the device takes expf of its own: equal up to that function's last bit).
+    ``dones`` are rb.sample's: done * (1 - timeout)."""
+    if (ent_coef is None) == (log_ent_coef is None):
+        raise ValueError("give either ent_coef or log_ent_coef")
+    alpha = _F32(ent_coef) if log_ent_coef is None else _F32(np.exp(np.float64(_F32(log_ent_coef))))
+    f = lambda x: np.asarray(x, dtype=np.float32)
+    q1, q2, lp, r, d = f(q1), f(q2), f(logp2), f(rewards), f(dones)
+    v = _fmaf(-alpha, lp, np.minimum(q1, q2))
+    return _fmaf(_F32(gamma) * (_F32(1.0) - d), v, r)
+
+
+class SquashedGaussianMLP:
+    """SB3 1.5's ``sac.policies.Actor`` with ``use_sde=False``: latent = MLP(obs) over ``layers`` (one or two hidden (W, b)
+    pairs, torch.nn.Linear layout), mu = W_mu latent + b_mu, log_std = clamp(W_ls latent + b_ls, -20, 2) with ``mu`` = (W_mu,
+    b_mu) and ``log_std_head`` = (W_ls, b_ls); x = mu + exp(log_std) z, a = tanh(x).  A host object holding the arrays;
+    ``make_sac_actor`` puts it on the device.  Widths up to 128: SB3's default net_arch [256, 256] does not fit the kernel."""
+
+    LOG_STD_MIN, LOG_STD_MAX, EPS = -20.0, 2.0, 1e-6
+
+    def __init__(self, layers, mu, log_std_head, hidden_act: str = "relu"):
+        if len(layers) not in (1, 2):
+            raise ValueError("SquashedGaussianMLP takes one or two hidden layers")
+        if hidden_act not in ("tanh", "relu"):
+            raise ValueError("hidden_act must be 'tanh' or 'relu'")
+        c = lambda Wb: (np.ascontiguousarray(Wb[0], dtype=np.float32), np.ascontiguousarray(Wb[1], dtype=np.float32))
+        self.layers, self.mu, self.log_std_head = [c(Wb) for Wb in layers], c(mu), c(log_std_head)
+        n = self.layers[0][0].shape[1]
+        for W, b in self.layers:
+            if W.ndim != 2 or b.shape != (W.shape[0],) or W.shape[1] != n:
+                raise ValueError("layer shapes do not chain: W [out, in], b [out]")
+            n = W.shape[0]
+        for W, b in (self.mu, self.log_std_head):
+            if W.ndim != 2 or W.shape[1] != n or b.shape != (W.shape[0],) or W.shape[0] != self.mu[0].shape[0]:
+                raise ValueError("mu and log_std_head: W [n_out, n_last], b [n_out], the same n_out")
+        self.hidden_act = hidden_act
+
+    n_in = property(lambda self: int(self.layers[0][0].shape[1]))
+    n_out = property(lambda self: int(self.mu[0].shape[0]))
+    n_hidden = property(lambda self: [int(W.shape[0]) for W, _ in self.layers])
+
+    @classmethod
+    def from_torch(cls, module_or_state_dict, hidden_act: Optional[str] = None):
+        """An SB3-style actor: a module with ``latent_pi`` (Sequential of Linear / ReLU / Tanh), ``mu`` and ``log_std`` (Linear),
+        or its state dict (``latent_pi.{0,2}.*``, ``mu.*``, ``log_std.*``; the hidden activation is then ``hidden_act``, SB3's
+        SAC default: relu).  Needs no stable-baselines3 import."""
+        def arr(t):
+            return (t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)).astype(np.float32)
+
+        if isinstance(module_or_state_dict, dict) or hasattr(module_or_state_dict, "keys"):
+            sd = module_or_state_dict
+            layers = [(arr(sd[f"latent_pi.{i}.weight"]), arr(sd[f"latent_pi.{i}.bias"])) for i in (0, 2) if f"latent_pi.{i}.weight" in sd]
+            if not layers or "mu.weight" not in sd or "log_std.weight" not in sd:
+                raise ValueError("state dict needs latent_pi.0.*, mu.* and log_std.*")
+            return cls(layers, (arr(sd["mu.weight"]), arr(sd["mu.bias"])), (arr(sd["log_std.weight"]), arr(sd["log_std.bias"])),
+                       hidden_act or "relu")
+        m = module_or_state_dict
+        layers, acts = [], []
+        for sub in m.latent_pi:
+            name = type(sub).__name__
+            if name == "Linear":
+                layers.append((arr(sub.weight), arr(sub.bias)))
+            elif name in ("Tanh", "ReLU"):
+                acts.append(name.lower())
+            else:
+                raise ValueError(f"unsupported layer {name} in latent_pi: Linear, Tanh and ReLU are")
+        if len(acts) != len(layers) or len(set(acts)) != 1 or (hidden_act and hidden_act != acts[0]):
+            raise ValueError("latent_pi: expected Linear-act[-Linear-act] with one kind of activation")
+        return cls(layers, (arr(m.mu.weight), arr(m.mu.bias)), (arr(m.log_std.weight), arr(m.log_std.bias)), acts[0])
+
+    # ------------------------------------------------------------------------------------------ statements
+    def forward_reference(self, obs, z=None):
+        """float64, by SB3's formulas as they are written: returns (a, log_prob, mu, log_std) with a = tanh(mu + exp(log_std) z)
+        (``z`` None: the deterministic action, z = 0) and log_prob = sum_j Normal(mu_j, std_j).log_prob(x_j) -
+        sum_j log(1 - a_j^2 + 1e-6).  obs [..., n_in], z [..., n_out]."""
+        x = np.asarray(obs, dtype=np.float64)
+        for W, b in self.layers:
+            x = _act(x @ W.astype(np.float64).T + b.astype(np.float64), self.hidden_act)
+        mu = x @ self.mu[0].astype(np.float64).T + self.mu[1].astype(np.float64)
+        ls = np.clip(x @ self.log_std_head[0].astype(np.float64).T + self.log_std_head[1].astype(np.float64),
+                     self.LOG_STD_MIN, self.LOG_STD_MAX)
+        z = np.zeros_like(mu) if z is None else np.asarray(z, dtype=np.float64)
+        std = np.exp(ls)
+        pre = mu + std * z
+        a = np.tanh(pre)
+        gauss = -((pre - mu) ** 2) / (2.0 * std ** 2) - ls - 0.5 * np.log(2.0 * np.pi)
+        return a, gauss.sum(axis=-1) - np.log(1.0 - a * a + self.EPS).sum(axis=-1), mu, ls
+
+    def forward_float32(self, obs, z=None):
+        """The kernel's epilogue expressions in float32 NumPy arrays (include/dockauv.h states them; the matrix products are
+        NumPy's float32): (a, log_prob).  What float32 can do on these expressions -- the yardstick of the device's
+        log-probability error, never a compute path."""
+        f = _F32
+        x = np.asarray(obs, dtype=np.float32)
+        for W, b in self.layers:
+            x = _act(x @ W.T + b, self.hidden_act).astype(np.float32)
+        mu = (x @ self.mu[0].T + self.mu[1]).astype(np.float32)
+        ls = np.clip((x @ self.log_std_head[0].T + self.log_std_head[1]).astype(np.float32), f(self.LOG_STD_MIN), f(self.LOG_STD_MAX))
+        z = np.zeros_like(mu) if z is None else np.asarray(z, dtype=np.float32)
+        pre = _fmaf(np.exp(ls), z, mu)
+        a = np.tanh(pre)
+        gauss = _fmaf(f(-0.5) * z, z, -(ls + f(0.918938533)))
+        e = np.exp(f(-2.0) * np.abs(pre))
+        d = f(1.0) + e
+        corr = np.log(f(4.0) * e / (d * d) + f(1e-6))
+        lo = gauss[..., :4].sum(axis=-1, dtype=np.float32) - corr[..., :4].sum(axis=-1, dtype=np.float32)
+        hi = gauss[..., 4:].sum(axis=-1, dtype=np.float32) - corr[..., 4:].sum(axis=-1, dtype=np.float32)
+        return a, (lo + hi).astype(np.float32)
+
+    def plain_twin(self, out_act: str = "tanh", log_std=None) -> "MLPPolicy":
+        """The plain ``MLPPolicy`` with the same hidden layers and W3 = W_mu, b3 = b_mu: its deterministic actions are this
+        actor's bit for bit, and with W_ls = 0, b_ls = ``log_std`` so are the stochastic ones."""
+        return MLPPolicy(self.layers + [self.mu], self.hidden_act, out_act, log_std)
+
+    # ------------------------------------------------------------------------------------------ C ABI
+    def shape_desc(self) -> _capi.SacActorDesc:
+        d = _capi.SacActorDesc()
+        d.struct_size = C.sizeof(_capi.SacActorDesc)
+        d.precision = _capi.F32
+        d.n_in, d.n_out = self.n_in, self.n_out
+        d.n_hidden[0] = self.n_hidden[0]
+        d.n_hidden[1] = self.n_hidden[1] if len(self.n_hidden) == 2 else 0
+        d.hidden_act = _ACTS[self.hidden_act]
+        return d
+
+    def host_desc(self, seed: int = 0, env_id_offset: int = 0) -> _capi.SacActorDesc:
+        """dockauv_sac_actor_desc over this object's host arrays (which must outlive the call that reads it)"""
+        d = self.shape_desc()
+        d.pointers_on_device = 0
+        ptrs = [a.ctypes.data for Wb in self.layers for a in Wb]
+        if len(self.layers) == 1:
+            ptrs += [None, None]
+        d.W1, d.b1, d.W2, d.b2 = ptrs
+        d.W_mu, d.b_mu = self.mu[0].ctypes.data, self.mu[1].ctypes.data
+        d.W_ls, d.b_ls = self.log_std_head[0].ctypes.data, self.log_std_head[1].ctypes.data
+        d.seed, d.env_id_offset = int(seed), int(env_id_offset)
+        return d
+
+
+class DevicePolicy:
+    """A dockauv_policy of one BatchedDocking3d handle (made by ``make_policy``, ``make_value``, ``make_sac_actor`` or
+    ``make_q``): the handle plus what a reload needs.  ``role``: "actor", "value", "sac" or "q"."""
+
+    def __init__(self, ptr: C.c_void_p, mlp, seed: int, env_id_offset: int, value_role: bool = False, role: Optional[str] = None):
         self.ptr, self.seed, self.env_id_offset = ptr, int(seed), int(env_id_offset)
-        self.value_role = bool(value_role)       # a critic (make_value): dockauv_value_create
+        self.role = role or ("value" if value_role else "actor")
+        self.value_role = self.role == "value"   # a critic (make_value): dockauv_value_create
         self.shape = mlp.shape_desc()
         self.n_in, self.n_hidden, self.n_out = mlp.n_in, mlp.n_hidden, mlp.n_out
-        self.has_log_std = mlp.log_std is not None and not self.value_role
+        self.has_log_std = self.role == "sac" or (self.role == "actor" and mlp.log_std is not None)
 
 
 class DeviceOptim:

@@ -16,7 +16,8 @@ import numpy as np
 
 from .policy import _philox4x32_10
 
-REPLAY_STREAM = 4          # word 3 of the Philox counter (0 episode generator, 1 current noise, 2 policy normals, 3 permutation)
+REPLAY_STREAM = 4          # word 3 of the Philox counter (0 episode generator, 1 current noise, 2 policy normals, 3 permutation;
+                           # 5: the squashed-Gaussian actor's normals on rows, policy.SAC_ROWS_STREAM)
 OUTCOME_TIME_LIMIT = 3     # monitor.OUTCOMES.index("time_limit")
 
 # what DeviceReplayBuffer.sample returns: the fields of SB3's ReplayBufferSamples, in its order

@@ -424,7 +424,8 @@ int dockauv_value_forward(dockauv_handle h, dockauv_policy critic, const float* 
  * In float32: term_j = fmaf(-0.5f * z, z, -(log_std[j] + 0.918938533f)); (term_0 + .. + term_3) + (term_4 + .. + term_7), each
  * sum from 0.0f in the order of j.  The actions are bit for bit those of dockauv_policy_forward.  Refused when the policy has
  * no log_std, and when out_act == DOCKAUV_ACT_TANH: the log-probability of a squashed action needs the correction
- * -sum_j log(1 - tanh(x_j)^2), which stays with the learner (SAC). */
+ * -sum_j log(1 - tanh(x_j)^2), which only the squashed-Gaussian actor has (dockauv_sac_actor_create, at the end of this header:
+ * for that role this call writes the squashed log-probability stated there). */
 int dockauv_policy_forward_logp(dockauv_handle h, dockauv_policy p, const float* rows, float* actions, float* log_prob,
                                 uint64_t t, int stochastic, void* hip_stream);
 /* RolloutBuffer.compute_returns_and_advantage on the rows of a rollout.  rows_out: float32 [n_steps][n_envs][n_obs + 2] (only
@@ -1114,6 +1115,124 @@ int dockauv_replay_sample(dockauv_handle h, dockauv_replay rb, const dockauv_rep
 int dockauv_replay_counts(dockauv_replay rb, long long* pos, long long* size, uint64_t* draws);
 int dockauv_replay_set_counts(dockauv_replay rb, long long pos, long long size, uint64_t draws);
 int dockauv_replay_state(dockauv_replay rb, float** storage, float** carry, long long* capacity_steps, int* record_floats);
+
+/*
+ * SAC, the gradient-free half: what SB3 1.5's SAC computes under torch.no_grad() plus the actor that collect_rollouts queries
+ * (train() with MODEL = SAC, SAC_HYPER_PARAMS_*) -- the squashed-Gaussian actor (sac.policies.Actor, use_sde = False), Q critics on
+ * [obs | action] (ContinuousCritic) and the TD target of SAC.train -- on the tile body of the MLP actor.  Additive: calls that do
+ * not use these objects queue exactly what they queued before.  The gradient half (dQ/da through the critic's first layer, the
+ * actor and critic losses, ent_coef, the Polyak update) is not in the library; torch on raw tensors plus dockauv_policy_load /
+ * dockauv_sac_actor_load serves until it is.  All pointers below are device pointers unless a descriptor says otherwise; every call
+ * is asynchronous on the stream and synchronises nothing.
+ *
+ * Widths stay <= DOCKAUV_POLICY_MAX_WIDTH (128), one or two hidden layers, tanh or ReLU hidden units.  SB3's SAC default
+ * net_arch = [256, 256] does NOT fit: 256 x 256 float32 weights alone exceed the 160 KiB of LDS a group keeps the network in.
+ * Use policy_kwargs = dict(net_arch = [128, 128]) or narrower.
+ *
+ * The actor.  latent = MLP(obs); mu = W_mu latent + b_mu; log_std = clamp(W_ls latent + b_ls, -20, 2);
+ *   x = mu + exp(log_std) z;  a = tanh(x);  log_prob = sum_j Normal(mu_j, std_j).log_prob(x_j) - sum_j log(1 - a_j^2 + 1e-6)
+ * and deterministic means a = tanh(mu).  A dockauv_policy with a third role (after actor and critic): the same handle ownership,
+ * dockauv_policy_destroy, and validation style -- every failure is DOCKAUV_E_INVALID with the field named, before any device call;
+ * n_in == dockauv_n_obs, n_out == dockauv_n_u.  Both heads live in the one 32-unit output tile every actor computes (W_mu in units
+ * 0 .. n_u - 1, W_ls in units 8 .. 8 + n_u - 1), so the second head costs no further matrix instruction.  Per action j, float32,
+ * with mu_j and ls_j each one accumulator chain from its bias as for every other unit:
+ *   ls  = fminf(fmaxf(ls_j, -20.0f), 2.0f)
+ *   std = expf(ls)                                   (the expf that gives the plain actor's exp(log_std))
+ *   x   = stochastic ? fmaf(std, z, mu_j) : mu_j     (z = 0 when not stochastic)
+ *   a_j = tanh(x)                                    (the plain actor's output tanh: the same bits)
+ *   g_j = fmaf(-0.5f * z, z, -(ls + 0.918938533f))
+ *   e = expf(-2.0f * fabsf(x));  d = 1.0f + e;  c_j = logf(4.0f * e / (d * d) + 1e-6f)
+ * 1 - tanh(x)^2 is formed as 4 e / (1 + e)^2, not as 1 - a * a: no cancellation where the correction matters, no overflow.
+ *   log_prob = (G_lo - C_lo) + (G_hi - C_hi),  G / C the sums of g_j / c_j from 0.0f in the order of j over j = 0..3 (lo) and 4..7 (hi).
+ * Consequences that tests hold bit for bit: deterministic actions are those of a plain dockauv_policy with the same hidden layers,
+ * W3 = W_mu, b3 = b_mu and out_act = DOCKAUV_ACT_TANH; with W_ls = 0 and b_ls = c in [-20, 2] the stochastic actions are those of
+ * that policy with log_std = c, same seed and t.
+ * z: in the per-env calls the plain actor's normal, Philox counter (env_id_offset + i, t mod 2^32, j, 2); in the rows form used by
+ * dockauv_sac_target a stream of its own, counter (row_offset + i, t mod 2^32, j, 5), i the position in the batch.
+ *
+ * Accepted by dockauv_policy_forward, dockauv_rollout (and so by the rollout that fills a replay buffer), by
+ * dockauv_policy_forward_logp -- which writes the squashed log-probability above for this role; a plain policy with out_act ==
+ * DOCKAUV_ACT_TANH is still refused there -- and by evaluation, which is a deterministic rollout.  Refused by name by everything
+ * PPO-specific: the dockauv_collect family, dockauv_ppo_head, dockauv_ppo_update, dockauv_policy_backward, dockauv_optim_create; and
+ * by dockauv_policy_load (its weights come through dockauv_sac_actor_load) and dockauv_policy_forward_rows.
+ */
+typedef struct dockauv_sac_actor_desc {
+    uint32_t struct_size;          /* sizeof(dockauv_sac_actor_desc): ABI check */
+    int32_t precision;             /* DOCKAUV_F32 */
+    int32_t n_in, n_hidden[2], n_out;  /* as dockauv_policy_desc: n_in = dockauv_n_obs, n_out = dockauv_n_u */
+    int32_t hidden_act;            /* DOCKAUV_ACT_TANH / _RELU (SB3's SAC default is ReLU) */
+    int32_t pointers_on_device;    /* 0: host arrays; 1: device arrays, copied stream-ordered */
+    int32_t reserved[2];
+    const float *W1, *b1, *W2, *b2;            /* latent_pi; W2/b2 NULL with one hidden layer */
+    const float *W_mu, *b_mu, *W_ls, *b_ls;    /* the two heads, [n_out][n_last] and [n_out] each (mu, log_std) */
+    uint64_t seed, env_id_offset;  /* as dockauv_policy_desc */
+} dockauv_sac_actor_desc;
+int dockauv_sac_actor_create(dockauv_handle h, const dockauv_sac_actor_desc* d, dockauv_policy* out);
+/* new weights of the same shapes and hidden activation; seed / env_id_offset are taken over */
+int dockauv_sac_actor_load(dockauv_policy p, const dockauv_sac_actor_desc* d, void* hip_stream);
+
+/*
+ * Q critics (SB3's ContinuousCritic, one network per handle; SAC uses two and two targets): a dockauv_policy with a fourth role,
+ * created from a dockauv_policy_desc with n_in == dockauv_n_obs + dockauv_n_u, n_out == 1 and out_act == DOCKAUV_ACT_NONE; log_std,
+ * seed and env_id_offset are ignored.  dockauv_policy_load (a target network's Polyak-averaged weights, pointers_on_device = 1) and
+ * dockauv_policy_destroy work on it; every other call that takes an actor or a value critic refuses it.
+ *
+ * dockauv_q_forward: q[i] = Q([obs row | action row]) for i < n_rows.  With r = row_index ? row_index[i] : i the layer-1 input
+ * column k is obs[r * obs_stride + k] for k < n_obs and actions[r * act_stride + k - n_obs] beyond; everything behind layer 1 is
+ * the actor's tile body.  Pointer, strides and index are free, so Q is evaluated straight from the replay ring without a sample
+ * copy: obs = storage (or storage + n_obs for next_obs), actions = storage + 2 n_obs, both strides record_floats, row_index = the
+ * index dockauv_replay_sample wrote.  A row's q depends on that row and the weights only.
+ */
+int dockauv_q_create(dockauv_handle h, const dockauv_policy_desc* d, dockauv_policy* out);
+typedef struct dockauv_q_io {
+    uint32_t struct_size;          /* sizeof(dockauv_q_io): ABI check */
+    int32_t obs_stride;            /* floats between observation rows, >= n_obs */
+    int32_t act_stride;            /* floats between action rows, >= n_u */
+    int32_t reserved;
+    const float* obs;
+    const float* actions;
+    const int64_t* row_index;      /* nullable [n_rows] */
+    long long n_rows;              /* >= 1 */
+    float* q;                      /* [n_rows] */
+} dockauv_q_io;
+int dockauv_q_forward(dockauv_handle h, dockauv_policy critic, const dockauv_q_io* io, void* hip_stream);
+
+/*
+ * The TD target of SAC.train in one host call:
+ *   a2, logp2 = actor.sample(next_obs);   y = r + gamma (1 - d) (min(Q1', Q2')(next_obs, a2) - alpha logp2)
+ * Exactly four launches: the actor's log-probability kernel on the rows (stochastic, the slot-5 normals above), the two Q kernels
+ * on (next_obs rows, a2), and one row kernel.  With s = row_index ? row_index[i] : i, next_obs row i starts at next_obs +
+ * s * next_obs_stride, and r, d are rewards[s * column_stride], dones[s * column_stride]; with timeouts (nullable) d <- d *
+ * (1.0f - timeouts[s * column_stride]), exact for the 0.0f / 1.0f the ring holds -- SB3's handle_timeout_termination.  So the call
+ * runs on dockauv_replay_sample's dense outputs (row_index NULL, next_obs_stride n_obs, column_stride 1, timeouts NULL: its dones
+ * are already done * (1 - timeout)) or on the ring itself (its index; next_obs = storage + n_obs, rewards = storage + 2 n_obs + n_u,
+ * dones and timeouts the two floats behind, both strides record_floats): the same bits.  alpha = log_ent_coef ?
+ * expf(*log_ent_coef) : ent_coef -- a learned coefficient needs no read-back.  The last kernel, float32:
+ *   v = fmaf(-alpha, logp2, fminf(q1, q2));   y = fmaf(gamma * (1.0f - d), v, r)
+ * Outputs are the caller's: a2 [n_rows][n_u], logp2, q1, q2, y [n_rows] each, all required.  Fusing the four launches into one
+ * kernel would need the three networks in LDS at once, which fits narrow networks only; it is not built.
+ * Refused before any device call: NULL arguments, a wrong struct_size, n_rows < 1, gamma outside [0, 1], strides below the row
+ * widths, an actor that is not a squashed-Gaussian actor, critics that are not Q critics, objects of another handle.
+ */
+typedef struct dockauv_sac_target_io {
+    uint32_t struct_size;          /* sizeof(dockauv_sac_target_io): ABI check */
+    int32_t next_obs_stride;       /* floats between next_obs rows, >= n_obs */
+    int32_t column_stride;         /* floats between the entries of rewards / dones / timeouts, >= 1 */
+    float gamma;                   /* in [0, 1] */
+    float ent_coef;                /* alpha when log_ent_coef is NULL */
+    int32_t reserved;
+    const float* next_obs;
+    const int64_t* row_index;      /* nullable [n_rows] */
+    const float* rewards;
+    const float* dones;
+    const float* timeouts;         /* nullable */
+    const float* log_ent_coef;     /* nullable device scalar */
+    long long n_rows;              /* >= 1 */
+    uint64_t t, row_offset;        /* the normals' counter: (row_offset + i, t mod 2^32, j, 5), key = the actor's seed */
+    float *a2, *logp2, *q1, *q2, *y;
+} dockauv_sac_target_io;
+int dockauv_sac_target(dockauv_handle h, dockauv_policy actor, dockauv_policy q1_target, dockauv_policy q2_target,
+                       const dockauv_sac_target_io* io, void* hip_stream);
 
 #ifdef __cplusplus
 }
