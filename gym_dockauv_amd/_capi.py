@@ -247,6 +247,30 @@ class SacTargetIO(C.Structure):
     ]
 
 
+class SacRowsIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("row_stride", C.c_int32),
+        ("rows", C.c_void_p), ("row_index", C.c_void_p), ("n_rows", C.c_longlong), ("out", C.c_void_p),
+    ]
+
+
+class SacActorBackwardIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("row_stride", C.c_int32),
+        ("rows", C.c_void_p), ("row_index", C.c_void_p), ("n_rows", C.c_longlong), ("grad_out", C.c_void_p),
+        ("dW1", C.c_void_p), ("db1", C.c_void_p), ("dW2", C.c_void_p), ("db2", C.c_void_p),
+        ("dW_mu", C.c_void_p), ("db_mu", C.c_void_p), ("dW_ls", C.c_void_p), ("db_ls", C.c_void_p),
+    ]
+
+
+class QBackwardIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("obs_stride", C.c_int32), ("act_stride", C.c_int32), ("reserved", C.c_int32),
+        ("obs", C.c_void_p), ("actions", C.c_void_p), ("row_index", C.c_void_p), ("n_rows", C.c_longlong), ("grad_q", C.c_void_p),
+        ("grads", C.POINTER(PolicyGrads)), ("grad_actions", C.c_void_p),
+    ]
+
+
 # every symbol include/dockauv.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("dockauv_abi_version", C.c_int, []),
@@ -337,6 +361,11 @@ SYMBOLS = [
     ("dockauv_q_create", C.c_int, [C.c_void_p, C.POINTER(PolicyDesc), C.POINTER(C.c_void_p)]),
     ("dockauv_q_forward", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QIO), C.c_void_p]),
     ("dockauv_sac_target", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SacTargetIO), C.c_void_p]),
+    # (the networks' share of SAC's gradient half)
+    ("dockauv_sac_actor_forward_rows", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SacRowsIO), C.c_void_p]),
+    ("dockauv_sac_actor_backward", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SacActorBackwardIO), C.c_void_p]),
+    ("dockauv_q_backward", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QBackwardIO), C.c_void_p]),
+    ("dockauv_policy_backward_workspace", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]),
     ("dockauv_replay_create", C.c_int, [C.c_void_p, C.c_longlong, C.c_uint64, C.POINTER(C.c_void_p)]),
     ("dockauv_replay_destroy", C.c_int, [C.c_void_p]),
     ("dockauv_replay_sync", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

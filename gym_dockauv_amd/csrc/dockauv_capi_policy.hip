@@ -1,5 +1,5 @@
 // dockauv_capi_policy.hip -- C ABI of libdockauv.so (include/dockauv.h), second part: MLP policy and critic, closed-loop
-// rollout, PPO collector, backward, head, optimiser, episode monitor and reward normaliser, and (at the end) SAC's forward half.
+// rollout, PPO collector, backward, head, optimiser, episode monitor and reward normaliser, and (at the end) SAC's forward half and its networks' gradients.
 // The kernels are in dockauv_policy / _collect / _backward / _head / _optim / _monitor / _update / _rewnorm / _sac.hip.
 #include <cmath>
 #include <cstring>
@@ -1438,6 +1438,145 @@ int dockauv_sac_target(dockauv_handle h, dockauv_policy actor, dockauv_policy q1
     if ((rc = launch_sac_target_rows(tl, hip_stream)) != 0)
         return fail(h, DOCKAUV_E_HIP, "SAC target kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     h->last_stream = (hipStream_t)hip_stream;
+    return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ SAC: the networks' gradients (dockauv_backward.hip)
+namespace {
+
+// `p` must be this handle's squashed-Gaussian actor (sac) or Q critic (!sac): the three other roles by name
+int check_sac_role(dockauv_handle h, dockauv_policy p, const char* fn, bool sac) {
+    if (p->h != h) return fail(h, DOCKAUV_E_INVALID, "%s: the policy was created for another handle", fn);
+    const char* want = sac ? "a squashed-Gaussian actor (dockauv_sac_actor_create)" : "a Q critic (dockauv_q_create)";
+    if (p->value_role) return fail(h, DOCKAUV_E_INVALID, "%s: the policy is a value critic (dockauv_value_create), %s is needed", fn, want);
+    if (p->sac_role && !sac) return fail(h, DOCKAUV_E_INVALID, "%s: the policy is a squashed-Gaussian actor (dockauv_sac_actor_create), %s is needed", fn, want);
+    if (p->q_role && sac) return fail(h, DOCKAUV_E_INVALID, "%s: the policy is a Q critic (dockauv_q_create), %s is needed", fn, want);
+    if (!p->sac_role && !p->q_role) return fail(h, DOCKAUV_E_INVALID, "%s: the policy is a plain actor (dockauv_policy_create), %s is needed", fn, want);
+    return 0;
+}
+
+// the LDS need of the backward of `p` against the 160 KiB of a group
+int check_backward_lds(dockauv_handle h, dockauv_policy p, const BackwardLayout& L, const char* fn) {
+    if (backward_lds_bytes(L) > kPolMaxLds)
+        return fail(h, DOCKAUV_E_INVALID, "%s: the kernel needs %zu B of LDS for n_in %d, n_hidden %d / %d (weights, one pass's rows, "
+                    "activations and deltas), more than the 160 KiB of a group: narrower layers or observations",
+                    fn, backward_lds_bytes(L), p->S.n_in, p->S.n_h1, p->S.n_h2);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dockauv_sac_actor_forward_rows(dockauv_handle h, dockauv_policy actor, const dockauv_sac_rows_io* io, void* hip_stream) {
+    const char* fn = "dockauv_sac_actor_forward_rows";
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "%s: io is NULL", fn);
+    if (io->struct_size != sizeof(dockauv_sac_rows_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_rows_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_sac_rows_io));
+    if (io->n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_rows_io.n_rows: %lld must be >= 1", io->n_rows);
+    if (io->row_stride < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_rows_io.row_stride: %d is below every row width", io->row_stride);
+    if (!io->rows) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_rows_io.rows is NULL");
+    if (!io->out) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_rows_io.out is NULL");
+    if (!actor) return fail(h, DOCKAUV_E_INVALID, "%s: null actor", fn);
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
+    if (int rc = check_sac_role(h, actor, fn, true)) return rc;
+    if (io->row_stride < h->n_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_rows_io.row_stride: %d is below the handle's n_obs %d", io->row_stride, h->n_obs);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int rc = launch_sac_actor_heads(actor->S, actor->packed, io->rows, (const long long*)io->row_index, (long)io->n_rows, io->row_stride,
+                                          io->out, hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "SAC actor heads kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
+    return 0;
+}
+
+int dockauv_sac_actor_backward(dockauv_handle h, dockauv_policy actor, const dockauv_sac_actor_backward_io* io, void* hip_stream) {
+    const char* fn = "dockauv_sac_actor_backward";
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "%s: io is NULL", fn);
+    if (io->struct_size != sizeof(dockauv_sac_actor_backward_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_backward_io.struct_size: got %u, library has %zu", io->struct_size,
+                    sizeof(dockauv_sac_actor_backward_io));
+    if (io->n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_backward_io.n_rows: %lld must be >= 1", io->n_rows);
+    if (io->row_stride < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_backward_io.row_stride: %d is below every row width", io->row_stride);
+    if (!io->rows) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_backward_io.rows is NULL");
+    if (!io->grad_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_backward_io.grad_out is NULL");
+    if (!io->dW1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_backward_io.dW1 is NULL");
+    if (!io->db1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_backward_io.db1 is NULL");
+    if (!io->dW_mu) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_backward_io.dW_mu is NULL");
+    if (!io->db_mu) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_backward_io.db_mu is NULL");
+    if (!io->dW_ls) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_backward_io.dW_ls is NULL");
+    if (!io->db_ls) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_backward_io.db_ls is NULL");
+    if (!actor) return fail(h, DOCKAUV_E_INVALID, "%s: null actor", fn);
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
+    if (int rc = check_sac_role(h, actor, fn, true)) return rc;
+    if (io->row_stride < h->n_obs)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_backward_io.row_stride: %d is below the handle's n_obs %d", io->row_stride, h->n_obs);
+    if (actor->S.n_h2 > 0 && !io->dW2) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_backward_io.dW2 is NULL, the actor has two hidden layers");
+    if (actor->S.n_h2 > 0 && !io->db2) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_backward_io.db2 is NULL, the actor has two hidden layers");
+    BackwardLayout L;
+    sac_actor_backward_layout(actor->S, L);
+    if (int rc = check_backward_lds(h, actor, L, fn)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!actor->bwd_partial) HIP_TRY(h, hipMalloc((void**)&actor->bwd_partial, (size_t)kBwdMaxGroups * L.n_params * sizeof(float)));
+    const bool two = actor->S.n_h2 > 0;
+    const SacActorGrads g{io->dW1, io->db1, two ? io->dW2 : nullptr, two ? io->db2 : nullptr, io->dW_mu, io->db_mu, io->dW_ls, io->db_ls};
+    const SacBackwardLaunch l{io->rows, nullptr, (const long long*)io->row_index, io->grad_out, nullptr, (long)io->n_rows, io->row_stride, 0,
+                              actor->S.n_in};
+    const int rc = launch_sac_actor_backward(actor->S, actor->packed, l, actor->bwd_partial, g, hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "SAC actor backward launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
+    return 0;
+}
+
+int dockauv_q_backward(dockauv_handle h, dockauv_policy critic, const dockauv_q_backward_io* io, void* hip_stream) {
+    const char* fn = "dockauv_q_backward";
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "%s: io is NULL", fn);
+    if (io->struct_size != sizeof(dockauv_q_backward_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_q_backward_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_q_backward_io));
+    if (io->n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_q_backward_io.n_rows: %lld must be >= 1", io->n_rows);
+    if (io->obs_stride < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_q_backward_io.obs_stride: %d is below every row width", io->obs_stride);
+    if (io->act_stride < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_q_backward_io.act_stride: %d is below every row width", io->act_stride);
+    if (!io->obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_q_backward_io.obs is NULL");
+    if (!io->actions) return fail(h, DOCKAUV_E_INVALID, "dockauv_q_backward_io.actions is NULL");
+    if (!io->grad_q) return fail(h, DOCKAUV_E_INVALID, "dockauv_q_backward_io.grad_q is NULL");
+    if (!io->grads && !io->grad_actions)
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_q_backward_io: grads and grad_actions are both NULL, at least one output is required");
+    const dockauv_policy_grads* gr = io->grads;
+    if (gr && gr->struct_size != sizeof(dockauv_policy_grads))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_grads.struct_size: got %u, library has %zu", gr->struct_size, sizeof(dockauv_policy_grads));
+    if (gr && (!gr->dW1 || !gr->db1 || !gr->dW3 || !gr->db3))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_grads: dW1/db1/dW3/db3 must not be NULL");
+    if (!critic) return fail(h, DOCKAUV_E_INVALID, "%s: null critic", fn);
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
+    if (int rc = check_sac_role(h, critic, fn, false)) return rc;
+    if (io->obs_stride < h->n_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_q_backward_io.obs_stride: %d is below the handle's n_obs %d", io->obs_stride, h->n_obs);
+    if (io->act_stride < h->n_u_max) return fail(h, DOCKAUV_E_INVALID, "dockauv_q_backward_io.act_stride: %d is below the handle's n_u %d", io->act_stride, h->n_u_max);
+    if (gr && critic->S.n_h2 > 0 && (!gr->dW2 || !gr->db2))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_policy_grads: dW2/db2 are NULL, the critic has two hidden layers");
+    BackwardLayout L;
+    backward_layout(critic->S, L);
+    if (int rc = check_backward_lds(h, critic, L, fn)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (gr && !critic->bwd_partial) HIP_TRY(h, hipMalloc((void**)&critic->bwd_partial, (size_t)kBwdMaxGroups * L.n_params * sizeof(float)));
+    const bool two = critic->S.n_h2 > 0;
+    PolicyGrads g{};
+    if (gr) g = PolicyGrads{gr->dW1, gr->db1, two ? gr->dW2 : nullptr, two ? gr->db2 : nullptr, gr->dW3, gr->db3};
+    const SacBackwardLaunch l{io->obs, io->actions, (const long long*)io->row_index, io->grad_q, io->grad_actions, (long)io->n_rows,
+                              io->obs_stride, io->act_stride, h->n_obs};
+    const int rc = launch_q_backward(critic->S, critic->packed, l, gr ? critic->bwd_partial : nullptr, gr ? &g : nullptr, hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "Q backward launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
+    return 0;
+}
+
+int dockauv_policy_backward_workspace(dockauv_policy p, float** partial, long long* n_floats) {
+    if (!p) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_policy_backward_workspace: null policy");
+    BackwardLayout L;                                   // (the role fixes the partial's size)
+    if (p->sac_role) sac_actor_backward_layout(p->S, L);
+    else backward_layout(p->S, L);
+    if (partial) *partial = p->bwd_partial;
+    if (n_floats) *n_floats = p->bwd_partial ? (long long)kBwdMaxGroups * L.n_params : 0;
     return 0;
 }
 

@@ -597,6 +597,7 @@ int launch_sac_target_rows(const SacTargetLaunch& l, void* stream);
 // group of four waves walks passes of 32 rt rows.  Everything a pass touches lies in LDS as plain row-major matrices with odd
 // strides, so that each is an MFMA A operand (lane = row of the matrix) and a B operand (lane = column) without bank conflicts:
 //   W1 [32 mt1][ws1], W2 [32 mt2][ws2], W3 [8][ws3]   torch.nn.Linear layout, zero-padded (un-permuted from `packed` once per group)
+//                                                      (W3 and G: 16 rows for the squashed-Gaussian actor's two heads, out_rows)
 //   X [2 ks1][rs], G [8][rs]                           the pass's observations and upstream gradients, [column][row of the pass]
 //   H1 [32 mt1][rs], H2 [32 max(mt1, mt2)][rs], D [32 mtl][rs]   activations and deltas, [unit][row]; delta 1 of two layers reuses H2
 //   ACC [slots][4][1024]                               dW1 tiles a wave holds beyond its two register tiles (wide observations)
@@ -607,7 +608,7 @@ struct BackwardLayout {
     int off_w1, off_w2, off_w3, off_b1, off_b2, off_x, off_g, off_h1, off_h2, off_d, off_acc, total;
     int p_w1, p_b1, p_w2, p_b2, p_w3, p_b3, n_params;
 };
-inline void backward_layout(const PolicyShape& s, BackwardLayout& l) {
+inline void backward_layout(const PolicyShape& s, BackwardLayout& l, int out_rows = 8) {   // out_rows: rows of W3 and G
     const int mtl = s.mt2 ? s.mt2 : s.mt1, mtmax = s.mt1 > s.mt2 ? s.mt1 : s.mt2;
     l.rt = mtmax >= 3 ? 1 : (mtmax == 2 ? 2 : 4);
     l.rs = 32 * l.rt + 1;
@@ -620,11 +621,11 @@ inline void backward_layout(const PolicyShape& s, BackwardLayout& l) {
     int o = 0;
     l.off_w1 = o; o += 32 * s.mt1 * l.ws1;
     l.off_w2 = o; o += 32 * s.mt2 * l.ws2;
-    l.off_w3 = o; o += 8 * l.ws3;
+    l.off_w3 = o; o += out_rows * l.ws3;
     l.off_b1 = o; o += 32 * s.mt1;
     l.off_b2 = o; o += 32 * s.mt2;
     l.off_x = o; o += 2 * s.ks1 * l.rs;
-    l.off_g = o; o += 8 * l.rs;
+    l.off_g = o; o += out_rows * l.rs;
     l.off_h1 = o; o += 32 * s.mt1 * l.rs;
     l.off_h2 = o; o += (s.mt2 ? 32 * mtmax : 0) * l.rs;   // (delta 1, mt1 tiles, is written here too)
     l.off_d = o; o += 32 * mtl * l.rs;
@@ -649,6 +650,42 @@ struct PolicyGrads {   // device pointers, Linear layout; dW2 / db2 null with on
 // group order.  backward_lds_bytes must be <= kPolMaxLds (the caller checks).  Returns a hipError_t as int.
 int launch_policy_backward(const PolicyShape& s, const float* packed, const float* rows, const long long* row_index, long n,
                            int row_stride, const float* grad_out, float* partial, const PolicyGrads& grads, void* stream);
+
+// ------------------------------------------------------------------------------------------ SAC backward (dockauv_backward.hip)
+// The same passes for SAC's networks (include/dockauv.h: dockauv_sac_actor_backward, dockauv_q_backward).  The squashed-Gaussian
+// actor: W3 [16][ws3] and G [16][rs] -- W_mu / d mu in rows 0 .. n_u - 1, W_ls / d log_std in rows 8 .. 8 + n_u - 1, as the packed
+// output tile holds them -- and a partial whose output block is [2 n_u][n_last] + [2 n_u], mu first (s.n_out = n_u).
+inline void sac_actor_backward_layout(const PolicyShape& s, BackwardLayout& l) {
+    PolicyShape both = s;
+    both.n_out = 2 * s.n_out;             // (only p_b3 and n_params depend on n_out)
+    backward_layout(both, l, 16);
+}
+struct SacActorGrads {   // device pointers, Linear layout; dW2 / db2 null with one hidden layer
+    float *dW1, *db1, *dW2, *db2, *dW_mu, *db_mu, *dW_ls, *db_ls;
+};
+// X row i = [rows[r * row_stride + 0 .. n_obs) | actions[r * act_stride + 0 .. n_in - n_obs)], r = row_index ? row_index[i] : i
+// (the actor: n_obs = n_in, actions unread).  grad_out: the actor's [n][2 n_u] on (mu | raw log_std), a critic's [n].
+struct SacBackwardLaunch {
+    const float *rows, *actions;
+    const long long* row_index;           // nullable [n]
+    const float* grad_out;
+    float* grad_actions;                  // Q only, nullable: [n][n_u] = W1[:, n_obs ..]^T delta1 of row i, overwritten
+    long n;
+    int row_stride, act_stride, n_obs;
+};
+// Two launches (partials, their sum in group order into the eight arrays).  partial: [kBwdMaxGroups][n_params of
+// sac_actor_backward_layout].  Returns a hipError_t as int.
+int launch_sac_actor_backward(const PolicyShape& s, const float* packed, const SacBackwardLaunch& l, float* partial,
+                              const SacActorGrads& grads, void* stream);
+// grads != nullptr: launch_policy_backward's two launches on x = [obs | action].  grad_actions != nullptr: ONE launch of the form
+// without parameter gradients -- no gradient tiles, no bias sums, partial untouched (may be null without grads) -- behind them.
+// Returns a hipError_t as int.
+int launch_q_backward(const PolicyShape& s, const float* packed, const SacBackwardLaunch& l, float* partial, const PolicyGrads* grads,
+                      void* stream);
+// out[i][0 .. n_u) = mu, out[i][n_u .. 2 n_u) = the raw log_std head of row rows[(row_index ? row_index[i] : i) * row_stride]: the
+// tile body of launch_sac_actor without noise, clamp and tanh (dockauv_sac.hip).  out: [n][2 n_u].  Returns a hipError_t as int.
+int launch_sac_actor_heads(const PolicyShape& s, const float* packed, const float* rows, const long long* row_index, long n,
+                           int row_stride, float* out, void* stream);
 
 // ------------------------------------------------------------------------------------------ GAE (dockauv_collect.hip)
 // SB3's compute_returns_and_advantage over packed rows: rows [K][N][row_stride] with the reward in column n_obs and done in

@@ -10,6 +10,8 @@
 //   * the Q critic: the same body with a two-source layer-1 operand -- column k < n_obs from the observation row, k >= n_obs from
 //     actions[k - n_obs], chosen per lane, so an odd n_obs straddles the two sources inside one k step;
 //   * the TD target's last stage: one thread per row.
+//   * sac_actor_heads_kernel (dockauv_sac_actor_forward_rows, the forward of the gradient half): the actor's tile body with mu and
+//     the raw log_std written out, before clamp, noise and tanh.
 // Rows come through an optional int64 index with a free row stride (as policy_rows_kernel takes them), so all of it runs on the
 // replay ring as it stands.  Instantiated per (tiles of hidden layer 1, tiles of hidden layer 2) like the other MLP kernels.
 #include <hip/hip_runtime.h>
@@ -104,6 +106,34 @@ __global__ __launch_bounds__(kPolThreads) void sac_actor_logp_kernel(const SacAr
     sac_actor_tile_<MT1, MT2, true>(a, lds, tile);
 }
 
+// both heads before the clamp, without noise and tanh (dockauv_sac_actor_forward_rows): the tile body above with another
+// epilogue -- registers r (mu_j) and 4 + r (the raw log_std_j), j = 4 half + r, written out as out[row][j] and out[row][n_u + j]
+template <int MT1, int MT2>
+__global__ __launch_bounds__(kPolThreads) void sac_actor_heads_kernel(const SacArgs a) {
+    extern __shared__ float lds[];
+    stage_weights_(a.packed, a.S.total, lds);
+    const long tile = (long)blockIdx.x * (kPolThreads / 64) + (threadIdx.x >> 6);
+    if (tile * 32 >= a.n) return;                       // (no barrier below)
+    const PolicyShape& S = a.S;
+    const int lane = threadIdx.x & 63, half = lane >> 5;
+    const long env = tile * 32 + (lane & 31);
+    const bool live = env < a.n;                        // tail: rows >= n are neither read nor written
+    long src = live ? env : 0;
+    if (live && a.row_index) src = (long)a.row_index[env];
+    const float* row = a.rows + src * (long)a.row_stride;
+    f32x16 out[1];
+    mlp_tile_<MT1, MT2>(S, lds, lane, half, [&](int k) { return (live && k < S.n_in) ? row[k] : 0.0f; }, out);
+    float* dst = a.out + (live ? env : 0) * (long)a.out_stride;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int j = 4 * half + r;
+        if (live && j < S.n_out) {
+            dst[j] = out[0][r];
+            dst[S.n_out + j] = out[0][4 + r];
+        }
+    }
+}
+
 // Q(obs, action) of any rows: layer-1 column k from the observation row (k < n_obs) or the action row (n_obs <= k < n_in)
 template <int MT1, int MT2>
 __global__ __launch_bounds__(kPolThreads) void q_kernel(const SacArgs a) {
@@ -148,14 +178,15 @@ __global__ void sac_target_kernel(const TargetArgs a) {
     a.y[i] = fmaf(a.gamma * (1.0f - d), v, r);
 }
 
-enum SacKernel { SAC_ACTOR, SAC_ACTOR_LOGP, SAC_Q };
+enum SacKernel { SAC_ACTOR, SAC_ACTOR_LOGP, SAC_Q, SAC_HEADS };
 
 template <int MT1, int MT2>
 int launch_sac_(const SacArgs& a, int which, size_t lds, hipStream_t stream) {
     const long tiles = ((long)a.n + 31) / 32;
     const long groups = (tiles + kPolThreads / 64 - 1) / (kPolThreads / 64);
     void (*kernel)(const SacArgs) = which == SAC_Q ? q_kernel<MT1, MT2>
-                                    : (which == SAC_ACTOR_LOGP ? sac_actor_logp_kernel<MT1, MT2> : sac_actor_kernel<MT1, MT2>);
+                                    : (which == SAC_HEADS ? sac_actor_heads_kernel<MT1, MT2>
+                                       : (which == SAC_ACTOR_LOGP ? sac_actor_logp_kernel<MT1, MT2> : sac_actor_kernel<MT1, MT2>));
     if (groups > 0x7fffffffL) return (int)hipErrorInvalidValue;
     if (lds > 64 * 1024) {
         // more than 64 KiB of LDS per group must be requested explicitly, per (device, function): on the launch path
@@ -209,6 +240,20 @@ int launch_sac_actor(const PolicyShape& s, const float* packed, const SacActorLa
     a.slot = l.slot;
     a.seed = l.seed;
     return launch_sac_any_(a, l.log_prob ? SAC_ACTOR_LOGP : SAC_ACTOR, (hipStream_t)stream);
+}
+
+int launch_sac_actor_heads(const PolicyShape& s, const float* packed, const float* rows, const long long* row_index, long n,
+                           int row_stride, float* out, void* stream) {
+    SacArgs a{};
+    a.S = s;
+    a.packed = packed;
+    a.rows = rows;
+    a.row_index = row_index;
+    a.out = out;
+    a.n = n;
+    a.row_stride = row_stride;
+    a.out_stride = 2 * s.n_out;
+    return launch_sac_any_(a, SAC_HEADS, (hipStream_t)stream);
 }
 
 int launch_q_forward(const PolicyShape& s, const float* packed, const QLaunch& l, void* stream) {

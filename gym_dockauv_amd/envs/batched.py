@@ -684,6 +684,58 @@ class BatchedDocking3d:
         rc = self._lib.dockauv_q_forward(self._handle, critic.ptr, C.byref(io), C.c_void_p(stream or None))
         _capi.check(self._lib, self._handle, rc, "dockauv_q_forward")
 
+    def sac_actor_forward_rows_device(self, actor, rows_ptr: int, n_rows: int, out_ptr: int, row_stride: int = 0, index_ptr: int = 0,
+                                      stream: int = 0) -> None:
+        """out float32 [n_rows][2 n_u] = (mu | the raw log_std head, before its clamp) of a squashed-Gaussian actor for observation
+        rows ``row_stride`` floats apart (0: dense, n_obs), through the int64 ``index_ptr`` when given
+        (dockauv_sac_actor_forward_rows): no noise, no tanh; asynchronous."""
+        io = _capi.SacRowsIO()
+        io.struct_size = C.sizeof(_capi.SacRowsIO)
+        io.row_stride = int(row_stride) or self.n_observations
+        io.rows, io.row_index, io.n_rows, io.out = rows_ptr or None, index_ptr or None, int(n_rows), out_ptr or None
+        rc = self._lib.dockauv_sac_actor_forward_rows(self._handle, actor.ptr, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_sac_actor_forward_rows")
+
+    def sac_actor_backward_device(self, actor, rows_ptr: int, n_rows: int, grad_out_ptr: int, grad_ptrs, row_stride: int = 0,
+                                  index_ptr: int = 0, stream: int = 0) -> None:
+        """Gradients of all weights and biases of a squashed-Gaussian actor for grad_out float32 [n_rows][2 n_u] on the output of
+        ``sac_actor_forward_rows_device`` (dockauv_sac_actor_backward): ``grad_ptrs`` = (dW1, db1, dW2, db2, dW_mu, db_mu, dW_ls,
+        db_ls) device addresses, torch.nn.Linear layout (dW2 / db2 0 with one hidden layer), overwritten; asynchronous."""
+        io = _capi.SacActorBackwardIO()
+        io.struct_size = C.sizeof(_capi.SacActorBackwardIO)
+        io.row_stride = int(row_stride) or self.n_observations
+        io.rows, io.row_index, io.n_rows, io.grad_out = rows_ptr or None, index_ptr or None, int(n_rows), grad_out_ptr or None
+        io.dW1, io.db1, io.dW2, io.db2, io.dW_mu, io.db_mu, io.dW_ls, io.db_ls = [int(x) or None for x in grad_ptrs]
+        rc = self._lib.dockauv_sac_actor_backward(self._handle, actor.ptr, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_sac_actor_backward")
+
+    def q_backward_device(self, critic, obs_ptr: int, actions_ptr: int, n_rows: int, grad_q_ptr: int, grad_ptrs=None,
+                          grad_actions_ptr: int = 0, obs_stride: int = 0, act_stride: int = 0, index_ptr: int = 0, stream: int = 0) -> None:
+        """A Q critic's backward for grad_q float32 [n_rows] on the rows of ``q_forward_device`` (dockauv_q_backward):
+        ``grad_ptrs`` = (dW1, db1, dW2, db2, dW3, db3) device addresses or None, ``grad_actions_ptr`` float32 [n_rows][n_u] or 0
+        (dq/da scaled by grad_q); at least one.  With ``grad_ptrs`` None it is one launch that touches no workspace."""
+        io = _capi.QBackwardIO()
+        io.struct_size = C.sizeof(_capi.QBackwardIO)
+        io.obs_stride, io.act_stride = int(obs_stride) or self.n_observations, int(act_stride) or self.n_u
+        io.obs, io.actions, io.row_index = obs_ptr or None, actions_ptr or None, index_ptr or None
+        io.n_rows, io.grad_q, io.grad_actions = int(n_rows), grad_q_ptr or None, grad_actions_ptr or None
+        g = None
+        if grad_ptrs is not None:
+            g = _capi.PolicyGrads()
+            g.struct_size = C.sizeof(_capi.PolicyGrads)
+            g.dW1, g.db1, g.dW2, g.db2, g.dW3, g.db3 = [int(x) or None for x in grad_ptrs]
+            io.grads = C.pointer(g)
+        rc = self._lib.dockauv_q_backward(self._handle, critic.ptr, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_q_backward")
+
+    def backward_workspace(self, policy):
+        """(device address or 0, floats) of the partial sums the backward calls of ``policy`` share
+        (dockauv_policy_backward_workspace): (0, 0) until the first backward with parameter gradients."""
+        ptr, n = C.c_void_p(), C.c_longlong()
+        rc = self._lib.dockauv_policy_backward_workspace(policy.ptr, C.byref(ptr), C.byref(n))
+        _capi.check(self._lib, self._handle, rc, "dockauv_policy_backward_workspace")
+        return int(ptr.value or 0), int(n.value)
+
     def sac_target_device(self, actor, q1_target, q2_target, next_obs_ptr: int, rewards_ptr: int, dones_ptr: int, n_rows: int,
                           gamma: float, a2_ptr: int, logp2_ptr: int, q1_ptr: int, q2_ptr: int, y_ptr: int, ent_coef: float = 0.0,
                           log_ent_coef_ptr: int = 0, t: int = 0, row_offset: int = 0, next_obs_stride: int = 0,

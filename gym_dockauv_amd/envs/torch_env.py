@@ -211,6 +211,136 @@ class TorchDocking3d:
         self.sac_buffers = b
         return b["y"].view(shape)
 
+    # ------------------------------------------------------------------------------------------ SAC: the networks' gradients
+    def _grad_out_ok(self, t, shape, what: str):
+        torch = self.torch
+        if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise ValueError(f"{what} must be a contiguous float32 {list(shape)} tensor on {self.device}")
+
+    def _grad_arrays(self, shapes, out):
+        torch = self.torch
+        if out is None:
+            return [torch.empty(s, device=self.device, dtype=torch.float32) for s in shapes]
+        grads = list(out)
+        if len(grads) != len(shapes) or any(g.device != self.device or g.dtype != torch.float32 or not g.is_contiguous()
+                                            or tuple(g.shape) != s for g, s in zip(grads, shapes)):
+            raise ValueError(f"out must be contiguous float32 tensors of shapes {shapes} on {self.device}")
+        return grads
+
+    def sac_actor_heads(self, actor, obs, index=None):
+        """[B, 2 n_u] float32 (a fresh tensor): columns 0 .. n_u - 1 are mu, n_u .. 2 n_u - 1 the log-std head BEFORE its clamp
+        to [-20, 2], of a ``make_sac_actor`` actor for obs[r], r = index[i] (``index`` int64 [B]) or i: no noise, no tanh
+        (dockauv_sac_actor_forward_rows on the current stream).  ``obs`` [n, n_obs] may be a strided view -- the replay ring:
+        ``rb.storage.view(-1, rb.record_floats)[:, :n_obs]`` with ``rb.index``."""
+        torch = self.torch
+        ptr, stride = self._rows_view(obs, self.n_obs, "obs")
+        B = obs.shape[0] if index is None else self._index_ok(index)
+        out = torch.empty((B, 2 * self.n_u), device=self.device, dtype=torch.float32)
+        self.batch.sac_actor_forward_rows_device(actor, ptr, B, out.data_ptr(), row_stride=stride,
+                                                 index_ptr=0 if index is None else index.data_ptr(),
+                                                 stream=torch.cuda.current_stream().cuda_stream)
+        return out
+
+    def sac_actor_backward(self, actor, obs, grad_out, index=None, out=None):
+        """The gradients of all weights and biases of the actor for ``grad_out`` [B, 2 n_u] = dL/d(sac_actor_heads(actor, obs,
+        index)) (the clamp's mask is the caller's): dockauv_sac_actor_backward on the current stream.  Returns fresh tensors
+        (dW1, db1[, dW2, db2], dW_mu, db_mu, dW_ls, db_ls) in torch.nn.Linear layout, or writes into ``out`` (such a sequence)
+        and returns it.  Reproducible bit for bit; no gradient with respect to ``obs``."""
+        torch = self.torch
+        ptr, stride = self._rows_view(obs, self.n_obs, "obs")
+        B = obs.shape[0] if index is None else self._index_ok(index)
+        self._grad_out_ok(grad_out, (B, 2 * self.n_u), "grad_out")
+        widths = [actor.n_in] + actor.n_hidden
+        shapes = [s for i in range(len(widths) - 1) for s in ((widths[i + 1], widths[i]), (widths[i + 1],))]
+        shapes += [(actor.n_out, widths[-1]), (actor.n_out,)] * 2
+        grads = self._grad_arrays(shapes, out)
+        ptrs = [g.data_ptr() for g in grads]
+        if len(ptrs) == 6:
+            ptrs[2:2] = [0, 0]
+        self.batch.sac_actor_backward_device(actor, ptr, B, grad_out.data_ptr(), ptrs, row_stride=stride,
+                                             index_ptr=0 if index is None else index.data_ptr(),
+                                             stream=torch.cuda.current_stream().cuda_stream)
+        return tuple(grads)
+
+    def q_backward(self, critic, obs, actions, grad_q, index=None, params=True, grad_actions=False, out=None):
+        """A ``make_q`` critic's backward for ``grad_q`` [B] = dL/d(q_values(critic, obs, actions, index)) on the current stream
+        (dockauv_q_backward).  Returns (grads, dq_da): ``grads`` = (dW1, db1[, dW2, db2], dW3, db3) with ``params`` (fresh, or
+        ``out``), else None; ``dq_da`` [B, n_u] with ``grad_actions`` -- the gradient on the action of position i of the minibatch
+        -- else None.  At least one.  ``params=False`` is SAC's actor loss: one launch, no parameter tiles, no workspace, and the
+        bits the other form gives.  ``obs`` / ``actions`` may be strided views of the replay ring."""
+        torch = self.torch
+        if not params and not grad_actions:
+            raise ValueError("params and grad_actions are both False: nothing to compute")
+        optr, ostride = self._rows_view(obs, self.n_obs, "obs")
+        aptr, astride = self._rows_view(actions, self.n_u, "actions")
+        if index is None and obs.shape[0] != actions.shape[0]:
+            raise ValueError("obs and actions need the same number of rows")
+        B = obs.shape[0] if index is None else self._index_ok(index)
+        self._grad_out_ok(grad_q, (B,), "grad_q")
+        grads = ptrs = None
+        if params:
+            widths = [critic.n_in] + critic.n_hidden + [1]
+            grads = self._grad_arrays([s for i in range(len(widths) - 1) for s in ((widths[i + 1], widths[i]), (widths[i + 1],))], out)
+            ptrs = [g.data_ptr() for g in grads]
+            if len(ptrs) == 4:
+                ptrs[2:2] = [0, 0]
+        da = torch.empty((B, self.n_u), device=self.device, dtype=torch.float32) if grad_actions else None
+        self.batch.q_backward_device(critic, optr, aptr, B, grad_q.data_ptr(), grad_ptrs=ptrs,
+                                     grad_actions_ptr=0 if da is None else da.data_ptr(), obs_stride=ostride, act_stride=astride,
+                                     index_ptr=0 if index is None else index.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+        return (None if grads is None else tuple(grads)), da
+
+    def sac_actor_apply(self, actor, params, obs, index=None):
+        """``sac_actor_heads`` as a differentiable torch operation, in the style of ``mlp_apply``: ``params`` = the learner's
+        (W1, b1[, W2, b2], W_mu, b_mu, W_ls, b_ls) device leaves.  They are loaded into ``actor`` on the current stream
+        (``load_policy``) and the forward kernel runs; ``.backward()`` runs ``sac_actor_backward`` and hands each parameter its
+        gradient.  ``obs`` and ``index`` get none.  mu, log_std = out[:, :n_u], out[:, n_u:].clamp(-20, 2): torch's clamp
+        carries the mask."""
+        torch = self.torch
+        env = self
+
+        class _Apply(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, *ps):
+                return env.sac_actor_heads(actor, obs, index)
+
+            @staticmethod
+            def backward(ctx, grad):
+                return env.sac_actor_backward(actor, obs, grad.contiguous(), index)
+
+        params = tuple(params)
+        self._load_sac_actor(actor, [p.detach() for p in params])
+        return _Apply.apply(*params)
+
+    def q_apply(self, critic, params, obs, actions, index=None):
+        """``q_values`` as a differentiable torch operation: [B].  ``params`` = the learner's (W1, b1[, W2, b2], W3, b3) device
+        leaves, loaded into ``critic`` on the current stream as ``mlp_apply`` does, each of which gets its gradient; or None --
+        the critic's weights stay as loaded and only ``actions`` gets a gradient, through the form without parameter gradients
+        (SAC's actor loss: one launch a backward).  ``actions`` gets a gradient only when ``index`` is None (then row i of
+        ``actions`` is position i of the minibatch) and it requires one; ``obs`` and ``index`` never do."""
+        torch = self.torch
+        env = self
+        with_params = params is not None
+        want_da = index is None and actions.requires_grad
+        if not with_params and not want_da:
+            raise ValueError("params is None and actions gets no gradient (it needs requires_grad and index=None)")
+
+        class _Apply(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, acts, *ps):
+                return env.q_values(critic, obs, acts.detach(), index)
+
+            @staticmethod
+            def backward(ctx, grad):
+                grads, da = env.q_backward(critic, obs, actions.detach(), grad.contiguous(), index, params=with_params,
+                                           grad_actions=want_da)
+                return (da,) + (tuple(grads) if with_params else ())
+
+        ps = tuple(params) if with_params else ()
+        if with_params:
+            self.load_policy(critic, [p.detach() for p in ps])
+        return _Apply.apply(actions, *ps)
+
     def _load_sac_actor(self, policy, module_or_tensors) -> None:
         torch = self.torch
         m = module_or_tensors

@@ -295,6 +295,23 @@ class MLPPolicy:
                 g = (g @ self.layers[i][0].astype(np.float64)) * (1.0 - h * h if self.hidden_act == "tanh" else (h > 0.0).astype(np.float64))
         return tuple(grads)
 
+    def backward_input_reference(self, x: np.ndarray, grad_out: np.ndarray) -> np.ndarray:
+        """float64 dL/dx of the same pass: x [B, n_in], grad_out [B, n_out] on the raw output -> [B, n_in] = delta1 W1, row by
+        row (no sum over the rows).  Columns n_obs .. of a Q critic's [obs | a] are dockauv_q_backward's grad_actions."""
+        x = np.asarray(x, dtype=np.float64).reshape(-1, self.n_in)
+        g = np.asarray(grad_out, dtype=np.float64).reshape(-1, self.n_out)
+        if x.shape[0] != g.shape[0]:
+            raise ValueError("x [B, n_in] and grad_out [B, n_out] need the same B")
+        hs = [x]
+        for W, b in self.layers[:-1]:
+            hs.append(_act(hs[-1] @ W.astype(np.float64).T + b.astype(np.float64), self.hidden_act))
+        for i in range(len(self.layers) - 1, -1, -1):
+            g = g @ self.layers[i][0].astype(np.float64)
+            if i > 0:
+                h = hs[i]
+                g = g * (1.0 - h * h if self.hidden_act == "tanh" else (h > 0.0).astype(np.float64))
+        return g
+
     @staticmethod
     def normals_reference(seed: int, env_ids, t: int, n_out: int, slot: int = 2) -> np.ndarray:
         """The standard normals the kernel draws for step counter ``t``: Philox4x32-10 counter (env id mod 2^32, t mod 2^32,
@@ -487,6 +504,23 @@ class SquashedGaussianMLP:
         a = np.tanh(pre)
         gauss = -((pre - mu) ** 2) / (2.0 * std ** 2) - ls - 0.5 * np.log(2.0 * np.pi)
         return a, gauss.sum(axis=-1) - np.log(1.0 - a * a + self.EPS).sum(axis=-1), mu, ls
+
+    def _both_heads(self) -> "MLPPolicy":
+        """the plain network whose raw output is (mu | raw log_std): the two heads stacked as one output layer"""
+        return MLPPolicy(self.layers + [(np.concatenate([self.mu[0], self.log_std_head[0]]), np.concatenate([self.mu[1], self.log_std_head[1]]))],
+                         self.hidden_act, "none")
+
+    def heads_reference(self, obs) -> np.ndarray:
+        """float64 statement of dockauv_sac_actor_forward_rows: obs [..., n_in] -> [..., 2 n_out] = (mu | W_ls latent + b_ls), the
+        log-std head before its clamp."""
+        return self._both_heads().forward_reference(obs)
+
+    def backward_reference(self, obs, grad_out):
+        """float64 statement of dockauv_sac_actor_backward: obs [B, n_in], grad_out [B, 2 n_out] on ``heads_reference``.  Returns
+        (dW1, db1[, dW2, db2], dW_mu, db_mu, dW_ls, db_ls), summed over the rows, torch.nn.Linear layout."""
+        *hidden, dW, db = self._both_heads().backward_reference(obs, np.asarray(grad_out, dtype=np.float64).reshape(-1, 2 * self.n_out))
+        n = self.n_out
+        return tuple(hidden) + (dW[:n], db[:n], dW[n:], db[n:])
 
     def forward_float32(self, obs, z=None):
         """The kernel's epilogue expressions in float32 NumPy arrays (include/dockauv.h states them; the matrix products are

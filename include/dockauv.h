@@ -1120,9 +1120,11 @@ int dockauv_replay_state(dockauv_replay rb, float** storage, float** carry, long
  * SAC, the gradient-free half: what SB3 1.5's SAC computes under torch.no_grad() plus the actor that collect_rollouts queries
  * (train() with MODEL = SAC, SAC_HYPER_PARAMS_*) -- the squashed-Gaussian actor (sac.policies.Actor, use_sde = False), Q critics on
  * [obs | action] (ContinuousCritic) and the TD target of SAC.train -- on the tile body of the MLP actor.  Additive: calls that do
- * not use these objects queue exactly what they queued before.  The gradient half (dQ/da through the critic's first layer, the
- * actor and critic losses, ent_coef, the Polyak update) is not in the library; torch on raw tensors plus dockauv_policy_load /
- * dockauv_sac_actor_load serves until it is.  All pointers below are device pointers unless a descriptor says otherwise; every call
+ * not use these objects queue exactly what they queued before.  Of the gradient half the library has the networks' share, every
+ * matrix product (dockauv_sac_actor_forward_rows, dockauv_sac_actor_backward, dockauv_q_backward, at the end of this file).  What
+ * remains outside it: the loss head (the elementwise algebra of the actor, critic and ent_coef losses), ent_coef itself, the
+ * optimiser for these roles and the Polyak update; torch on small [B][n_u] tensors and on raw parameter tensors plus
+ * dockauv_policy_load / dockauv_sac_actor_load serves until they are.  All pointers below are device pointers unless a descriptor says otherwise; every call
  * is asynchronous on the stream and synchronises nothing.
  *
  * Widths stay <= DOCKAUV_POLICY_MAX_WIDTH (128), one or two hidden layers, tanh or ReLU hidden units.  SB3's SAC default
@@ -1233,6 +1235,88 @@ typedef struct dockauv_sac_target_io {
 } dockauv_sac_target_io;
 int dockauv_sac_target(dockauv_handle h, dockauv_policy actor, dockauv_policy q1_target, dockauv_policy q2_target,
                        const dockauv_sac_target_io* io, void* hip_stream);
+
+/*
+ * SAC, the networks' share of the gradient half: every matrix product of SAC.train's three backward passes.  What stays with the
+ * learner is elementwise algebra on [B][n_u] tensors (the clamp's mask, exp, tanh and the log-probability of the actor's sample;
+ * the three losses) and, until later calls exist, the optimiser and the Polyak update.  All pointers are device pointers, float32
+ * (row_index: int64); every call is asynchronous on the stream and synchronises nothing; every refusal is DOCKAUV_E_INVALID
+ * with the field named, before any device call.  Each call takes its own role only and refuses the three others by name;
+ * dockauv_policy_forward_rows and dockauv_policy_backward go on refusing both SAC roles.
+ *
+ * dockauv_sac_actor_forward_rows: with r = row_index ? row_index[i] : i and the observation row at rows + r * row_stride
+ * (row_stride >= n_obs; pointer, stride and index are free, so the replay ring serves as it stands), for i < n_rows
+ *   out[i][0 .. n_u) = mu,   out[i][n_u .. 2 n_u) = W_ls latent + b_ls, the log-std head BEFORE the clamp to [-20, 2]
+ * without noise and without tanh: the actor's tile body with another epilogue.  Held bit for bit: the mu columns are
+ * dockauv_policy_forward_rows of a plain policy with the same hidden layers and W3 = W_mu, b3 = b_mu, the log-std columns those of
+ * one with W3 = W_ls, b3 = b_ls -- each unit is one accumulator chain from its bias.
+ */
+typedef struct dockauv_sac_rows_io {
+    uint32_t struct_size;          /* sizeof(dockauv_sac_rows_io): ABI check */
+    int32_t row_stride;            /* floats between observation rows, >= n_obs */
+    const float* rows;
+    const int64_t* row_index;      /* nullable [n_rows] */
+    long long n_rows;              /* >= 1 */
+    float* out;                    /* [n_rows][2 n_u] */
+} dockauv_sac_rows_io;
+int dockauv_sac_actor_forward_rows(dockauv_handle h, dockauv_policy actor, const dockauv_sac_rows_io* io, void* hip_stream);
+
+/*
+ * dockauv_sac_actor_backward: the contract of dockauv_policy_backward -- the sums over the rows, the activation derivatives, the
+ * reproducibility (no floating-point atomics; two calls give the same bits; rows reached through row_index give the bits of the
+ * same rows laid out densely in that order), the library's partial sums (allocated at the first backward of the actor, freed by
+ * dockauv_policy_destroy; later calls allocate nothing), two launches -- with grad_out [n_rows][2 n_u] = dL/d(out), out as
+ * dockauv_sac_actor_forward_rows defines it: columns 0 .. n_u - 1 act on mu, n_u .. 2 n_u - 1 on the raw log-std head.  The clamp's
+ * mask (no gradient where the raw value lies outside [-20, 2]) belongs to the head and so to the caller, which has the raw values.
+ * Written, torch.nn.Linear layout, overwritten: dW1 db1 [dW2 db2] of latent_pi, dW_mu db_mu, dW_ls db_ls; a head whose columns of
+ * grad_out are all zero gets exact zeros.  The observation rows come through rows / row_stride / row_index as above.  LDS: the
+ * kernel of dockauv_policy_backward with 16 rows of output weights and upstream gradients where that has 8: a 36-128-128 actor
+ * needs 151 824 B of the 160 KiB; shapes beyond are refused with a message that names the need and the shape.
+ */
+typedef struct dockauv_sac_actor_backward_io {
+    uint32_t struct_size;          /* sizeof(dockauv_sac_actor_backward_io): ABI check */
+    int32_t row_stride;            /* floats between observation rows, >= n_obs */
+    const float* rows;
+    const int64_t* row_index;      /* nullable [n_rows] */
+    long long n_rows;              /* >= 1 */
+    const float* grad_out;         /* [n_rows][2 n_u] */
+    float *dW1, *db1, *dW2, *db2;  /* dW2 / db2 NULL with one hidden layer */
+    float *dW_mu, *db_mu, *dW_ls, *db_ls;
+} dockauv_sac_actor_backward_io;
+int dockauv_sac_actor_backward(dockauv_handle h, dockauv_policy actor, const dockauv_sac_actor_backward_io* io, void* hip_stream);
+
+/*
+ * dockauv_q_backward: a Q critic's backward for grad_q [n_rows] = dL/dq on the rows of dockauv_q_forward (obs, actions, two
+ * strides, one shared nullable index).  Two outputs, each nullable, at least one required:
+ *   grads         the parameter gradients, exactly what dockauv_policy_backward defines for x_r = [obs_r | a_r] (same contract,
+ *                 same partial sums -- the critic's own -- and the same two launches);
+ *   grad_actions  [n_rows][n_u]: grad_actions[i][j] = sum_u W1[u][n_obs + j] * delta1_u(i), dq/da of position i of the minibatch
+ *                 scaled by grad_q[i], float32, overwritten; nothing behind it is written.  One accumulator chain from 0 over
+ *                 the hidden units of layer 1 in order, two per step.
+ * With grads == NULL -- the actor loss, where the critic's own gradients are thrown away -- the call forms no parameter tile,
+ * touches no partial workspace (none is allocated by it) and queues no reduction: ONE launch.  Its grad_actions has the bits of
+ * the call that also asks for parameters, which queues that same launch behind its two (SAC asks for one output at a time:
+ * parameters on the replayed actions, grad_actions on the actor's).  Same reproducibility as above.  LDS as dockauv_policy_backward for n_in = n_obs + n_u:
+ * 44-128-128 needs 151 792 B; shapes beyond the 160 KiB are refused with a message that names the need and the shape.
+ */
+typedef struct dockauv_q_backward_io {
+    uint32_t struct_size;          /* sizeof(dockauv_q_backward_io): ABI check */
+    int32_t obs_stride;            /* floats between observation rows, >= n_obs */
+    int32_t act_stride;            /* floats between action rows, >= n_u */
+    int32_t reserved;
+    const float* obs;
+    const float* actions;
+    const int64_t* row_index;      /* nullable [n_rows] */
+    long long n_rows;              /* >= 1 */
+    const float* grad_q;           /* [n_rows] */
+    const dockauv_policy_grads* grads;   /* nullable */
+    float* grad_actions;           /* nullable [n_rows][n_u] */
+} dockauv_q_backward_io;
+int dockauv_q_backward(dockauv_handle h, dockauv_policy critic, const dockauv_q_backward_io* io, void* hip_stream);
+/* The partial-sum workspace of a policy's backward calls and its size in floats: NULL and 0 until the first backward with
+ * parameter gradients (dockauv_policy_backward, dockauv_sac_actor_backward, dockauv_q_backward with grads) allocates it.  Read-only
+ * bookkeeping, no device call. */
+int dockauv_policy_backward_workspace(dockauv_policy p, float** partial, long long* n_floats);
 
 #ifdef __cplusplus
 }
