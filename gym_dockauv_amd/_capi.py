@@ -271,6 +271,40 @@ class QBackwardIO(C.Structure):
     ]
 
 
+class SacSampleIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved", C.c_int32),
+        ("heads", C.c_void_p), ("n_rows", C.c_longlong), ("t", C.c_uint64), ("row_offset", C.c_uint64),
+        ("a", C.c_void_p), ("logp", C.c_void_p),
+    ]
+
+
+class SacCriticHeadIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved", C.c_int32),
+        ("q1", C.c_void_p), ("q2", C.c_void_p), ("y", C.c_void_p), ("n_rows", C.c_longlong),
+        ("grad_q1", C.c_void_p), ("grad_q2", C.c_void_p), ("stats", C.c_void_p),
+    ]
+
+
+class SacActorHeadIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("ent_coef", C.c_float),
+        ("heads", C.c_void_p), ("q1_pi", C.c_void_p), ("q2_pi", C.c_void_p), ("dq1", C.c_void_p), ("dq2", C.c_void_p),
+        ("log_ent_coef", C.c_void_p), ("n_rows", C.c_longlong), ("t", C.c_uint64), ("row_offset", C.c_uint64),
+        ("grad_out", C.c_void_p), ("stats", C.c_void_p),
+    ]
+
+
+class SacEntCoefIO(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("target_entropy", C.c_float),
+        ("state", C.c_void_p), ("logp", C.c_void_p), ("n_rows", C.c_longlong), ("step", C.c_longlong),
+        ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+        ("before", C.c_void_p), ("stats", C.c_void_p),
+    ]
+
+
 # every symbol include/dockauv.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("dockauv_abi_version", C.c_int, []),
@@ -366,6 +400,11 @@ SYMBOLS = [
     ("dockauv_sac_actor_backward", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SacActorBackwardIO), C.c_void_p]),
     ("dockauv_q_backward", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QBackwardIO), C.c_void_p]),
     ("dockauv_policy_backward_workspace", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]),
+    # (SAC's loss head and the learned entropy coefficient)
+    ("dockauv_sac_sample", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SacSampleIO), C.c_void_p]),
+    ("dockauv_sac_critic_head", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SacCriticHeadIO), C.c_void_p]),
+    ("dockauv_sac_actor_head", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SacActorHeadIO), C.c_void_p]),
+    ("dockauv_sac_ent_coef_step", C.c_int, [C.c_void_p, C.POINTER(SacEntCoefIO), C.c_void_p]),
     ("dockauv_replay_create", C.c_int, [C.c_void_p, C.c_longlong, C.c_uint64, C.POINTER(C.c_void_p)]),
     ("dockauv_replay_destroy", C.c_int, [C.c_void_p]),
     ("dockauv_replay_sync", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,6 +1,6 @@
 // dockauv_capi_policy.hip -- C ABI of libdockauv.so (include/dockauv.h), second part: MLP policy and critic, closed-loop
-// rollout, PPO collector, backward, head, optimiser, episode monitor and reward normaliser, and (at the end) SAC's forward half and its networks' gradients.
-// The kernels are in dockauv_policy / _collect / _backward / _head / _optim / _monitor / _update / _rewnorm / _sac.hip.
+// rollout, PPO collector, backward, head, optimiser, episode monitor and reward normaliser, and (at the end) SAC's forward half, its networks' gradients and its loss head.
+// The kernels are in dockauv_policy / _collect / _backward / _head / _optim / _monitor / _update / _rewnorm / _sac / _sac_head.hip.
 #include <cmath>
 #include <cstring>
 
@@ -1577,6 +1577,162 @@ int dockauv_policy_backward_workspace(dockauv_policy p, float** partial, long lo
     else backward_layout(p->S, L);
     if (partial) *partial = p->bwd_partial;
     if (n_floats) *n_floats = p->bwd_partial ? (long long)kBwdMaxGroups * L.n_params : 0;
+    return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ SAC: the loss head (dockauv_sac_head.hip)
+namespace {
+
+// do the float arrays [a, a + na) and [b, b + nb) share a byte?
+bool floats_overlap(const float* a, long long na, const float* b, long long nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + (uintptr_t)nb * sizeof(float) && b0 < a0 + (uintptr_t)na * sizeof(float);
+}
+
+struct FloatSpan {
+    const char* name;
+    const float* p;
+    long long n;
+};
+
+// every output against every input and against the outputs behind it; the first pair that overlaps is named
+int refuse_overlap(dockauv_handle h, const char* io_name, const FloatSpan* out, int n_out, const FloatSpan* in, int n_in) {
+    for (int i = 0; i < n_out; ++i) {
+        for (int k = 0; k < n_in; ++k)
+            if (in[k].p && floats_overlap(out[i].p, out[i].n, in[k].p, in[k].n))
+                return fail(h, DOCKAUV_E_INVALID, "%s.%s overlaps %s: outputs must not alias inputs", io_name, out[i].name, in[k].name);
+        for (int k = i + 1; k < n_out; ++k)
+            if (floats_overlap(out[i].p, out[i].n, out[k].p, out[k].n))
+                return fail(h, DOCKAUV_E_INVALID, "%s.%s overlaps %s: outputs must not alias one another", io_name, out[i].name, out[k].name);
+    }
+    return 0;
+}
+
+// the actor head's arrays for n_u actions a row (n_u = 1 before the handle is known: every array is at least that long)
+int refuse_actor_head_overlap(dockauv_handle h, const dockauv_sac_actor_head_io* io, int n_u) {
+    const long long B = io->n_rows;
+    const FloatSpan out[2] = {{"grad_out", io->grad_out, 2 * B * n_u}, {"stats", io->stats, 4}};
+    const FloatSpan in[6] = {{"heads", io->heads, 2 * B * n_u}, {"q1_pi", io->q1_pi, B}, {"q2_pi", io->q2_pi, B}, {"dq1", io->dq1, B * n_u},
+                             {"dq2", io->dq2, B * n_u}, {"log_ent_coef", io->log_ent_coef, 1}};
+    return refuse_overlap(h, "dockauv_sac_actor_head_io", out, 2, in, 6);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dockauv_sac_sample(dockauv_handle h, dockauv_policy actor, const dockauv_sac_sample_io* io, void* hip_stream) {
+    const char* fn = "dockauv_sac_sample";
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "%s: io is NULL", fn);
+    if (io->struct_size != sizeof(dockauv_sac_sample_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_sample_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_sac_sample_io));
+    if (io->n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_sample_io.n_rows: %lld must be >= 1", io->n_rows);
+    if (!io->heads) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_sample_io.heads is NULL");
+    if (!io->a) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_sample_io.a is NULL");
+    if (!io->logp) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_sample_io.logp is NULL");
+    if (!actor) return fail(h, DOCKAUV_E_INVALID, "%s: null actor", fn);
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
+    if (int rc = check_sac_role(h, actor, fn, true)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const SacSampleLaunch l{io->heads, io->a, io->logp, (long)io->n_rows, actor->S.n_out, (unsigned int)(io->t & 0xffffffffull),
+                            (unsigned int)(io->row_offset & 0xffffffffull), actor->seed};
+    const int rc = launch_sac_sample(l, hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "SAC sample kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
+    return 0;
+}
+
+int dockauv_sac_critic_head(dockauv_handle h, dockauv_policy q1_critic, const dockauv_sac_critic_head_io* io, void* hip_stream) {
+    const char* fn = "dockauv_sac_critic_head";
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "%s: io is NULL", fn);
+    if (io->struct_size != sizeof(dockauv_sac_critic_head_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_critic_head_io.struct_size: got %u, library has %zu", io->struct_size,
+                    sizeof(dockauv_sac_critic_head_io));
+    if (io->n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_critic_head_io.n_rows: %lld must be >= 1", io->n_rows);
+    if (!io->q1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_critic_head_io.q1 is NULL");
+    if (!io->q2) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_critic_head_io.q2 is NULL");
+    if (!io->y) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_critic_head_io.y is NULL");
+    if (!io->grad_q1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_critic_head_io.grad_q1 is NULL");
+    if (!io->grad_q2) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_critic_head_io.grad_q2 is NULL");
+    if (!io->stats) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_critic_head_io.stats is NULL");
+    const long long B = io->n_rows;
+    const FloatSpan out[3] = {{"grad_q1", io->grad_q1, B}, {"grad_q2", io->grad_q2, B}, {"stats", io->stats, 6}};
+    const FloatSpan in[3] = {{"q1", io->q1, B}, {"q2", io->q2, B}, {"y", io->y, B}};
+    if (int rc = refuse_overlap(h, "dockauv_sac_critic_head_io", out, 3, in, 3)) return rc;
+    if (!q1_critic) return fail(h, DOCKAUV_E_INVALID, "%s: null critic", fn);
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
+    if (int rc = check_sac_role(h, q1_critic, fn, false)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const SacCriticHeadLaunch l{io->q1, io->q2, io->y, io->grad_q1, io->grad_q2, io->stats, (long)B};
+    const int rc = launch_sac_critic_head(l, hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "SAC critic head kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
+    return 0;
+}
+
+int dockauv_sac_actor_head(dockauv_handle h, dockauv_policy actor, const dockauv_sac_actor_head_io* io, void* hip_stream) {
+    const char* fn = "dockauv_sac_actor_head";
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "%s: io is NULL", fn);
+    if (io->struct_size != sizeof(dockauv_sac_actor_head_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_head_io.struct_size: got %u, library has %zu", io->struct_size,
+                    sizeof(dockauv_sac_actor_head_io));
+    if (io->n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_head_io.n_rows: %lld must be >= 1", io->n_rows);
+    if (!io->log_ent_coef && std::isnan(io->ent_coef))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_head_io.ent_coef is NaN (and log_ent_coef is NULL)");
+    if (!io->heads) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_head_io.heads is NULL");
+    if (!io->q1_pi) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_head_io.q1_pi is NULL");
+    if (!io->q2_pi) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_head_io.q2_pi is NULL");
+    if (!io->dq1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_head_io.dq1 is NULL");
+    if (!io->dq2) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_head_io.dq2 is NULL");
+    if (!io->grad_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_head_io.grad_out is NULL");
+    if (!io->stats) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_actor_head_io.stats is NULL");
+    if (int rc = refuse_actor_head_overlap(h, io, 1)) return rc;
+    if (!actor) return fail(h, DOCKAUV_E_INVALID, "%s: null actor", fn);
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
+    if (int rc = check_sac_role(h, actor, fn, true)) return rc;
+    if (int rc = refuse_actor_head_overlap(h, io, actor->S.n_out)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const SacActorHeadLaunch l{io->heads, io->q1_pi, io->q2_pi, io->dq1, io->dq2, io->log_ent_coef, io->grad_out, io->stats, (long)io->n_rows,
+                               actor->S.n_out, (unsigned int)(io->t & 0xffffffffull), (unsigned int)(io->row_offset & 0xffffffffull),
+                               actor->seed, io->ent_coef};
+    const int rc = launch_sac_actor_head(l, hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "SAC actor head kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
+    return 0;
+}
+
+int dockauv_sac_ent_coef_step(dockauv_handle h, const dockauv_sac_ent_coef_io* io, void* hip_stream) {
+    const char* fn = "dockauv_sac_ent_coef_step";
+    if (!io) return fail(h, DOCKAUV_E_INVALID, "%s: io is NULL", fn);
+    if (io->struct_size != sizeof(dockauv_sac_ent_coef_io))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_ent_coef_io.struct_size: got %u, library has %zu", io->struct_size,
+                    sizeof(dockauv_sac_ent_coef_io));
+    if (io->n_rows < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_ent_coef_io.n_rows: %lld must be >= 1", io->n_rows);
+    if (io->step < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_ent_coef_io.step: %lld must be >= 1 (the caller's count of this step)", io->step);
+    if (!(io->lr >= 0.0) || !std::isfinite(io->lr)) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_ent_coef_io.lr: %g must be finite and >= 0", io->lr);
+    if (!(io->beta1 >= 0.0 && io->beta1 < 1.0)) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_ent_coef_io.beta1: %g outside [0, 1)", io->beta1);
+    if (!(io->beta2 >= 0.0 && io->beta2 < 1.0)) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_ent_coef_io.beta2: %g outside [0, 1)", io->beta2);
+    if (!(io->eps > 0.0)) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_ent_coef_io.eps: %g must be > 0", io->eps);
+    if (!io->state) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_ent_coef_io.state is NULL");
+    if (!io->logp) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_ent_coef_io.logp is NULL");
+    if (io->before && floats_overlap(io->before, 1, io->state, 3))
+        return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_ent_coef_io.before overlaps state: it receives the value from before the step");
+    if (io->stats && floats_overlap(io->stats, 4, io->state, 3)) return fail(h, DOCKAUV_E_INVALID, "dockauv_sac_ent_coef_io.stats overlaps state");
+    if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "%s: null handle", fn);
+    HIP_TRY(h, hipSetDevice(h->device));
+    // step's scalars in double, rounded once (include/dockauv.h: dockauv_optim_step)
+    EntCoefLaunch l{io->state, io->logp, io->before, io->stats, (long)io->n_rows, io->target_entropy};
+    l.c1 = (float)(1.0 - io->beta1);
+    l.c2 = (float)(1.0 - io->beta2);
+    l.b2 = (float)io->beta2;
+    l.step_size = (float)(io->lr / (1.0 - std::pow(io->beta1, (double)io->step)));
+    l.rsq = (float)(1.0 / std::sqrt(1.0 - std::pow(io->beta2, (double)io->step)));
+    l.eps = (float)io->eps;
+    const int rc = launch_ent_coef_step(l, hip_stream);
+    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "ent_coef step kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    h->last_stream = (hipStream_t)hip_stream;
     return 0;
 }
 

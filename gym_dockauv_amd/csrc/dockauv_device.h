@@ -687,6 +687,51 @@ int launch_q_backward(const PolicyShape& s, const float* packed, const SacBackwa
 int launch_sac_actor_heads(const PolicyShape& s, const float* packed, const float* rows, const long long* row_index, long n,
                            int row_stride, float* out, void* stream);
 
+// ------------------------------------------------------------------------------------------ SAC loss head (dockauv_sac_head.hip)
+// What lies between SAC's forward calls and its backward calls, and the learned entropy coefficient (include/dockauv.h:
+// dockauv_sac_sample, dockauv_sac_critic_head, dockauv_sac_actor_head, dockauv_sac_ent_coef_step state the arithmetic).  The sample
+// is elementwise on groups of kSacSampleThreads rows; each of the three calls with sums is ONE group of kSacHeadThreads lanes
+// (lane t takes the rows t, t + kSacHeadThreads, ..; float64 sums, a fixed tree in the wave, the waves in order) and needs no
+// workspace.  One launch each.  Every launcher returns a hipError_t as int.
+constexpr int kSacSampleThreads = 256;
+constexpr int kSacHeadThreads = 1024;
+struct SacSampleLaunch {
+    const float* heads;                   // [n][2 n_u]: mu | raw log-std
+    float *a, *logp;                      // [n][n_u], [n]
+    long n;
+    int n_u;
+    unsigned int t_lo, row_off_lo;        // the normal of (row i, j): Philox counter (row_off_lo + i, t_lo, j, 5)
+    unsigned long long seed;
+};
+int launch_sac_sample(const SacSampleLaunch& a, void* stream);
+struct SacCriticHeadLaunch {
+    const float *q1, *q2, *y;             // [n]
+    float *grad_q1, *grad_q2, *stats;     // [n], [n], [6]
+    long n;
+};
+int launch_sac_critic_head(const SacCriticHeadLaunch& a, void* stream);
+struct SacActorHeadLaunch {
+    const float* heads;                   // [n][2 n_u]
+    const float *q1_pi, *q2_pi, *dq1, *dq2;   // [n], [n], [n][n_u], [n][n_u]
+    const float* log_ent_coef;            // nullable device scalar
+    float *grad_out, *stats;              // [n][2 n_u], [4]
+    long n;
+    int n_u;
+    unsigned int t_lo, row_off_lo;
+    unsigned long long seed;
+    float ent_coef;
+};
+int launch_sac_actor_head(const SacActorHeadLaunch& a, void* stream);
+struct EntCoefLaunch {
+    float* state;                         // [3]: log_ent_coef, m, v
+    const float* logp;                    // [n]
+    float *before, *stats;                // nullable: one float, [4]
+    long n;
+    float target_entropy;
+    float c1, c2, b2, step_size, rsq, eps;   // host scalars of this step (dockauv_optim_step's)
+};
+int launch_ent_coef_step(const EntCoefLaunch& a, void* stream);
+
 // ------------------------------------------------------------------------------------------ GAE (dockauv_collect.hip)
 // SB3's compute_returns_and_advantage over packed rows: rows [K][N][row_stride] with the reward in column n_obs and done in
 // column n_obs + 1 (the observation columns are never read), values [K + 1][N], advantages / returns [K][N]; one lane per

@@ -736,6 +736,62 @@ class BatchedDocking3d:
         _capi.check(self._lib, self._handle, rc, "dockauv_policy_backward_workspace")
         return int(ptr.value or 0), int(n.value)
 
+    def sac_sample_device(self, actor, heads_ptr: int, n_rows: int, a_ptr: int, logp_ptr: int, t: int = 0, row_offset: int = 0,
+                          stream: int = 0) -> None:
+        """a float32 [n_rows][n_u] and logp [n_rows] of the squashed-Gaussian actor's sample from heads float32 [n_rows][2 n_u]
+        (``sac_actor_forward_rows_device``'s output) with the rows-form normals of counter (row_offset + i, t, j, 5): one launch
+        (dockauv_sac_sample); the bits of ``sac_target_device``'s a2 / logp2 for the same rows, t and row_offset."""
+        io = _capi.SacSampleIO()
+        io.struct_size = C.sizeof(_capi.SacSampleIO)
+        io.heads, io.n_rows, io.a, io.logp = heads_ptr or None, int(n_rows), a_ptr or None, logp_ptr or None
+        io.t, io.row_offset = int(t) & (2 ** 64 - 1), int(row_offset) & (2 ** 64 - 1)
+        rc = self._lib.dockauv_sac_sample(self._handle, actor.ptr, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_sac_sample")
+
+    def sac_critic_head_device(self, q1_critic, q1_ptr: int, q2_ptr: int, y_ptr: int, n_rows: int, grad_q1_ptr: int, grad_q2_ptr: int,
+                               stats_ptr: int, stream: int = 0) -> None:
+        """SAC's critic loss 0.5 (mse(q1, y) + mse(q2, y)) on float32 [n_rows] arrays: grad_q1 / grad_q2 [n_rows] = (q_k - y) /
+        n_rows -- what ``q_backward_device`` takes -- and stats float32 [6] = (critic_loss, mse1, mse2, mean q1, mean q2, mean y):
+        one launch (dockauv_sac_critic_head)."""
+        io = _capi.SacCriticHeadIO()
+        io.struct_size = C.sizeof(_capi.SacCriticHeadIO)
+        io.q1, io.q2, io.y, io.n_rows = q1_ptr or None, q2_ptr or None, y_ptr or None, int(n_rows)
+        io.grad_q1, io.grad_q2, io.stats = grad_q1_ptr or None, grad_q2_ptr or None, stats_ptr or None
+        rc = self._lib.dockauv_sac_critic_head(self._handle, q1_critic.ptr, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_sac_critic_head")
+
+    def sac_actor_head_device(self, actor, heads_ptr: int, q1_pi_ptr: int, q2_pi_ptr: int, dq1_ptr: int, dq2_ptr: int, n_rows: int,
+                              grad_out_ptr: int, stats_ptr: int, ent_coef: float = 0.0, log_ent_coef_ptr: int = 0, t: int = 0,
+                              row_offset: int = 0, stream: int = 0) -> None:
+        """SAC's actor loss mean(alpha logp - min(q1_pi, q2_pi)) for the draw (t, row_offset) of ``sac_sample_device`` on heads:
+        grad_out float32 [n_rows][2 n_u] on (mu | raw log-std) with the clamp's mask applied -- what ``sac_actor_backward_device``
+        takes -- and stats float32 [4] = (actor_loss, mean logp, mean min q, alpha); q1_pi / q2_pi [n_rows] the critics at the
+        sampled action, dq1 / dq2 [n_rows][n_u] their dq/da; alpha = ``ent_coef`` or exp of the device scalar at
+        ``log_ent_coef_ptr``: one launch (dockauv_sac_actor_head)."""
+        io = _capi.SacActorHeadIO()
+        io.struct_size = C.sizeof(_capi.SacActorHeadIO)
+        io.ent_coef, io.log_ent_coef = float(ent_coef), log_ent_coef_ptr or None
+        io.heads, io.q1_pi, io.q2_pi, io.dq1, io.dq2 = heads_ptr or None, q1_pi_ptr or None, q2_pi_ptr or None, dq1_ptr or None, dq2_ptr or None
+        io.n_rows, io.t, io.row_offset = int(n_rows), int(t) & (2 ** 64 - 1), int(row_offset) & (2 ** 64 - 1)
+        io.grad_out, io.stats = grad_out_ptr or None, stats_ptr or None
+        rc = self._lib.dockauv_sac_actor_head(self._handle, actor.ptr, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_sac_actor_head")
+
+    def sac_ent_coef_step_device(self, state_ptr: int, logp_ptr: int, n_rows: int, step: int, lr: float, target_entropy: float,
+                                 betas=(0.9, 0.999), eps: float = 1e-8, before_ptr: int = 0, stats_ptr: int = 0, stream: int = 0) -> None:
+        """One Adam step on the learned log_ent_coef for the gradient -mean(logp + target_entropy): state float32 [3] =
+        (log_ent_coef, m, v) updated in place, ``step`` the caller's count from 1; ``before_ptr`` (one float) receives log_ent_coef
+        as it was, ``stats_ptr`` float32 [4] = (ent_coef_loss, exp(log_ent_coef before), the mean, the new log_ent_coef): one
+        launch (dockauv_sac_ent_coef_step).  Not to be captured: the step's bias corrections travel in the kernel arguments."""
+        io = _capi.SacEntCoefIO()
+        io.struct_size = C.sizeof(_capi.SacEntCoefIO)
+        io.target_entropy, io.state, io.logp = float(target_entropy), state_ptr or None, logp_ptr or None
+        io.n_rows, io.step, io.lr = int(n_rows), int(step), float(lr)
+        io.beta1, io.beta2, io.eps = float(betas[0]), float(betas[1]), float(eps)
+        io.before, io.stats = before_ptr or None, stats_ptr or None
+        rc = self._lib.dockauv_sac_ent_coef_step(self._handle, C.byref(io), C.c_void_p(stream or None))
+        _capi.check(self._lib, self._handle, rc, "dockauv_sac_ent_coef_step")
+
     def sac_target_device(self, actor, q1_target, q2_target, next_obs_ptr: int, rewards_ptr: int, dones_ptr: int, n_rows: int,
                           gamma: float, a2_ptr: int, logp2_ptr: int, q1_ptr: int, q2_ptr: int, y_ptr: int, ent_coef: float = 0.0,
                           log_ent_coef_ptr: int = 0, t: int = 0, row_offset: int = 0, next_obs_stride: int = 0,

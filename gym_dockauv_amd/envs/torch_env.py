@@ -25,8 +25,10 @@ from ..config.env_config import BASE_CONFIG
 from .batched import BatchedDocking3d
 
 
+# what TorchDocking3d.sac_gradients returns: three tuples of gradient tensors, then views of buffers the env owns
+SacGradients = namedtuple("SacGradients", ["q1", "q2", "actor", "logp", "critic_stats", "actor_stats", "grad_out", "y"])
 # what TorchDocking3d.collect returns: views of buffers the env owns
-Collected = namedtuple("Collected", ["obs", "actions", "reward", "done", "log_prob", "values", "advantages", "returns"])
+Collected =namedtuple("Collected", ["obs", "actions", "reward", "done", "log_prob", "values", "advantages", "returns"])
 
 
 class TorchDocking3d:
@@ -340,6 +342,189 @@ class TorchDocking3d:
         if with_params:
             self.load_policy(critic, [p.detach() for p in ps])
         return _Apply.apply(actions, *ps)
+
+    # ------------------------------------------------------------------------------------------ SAC: the loss head
+    def _ent_coef_args(self, ent_coef, log_ent_coef):
+        """(ent_coef as a float, device address of log_ent_coef or 0): exactly one of the two is given"""
+        torch = self.torch
+        if (ent_coef is None) == (log_ent_coef is None):
+            raise ValueError("give either ent_coef or log_ent_coef")
+        if log_ent_coef is not None and (log_ent_coef.device != self.device or log_ent_coef.dtype != torch.float32 or log_ent_coef.numel() != 1):
+            raise ValueError(f"log_ent_coef must be a float32 tensor of one element on {self.device}")
+        return (0.0 if ent_coef is None else float(ent_coef)), (0 if log_ent_coef is None else log_ent_coef.data_ptr())
+
+    def sac_sample(self, actor, heads, t: int, row_offset: int = 0):
+        """(a [B, n_u], logp [B]) float32, fresh tensors: the squashed-Gaussian actor's sample from ``heads`` [B, 2 n_u]
+        (``sac_actor_heads``) with the rows-form normals of counter (row_offset + i, t, j, 5), one launch on the current stream
+        (dockauv_sac_sample).  For the same rows, ``t`` and ``row_offset`` these are ``sac_target``'s a2 and logp2 bit for bit; a
+        learner gives the actor loss's draw another ``t`` than the target's draw of the same gradient step."""
+        torch = self.torch
+        B = int(heads.shape[0]) if heads.dim() == 2 else 0
+        self._grad_out_ok(heads, (B, 2 * self.n_u), "heads")
+        a = torch.empty((B, self.n_u), device=self.device, dtype=torch.float32)
+        logp = torch.empty((B,), device=self.device, dtype=torch.float32)
+        self.batch.sac_sample_device(actor, heads.data_ptr(), B, a.data_ptr(), logp.data_ptr(), t=int(t), row_offset=int(row_offset),
+                                     stream=torch.cuda.current_stream().cuda_stream)
+        return a, logp
+
+    def sac_critic_head(self, q1_critic, q1, q2, y):
+        """(grad_q1 [B], grad_q2 [B], stats [6]) float32, fresh tensors: SB3's critic_loss = 0.5 (mse(q1, y) + mse(q2, y)) on
+        ``q1``, ``q2`` = ``q_values`` of the two critics on the replayed actions and ``y`` = ``sac_target``; grad_q_k = (q_k - y) / B
+        is what ``q_backward`` takes; stats = (critic_loss, mse1, mse2, mean q1, mean q2, mean y).  One launch on the current
+        stream (dockauv_sac_critic_head); ``q1_critic``: a ``make_q`` critic of this env."""
+        torch = self.torch
+        B = int(q1.numel())
+        for x, what in ((q1, "q1"), (q2, "q2"), (y, "y")):
+            self._grad_out_ok(x.view(-1) if x.is_contiguous() else x, (B,), what)
+        g1, g2 = (torch.empty((B,), device=self.device, dtype=torch.float32) for _ in range(2))
+        stats = torch.empty((6,), device=self.device, dtype=torch.float32)
+        self.batch.sac_critic_head_device(q1_critic, q1.data_ptr(), q2.data_ptr(), y.data_ptr(), B, g1.data_ptr(), g2.data_ptr(),
+                                          stats.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+        return g1, g2, stats
+
+    def sac_actor_head(self, actor, heads, t: int, q1_pi, q2_pi, dq1, dq2, ent_coef=None, log_ent_coef=None, row_offset: int = 0):
+        """(grad_out [B, 2 n_u], stats [4]) float32, fresh tensors: SB3's actor_loss = mean(alpha logp - min(q1_pi, q2_pi)) for
+        the draw (``t``, ``row_offset``) of ``sac_sample`` on ``heads``.  ``q1_pi``, ``q2_pi`` [B] = ``q_values`` at the sampled
+        action; ``dq1``, ``dq2`` [B, n_u] = ``q_backward(.., grad_q=ones, params=False, grad_actions=True)``, pure dq/da.
+        grad_out is d actor_loss / d heads with the clamp's mask applied -- what ``sac_actor_backward`` takes; stats =
+        (actor_loss, mean logp, mean min q, alpha).  alpha: ``ent_coef`` (a float) or ``log_ent_coef`` (a float32 device tensor of
+        one element).  One launch on the current stream (dockauv_sac_actor_head)."""
+        torch = self.torch
+        ec, lec = self._ent_coef_args(ent_coef, log_ent_coef)
+        B = int(heads.shape[0]) if heads.dim() == 2 else 0
+        self._grad_out_ok(heads, (B, 2 * self.n_u), "heads")
+        for x, shape, what in ((q1_pi, (B,), "q1_pi"), (q2_pi, (B,), "q2_pi"), (dq1, (B, self.n_u), "dq1"), (dq2, (B, self.n_u), "dq2")):
+            self._grad_out_ok(x, shape, what)
+        grad_out = torch.empty((B, 2 * self.n_u), device=self.device, dtype=torch.float32)
+        stats = torch.empty((4,), device=self.device, dtype=torch.float32)
+        self.batch.sac_actor_head_device(actor, heads.data_ptr(), q1_pi.data_ptr(), q2_pi.data_ptr(), dq1.data_ptr(), dq2.data_ptr(), B,
+                                         grad_out.data_ptr(), stats.data_ptr(), ent_coef=ec, log_ent_coef_ptr=lec, t=int(t),
+                                         row_offset=int(row_offset), stream=torch.cuda.current_stream().cuda_stream)
+        return grad_out, stats
+
+    def ent_coef_state(self, init: float = 1.0):
+        """The learned entropy coefficient's state, a float32 [3] device tensor (log_ent_coef, m, v) = (log(init), 0, 0); SB3's
+        ent_coef="auto" is init = 1, "auto_0.1" init = 0.1.  ``state[:1]`` is the ``log_ent_coef`` the other calls take."""
+        import math
+        if not float(init) > 0.0:
+            raise ValueError("init must be > 0")
+        return self.torch.tensor([math.log(float(init)), 0.0, 0.0], dtype=self.torch.float32, device=self.device)
+
+    def ent_coef_step(self, state, logp, step: int, lr: float, target_entropy=None, betas=(0.9, 0.999), eps: float = 1e-8, before=None):
+        """One Adam step of SB3's ent_coef_loss = -(log_ent_coef * (logp + target_entropy)).mean() on ``state`` (``ent_coef_state``),
+        in place, one launch on the current stream (dockauv_sac_ent_coef_step).  ``step``: the caller's count of this step, from 1;
+        ``target_entropy``: default -n_u (SB3's "auto"); ``before``: a float32 device tensor of one element that receives
+        log_ent_coef as it was -- SB3 evaluates the target and the actor loss at the coefficient from before the step, so that
+        is the ``log_ent_coef`` to hand them when the step is queued first.  Returns stats, a fresh float32 [4] = (ent_coef_loss,
+        exp(log_ent_coef before), mean(logp + target_entropy), the new log_ent_coef).  Not to be captured in a graph."""
+        torch = self.torch
+        self._grad_out_ok(state, (3,), "state")
+        B = int(logp.numel())
+        self._grad_out_ok(logp, (B,), "logp")
+        if before is not None and (before.device != self.device or before.dtype != torch.float32 or before.numel() != 1):
+            raise ValueError(f"before must be a float32 tensor of one element on {self.device}")
+        stats = torch.empty((4,), device=self.device, dtype=torch.float32)
+        self.batch.sac_ent_coef_step_device(state.data_ptr(), logp.data_ptr(), B, int(step), float(lr),
+                                            float(-self.n_u if target_entropy is None else target_entropy), betas=betas, eps=eps,
+                                            before_ptr=0 if before is None else before.data_ptr(), stats_ptr=stats.data_ptr(),
+                                            stream=torch.cuda.current_stream().cuda_stream)
+        return stats
+
+    def sac_gradients(self, actor, q1, q2, q1_target, q2_target, samples_or_buffer, gamma: float, t: int, ent_coef=None,
+                      log_ent_coef=None, out=None):
+        """The whole gradient half of one SAC step on the current stream, with no torch arithmetic and no synchronisation:
+        every gradient of SB3 1.5's critic loss and actor loss on one minibatch, and the logp ``ent_coef_step`` takes.
+        ``samples_or_buffer``: as for ``sac_target`` -- the ``ReplaySamples`` of ``rb.sample(...)``, or the buffer itself after
+        ``rb.sample(..., want_index=True)``, then the rows are read from the ring through ``rb.index`` (but for the critics at the sampled action, which
+        read the sample's dense observations: the same rows).  Queued in this order:
+          1. heads = the actor's two heads on obs                                      1 launch
+          2. a, logp = the sample at counter t_pi = 2 t + 1                            1
+          3. y = ``sac_target`` at counter 2 t (its own draw on next_obs)              4
+          4. q1, q2 on the replayed actions                                            2
+          5. the critic head                                                           1
+          6. ``q_backward`` of both critics with parameters                            2 x 2
+          7. q1_pi, q2_pi at a                                                         2
+          8. dq1, dq2: ``q_backward`` without parameters on a cached buffer of ones    2
+          9. the actor head                                                            1
+         10. ``sac_actor_backward``                                                    2
+        20 launches.  All three losses are evaluated at the weights the networks hold at the call.  SB3 steps the critics'
+        optimiser before it evaluates q_pi for the actor loss; a learner who wants that order calls the pieces (``sac_target``,
+        ``q_values``, ``sac_critic_head``, ``q_backward``, then -- after its critic step and ``load_policy`` -- ``sac_sample``,
+        ``sac_actor_head``, ``sac_actor_backward``).  alpha: ``ent_coef`` or ``log_ent_coef`` as for ``sac_target``, used in the
+        target and in the actor loss.  ``out``: (q1 grads, q2 grads, actor grads), sequences of tensors to write into (as
+        ``q_backward`` / ``sac_actor_backward`` take them); None: fresh tensors.  Returns ``SacGradients(q1, q2, actor, logp,
+        critic_stats, actor_stats, grad_out, y)``: the three gradient tuples in torch.nn.Linear layout, logp [B], stats [6] and
+        [4] as ``sac_critic_head`` / ``sac_actor_head`` define them, the actor head's grad_out [B, 2 n_u] and the target y [B];
+        everything from logp on is a view of buffers the env owns and reuses for the same number of rows."""
+        torch = self.torch
+        ec, lec = self._ent_coef_args(ent_coef, log_ent_coef)
+        n_obs, n_u, st = self.n_obs, self.n_u, torch.cuda.current_stream().cuda_stream
+        if hasattr(samples_or_buffer, "storage"):
+            rb = samples_or_buffer
+            if rb.env is not self or rb.index is None:
+                raise ValueError("the buffer must be this env's, after rb.sample(..., want_index=True)")
+            n, R, base = self._index_ok(rb.index), rb.record_floats, rb.storage.data_ptr()
+            obs_ptr, act_ptr, obs_stride, act_stride, index_ptr = base, base + 4 * 2 * n_obs, R, R, rb.index.data_ptr()
+            # (the critics at the sampled action pair a ring row with a dense action row: dockauv_q_forward has one index for
+            # both, so those four launches read the sample's dense copy of the same observation rows)
+            dense_obs_ptr = rb.last_samples.observations.data_ptr()
+        else:
+            sm = samples_or_buffer
+            for x in (sm.observations, sm.actions):
+                if x.device != self.device or x.dtype != torch.float32 or not x.is_contiguous():
+                    raise ValueError(f"the samples must be contiguous float32 tensors on {self.device}")
+            n = int(sm.rewards.numel())
+            if sm.observations.numel() != n * n_obs or sm.actions.numel() != n * n_u:
+                raise ValueError("observations [.., n_obs] and actions [.., n_u] of the minibatch's shape")
+            obs_ptr, act_ptr, obs_stride, act_stride, index_ptr = sm.observations.data_ptr(), sm.actions.data_ptr(), n_obs, n_u, 0
+            dense_obs_ptr = obs_ptr
+        ws = getattr(self, "_sac_grad_bufs", None)
+        if ws is None:
+            ws = self._sac_grad_bufs = {}
+        b = ws.get(n)
+        if b is None:
+            e = lambda *sh: torch.empty(sh, device=self.device, dtype=torch.float32)
+            b = ws[n] = dict(heads=e(n, 2 * n_u), a=e(n, n_u), logp=e(n), q1=e(n), q2=e(n), grad_q1=e(n), grad_q2=e(n), q1_pi=e(n),
+                             q2_pi=e(n), dq1=e(n, n_u), dq2=e(n, n_u), grad_out=e(n, 2 * n_u), critic_stats=e(6), actor_stats=e(4),
+                             ones=torch.ones((n,), device=self.device, dtype=torch.float32))
+        p = {k: v.data_ptr() for k, v in b.items()}
+
+        def shapes(net, heads: int):
+            widths = [net.n_in] + net.n_hidden
+            s = [x for i in range(len(widths) - 1) for x in ((widths[i + 1], widths[i]), (widths[i + 1],))]
+            return s + [(net.n_out if heads == 2 else 1, widths[-1]), (net.n_out if heads == 2 else 1,)] * heads
+
+        def eight(grads, net):      # (the device calls take dW2 / db2 = 0 with one hidden layer)
+            ptrs = [g.data_ptr() for g in grads]
+            if len(net.n_hidden) == 1:
+                ptrs[2:2] = [0, 0]
+            return ptrs
+
+        out = (None, None, None) if out is None else tuple(out)
+        if len(out) != 3:
+            raise ValueError("out: (q1 grads, q2 grads, actor grads)")
+        g_q1, g_q2 = self._grad_arrays(shapes(q1, 1), out[0]), self._grad_arrays(shapes(q2, 1), out[1])
+        g_actor = self._grad_arrays(shapes(actor, 2), out[2])
+        bt = self.batch
+        bt.sac_actor_forward_rows_device(actor, obs_ptr, n, p["heads"], row_stride=obs_stride, index_ptr=index_ptr, stream=st)
+        bt.sac_sample_device(actor, p["heads"], n, p["a"], p["logp"], t=2 * int(t) + 1, stream=st)
+        self.sac_target(actor, q1_target, q2_target, samples_or_buffer, gamma, ent_coef=ent_coef, log_ent_coef=log_ent_coef, t=2 * int(t))
+        y_ptr = self.sac_buffers["y"].data_ptr()
+        for q, key in ((q1, "q1"), (q2, "q2")):
+            bt.q_forward_device(q, obs_ptr, act_ptr, n, p[key], obs_stride=obs_stride, act_stride=act_stride, index_ptr=index_ptr, stream=st)
+        bt.sac_critic_head_device(q1, p["q1"], p["q2"], y_ptr, n, p["grad_q1"], p["grad_q2"], p["critic_stats"], stream=st)
+        for q, key, grads in ((q1, "grad_q1", g_q1), (q2, "grad_q2", g_q2)):
+            bt.q_backward_device(q, obs_ptr, act_ptr, n, p[key], grad_ptrs=eight(grads, q), obs_stride=obs_stride, act_stride=act_stride,
+                                 index_ptr=index_ptr, stream=st)
+        for q, key in ((q1, "q1_pi"), (q2, "q2_pi")):
+            bt.q_forward_device(q, dense_obs_ptr, p["a"], n, p[key], stream=st)
+        for q, key in ((q1, "dq1"), (q2, "dq2")):
+            bt.q_backward_device(q, dense_obs_ptr, p["a"], n, p["ones"], grad_ptrs=None, grad_actions_ptr=p[key], stream=st)
+        bt.sac_actor_head_device(actor, p["heads"], p["q1_pi"], p["q2_pi"], p["dq1"], p["dq2"], n, p["grad_out"], p["actor_stats"],
+                                 ent_coef=ec, log_ent_coef_ptr=lec, t=2 * int(t) + 1, stream=st)
+        bt.sac_actor_backward_device(actor, obs_ptr, n, p["grad_out"], eight(g_actor, actor), row_stride=obs_stride, index_ptr=index_ptr, stream=st)
+        return SacGradients(tuple(g_q1), tuple(g_q2), tuple(g_actor), b["logp"], b["critic_stats"], b["actor_stats"], b["grad_out"],
+                            self.sac_buffers["y"])
 
     def _load_sac_actor(self, policy, module_or_tensors) -> None:
         torch = self.torch

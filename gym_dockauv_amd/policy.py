@@ -7,7 +7,9 @@ is SB3's ``MlpPolicy``, which train.py:64 instantiates and train.py:64-71 / 86-1
 put it on the device.  An ``MLPPolicy`` with one raw output is a critic (SB3's ``mlp_extractor.value_net`` + ``value_net``;
 ``value_from_torch``, ``make_value``): the PPO collector (dockauv_collect) evaluates it on the rollout's rows.
 ``SquashedGaussianMLP`` is SAC's actor (two heads, a state-dependent log_std, tanh squashing; ``make_sac_actor``), an ``MLPPolicy``
-on [obs | action] with one raw output a Q critic (``make_q``); ``sac_target_reference`` states the TD target's last kernel.
+on [obs | action] with one raw output a Q critic (``make_q``); ``sac_target_reference`` states the TD target's last kernel,
+``sac_critic_head_reference``, ``sac_actor_head_reference`` and ``ent_coef_step_reference`` SAC's loss head in float64 (their
+``*_float32`` twins and ``normals_float32``: what float32 does to them, the tests' yardstick).
 ``forward_reference``, ``backward_reference``, ``normals_reference``, ``log_prob_reference``, ``gae_reference``,
 ``ppo_head_reference``, ``adam_reference`` and ``permutation_reference`` (exact integers) are float64
 NumPy statements of what the kernels compute (for tests and for callers who want to check a port); they are never used as a compute path.
@@ -335,6 +337,26 @@ class MLPPolicy:
         return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
 
     @staticmethod
+    def normals_float32(seed: int, env_ids, t: int, n_out: int, slot: int = 2) -> np.ndarray:
+        """The float32 restatement of the same draw, as the kernel forms it (dockauv_policy_tile.h: policy_normal_): u1 =
+        ((float)(x0 >> 8) + 0.5f) 2^-24 with the sum rounded to float32, u2 = (float)(x1 >> 8) 2^-24, z = sqrtf(-2 logf(u1))
+        cospif(2 u2), every operation in float32 NumPy (the cosine of the exactly reduced argument, rounded once).  Returns
+        float32 [len(env_ids), n_out]: the yardstick of what float32 does to ``normals_reference``, never a compute path."""
+        env = np.asarray(env_ids, dtype=np.uint64).reshape(-1) & _MASK
+        ctr = np.empty((env.size, n_out, 4), dtype=np.uint64)
+        ctr[..., 0] = env[:, None]
+        ctr[..., 1] = np.uint64(int(t) & 0xFFFFFFFF)
+        ctr[..., 2] = np.arange(n_out, dtype=np.uint64)[None, :]
+        ctr[..., 3] = np.uint64(int(slot))
+        x = _philox4x32_10(ctr, (int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF))
+        f = np.float32
+        u1 = ((x[..., 0] >> np.uint64(8)).astype(np.float32) + f(0.5)) * f(1.0 / 16777216.0)
+        u2 = (x[..., 1] >> np.uint64(8)).astype(np.float32) * f(1.0 / 16777216.0)
+        z = np.sqrt(f(-2.0) * np.log(u1)) * np.cos(np.pi * (f(2.0) * u2).astype(np.float64)).astype(np.float32)
+        assert z.dtype == np.float32
+        return z
+
+    @staticmethod
     def permutation_reference(seed: int, epoch: int, n: int) -> np.ndarray:
         """The exact statement of dockauv_permutation: int64 [n], out[i] = P(i) for the keyed bijection P of [0, n) -- an
         eight-round Feistel network on b = max(2, bit_length(n - 1)) bits (left half: the high b // 2 bits) whose round keys
@@ -427,6 +449,157 @@ def sac_target_reference(q1, q2, logp2, rewards, dones, gamma: float, ent_coef=N
     q1, q2, lp, r, d = f(q1), f(q2), f(logp2), f(rewards), f(dones)
     v = _fmaf(-alpha, lp, np.minimum(q1, q2))
     return _fmaf(_F32(gamma) * (_F32(1.0) - d), v, r)
+
+
+# ------------------------------------------------------------------------------------------ SAC: the loss head
+# float64 statements of dockauv_sac_critic_head, dockauv_sac_actor_head and dockauv_sac_ent_coef_step by SB3 1.5's formulas as they
+# are written, and their float32 NumPy restatements (include/dockauv.h's expressions through _fmaf and _F32): what float32 can do
+# on these expressions -- the yardstick of the device's error, never a compute path.
+def _mean32(x) -> np.float32:
+    """a float64 sum of float32 terms divided by their count, rounded once: how the head kernels form a mean"""
+    x = np.asarray(x)
+    assert x.dtype == np.float32
+    return _F32(x.astype(np.float64).sum() / x.size)
+
+
+def _alpha_of(ent_coef, log_ent_coef, f32: bool):
+    if (ent_coef is None) == (log_ent_coef is None):
+        raise ValueError("give either ent_coef or log_ent_coef")
+    if log_ent_coef is None:
+        return _F32(ent_coef) if f32 else float(_F32(ent_coef))
+    e = np.exp(np.float64(_F32(log_ent_coef)))
+    return _F32(e) if f32 else float(e)
+
+
+def sac_critic_head_reference(q1, q2, y):
+    """float64 statement of dockauv_sac_critic_head: SB3's critic_loss = 0.5 * sum_k mse_loss(q_k, y) on arrays [B].  Returns
+    (grad_q1, grad_q2, stats [6]) = d critic_loss / d q_k = (q_k - y) / B and (critic_loss, mse1, mse2, mean q1, mean q2, mean y)."""
+    q1, q2, y = (np.asarray(x, dtype=np.float64).reshape(-1) for x in (q1, q2, y))
+    if not (q1.shape == q2.shape == y.shape) or q1.size < 1:
+        raise ValueError("q1, q2, y: [B]")
+    B = q1.size
+    d1, d2 = q1 - y, q2 - y
+    mse1, mse2 = float((d1 * d1).mean()), float((d2 * d2).mean())
+    return d1 / B, d2 / B, np.array([0.5 * (mse1 + mse2), mse1, mse2, q1.mean(), q2.mean(), y.mean()], dtype=np.float64)
+
+
+def sac_critic_head_float32(q1, q2, y):
+    """The float32 restatement of dockauv_sac_critic_head: the subtraction and the division are exact IEEE operations, so the two
+    gradients are the device's bit for bit; stats as the kernel forms them (float64 sums of float32 terms, rounded once)."""
+    q1, q2, y = (np.asarray(x, dtype=np.float32).reshape(-1) for x in (q1, q2, y))
+    nf = _F32(q1.size)
+    d1, d2 = q1 - y, q2 - y
+    mse1, mse2 = _mean32(d1 * d1), _mean32(d2 * d2)
+    stats = np.array([_F32(0.5) * (mse1 + mse2), mse1, mse2, _mean32(q1), _mean32(q2), _mean32(y)], dtype=np.float32)
+    return d1 / nf, d2 / nf, stats
+
+
+def sac_actor_head_reference(heads, z, q1_pi, q2_pi, dq1, dq2, ent_coef=None, log_ent_coef=None):
+    """float64 statement of dockauv_sac_actor_head by SB3's formulas as they are written: heads [B, 2 n_u] = (mu | raw log-std), z
+    [B, n_u] the normals of the draw; x = mu + exp(clamp(raw, -20, 2)) z, a = tanh(x), logp = sum_j Normal(mu, std).log_prob(x) -
+    sum_j log(1 - a^2 + 1e-6); actor_loss = mean(alpha logp - min(q1_pi, q2_pi)) with q_pi [B] the critics at a and dq1, dq2
+    [B, n_u] their gradients on a.  Returns (grad_out [B, 2 n_u], stats [4], a, logp): d actor_loss / d heads -- zero on the raw
+    log-std where it lies outside [-20, 2], the edges included as torch.clamp's backward includes them; the minimum's gradient
+    goes to critic 1 on a tie -- and (actor_loss, mean logp, mean min q, alpha)."""
+    alpha = _alpha_of(ent_coef, log_ent_coef, False)
+    heads = np.asarray(heads, dtype=np.float64)
+    B, n_u = heads.shape[0], heads.shape[1] // 2
+    z, dq1, dq2 = (np.asarray(x, dtype=np.float64).reshape(B, n_u) for x in (z, dq1, dq2))
+    q1, q2 = (np.asarray(x, dtype=np.float64).reshape(B) for x in (q1_pi, q2_pi))
+    mu, raw = heads[:, :n_u], heads[:, n_u:]
+    ls = np.clip(raw, -20.0, 2.0)
+    std = np.exp(ls)
+    x = mu + std * z
+    a = np.tanh(x)
+    s = 1.0 - a * a
+    logp = (-((x - mu) ** 2) / (2.0 * std ** 2) - ls - 0.5 * np.log(2.0 * np.pi)).sum(axis=1) - np.log(s + 1e-6).sum(axis=1)
+    w = 2.0 * a * s / (s + 1e-6)                       # d logp / d x
+    sel = np.where((q1 <= q2)[:, None], dq1, dq2)
+    gx = (alpha * w - sel * s) / B
+    inside = (raw >= -20.0) & (raw <= 2.0)
+    g_ls = np.where(inside, gx * std * z - alpha / B, 0.0)
+    mq = np.minimum(q1, q2)
+    stats = np.array([(alpha * logp - mq).mean(), logp.mean(), mq.mean(), alpha], dtype=np.float64)
+    return np.concatenate([gx, g_ls], axis=1), stats, a, logp
+
+
+def sac_actor_head_float32(heads, z, q1_pi, q2_pi, dq1, dq2, ent_coef=None, log_ent_coef=None):
+    """The float32 restatement of dockauv_sac_actor_head (and, in its last two results, of dockauv_sac_sample): include/dockauv.h's
+    expressions in float32 NumPy arrays, ``z`` rounded to float32.  Returns (grad_out, stats [4], a, logp), all float32."""
+    f = _F32
+    alpha = _alpha_of(ent_coef, log_ent_coef, True)
+    heads = np.asarray(heads, dtype=np.float32)
+    B, n_u = heads.shape[0], heads.shape[1] // 2
+    z, dq1, dq2 = (np.asarray(x, dtype=np.float32).reshape(B, n_u) for x in (z, dq1, dq2))
+    q1, q2 = (np.asarray(x, dtype=np.float32).reshape(B) for x in (q1_pi, q2_pi))
+    nf = f(B)
+    mu, raw = heads[:, :n_u], heads[:, n_u:]
+    ls = np.clip(raw, f(-20.0), f(2.0))
+    std = np.exp(ls)
+    x = _fmaf(std, z, mu)
+    a = np.tanh(x)
+    gauss = _fmaf(f(-0.5) * z, z, -(ls + f(0.918938533)))
+    e = np.exp(f(-2.0) * np.abs(x))
+    d = f(1.0) + e
+    s = f(4.0) * e / (d * d)
+    corr = np.log(s + f(1e-6))
+    seq = lambda t: np.add.accumulate(t, axis=1, dtype=np.float32)[:, -1] if t.shape[1] else np.zeros(B, dtype=np.float32)
+    logp = (seq(gauss[:, :4]) - seq(corr[:, :4])) + (seq(gauss[:, 4:]) - seq(corr[:, 4:]))
+    w = (f(2.0) * a) * (s / (s + f(1e-6)))
+    sel = np.where((q1 <= q2)[:, None], dq1, dq2)
+    gx = _fmaf(alpha, w, -(sel * s)) / nf
+    inside = (raw >= f(-20.0)) & (raw <= f(2.0))
+    g_ls = np.where(inside, _fmaf(gx, std * z, -(alpha / nf)), f(0.0)).astype(np.float32)
+    mq = np.minimum(q1, q2)
+    loss = _fmaf(alpha, logp, -mq)
+    stats = np.array([_mean32(loss), _mean32(logp), _mean32(mq), alpha], dtype=np.float32)
+    out = np.concatenate([gx, g_ls], axis=1)
+    for t in (x, a, s, logp, w, gx, g_ls, out):
+        assert t.dtype == np.float32
+    return out, stats, a, logp
+
+
+def ent_coef_step_reference(state, logp, step: int, lr: float, target_entropy: float, betas=(0.9, 0.999), eps: float = 1e-8):
+    """float64 statement of dockauv_sac_ent_coef_step: SB3's ent_coef_loss = -(log_ent_coef * (logp + target_entropy)).mean() and
+    step ``step`` >= 1 of torch.optim.Adam (no weight decay, no amsgrad) on the scalar.  ``state`` = (log_ent_coef, m, v).  Returns
+    (new state [3], stats [4]) = (ent_coef_loss, exp(log_ent_coef) before the step, mean(logp + target_entropy), the new
+    log_ent_coef); nothing is changed in place."""
+    if int(step) < 1:
+        raise ValueError("step counts from 1")
+    p, m, v = (float(x) for x in np.asarray(state, dtype=np.float64).reshape(3))
+    b1, b2 = float(betas[0]), float(betas[1])
+    mean = float((np.asarray(logp, dtype=np.float64).reshape(-1) + float(target_entropy)).mean())
+    g = -mean
+    m = m + (1.0 - b1) * (g - m)
+    v = b2 * v + (1.0 - b2) * g * g
+    step_size, rsq = float(lr) / (1.0 - b1 ** int(step)), 1.0 / np.sqrt(1.0 - b2 ** int(step))
+    p_new = p - step_size * (m / (np.sqrt(v) * rsq + float(eps)))
+    return np.array([p_new, m, v], dtype=np.float64), np.array([-(p * mean), np.exp(p), mean, p_new], dtype=np.float64)
+
+
+def ent_coef_mean_float32(logp, target_entropy: float) -> np.float32:
+    """the mean dockauv_sac_ent_coef_step forms: the add in float32, the sum in float64, one rounding"""
+    return _mean32(np.asarray(logp, dtype=np.float32).reshape(-1) + _F32(target_entropy))
+
+
+def ent_coef_step_float32(state, mean, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8):
+    """The exact float32 statement of dockauv_sac_ent_coef_step's update for a given ``mean`` (``ent_coef_mean_float32``, or the
+    device's own from stats[2]): the host scalars in double rounded once, then include/dockauv.h's order.  Returns (new state [3]
+    float32, ent_coef_loss float32)."""
+    f = _F32
+    p, m, v = (f(x) for x in np.asarray(state, dtype=np.float32).reshape(3))
+    mean = f(mean)
+    c1, c2, b2 = f(1.0 - betas[0]), f(1.0 - betas[1]), f(betas[1])
+    step_size, rsq = f(lr / (1.0 - betas[0] ** int(step))), f(1.0 / np.sqrt(1.0 - betas[1] ** int(step)))
+    g = -mean
+    one = lambda x: f(np.asarray(x).reshape(-1)[0])     # (_fmaf returns at least one dimension)
+    m = one(_fmaf(c1, g - m, m))
+    v = one(_fmaf(c2 * g, g, b2 * v))
+    denom = one(_fmaf(np.sqrt(v), rsq, f(eps)))
+    p_new = p - step_size * (m / denom)
+    out = np.array([p_new, m, v])
+    assert out.dtype == np.float32
+    return out, -(p * mean)
 
 
 class SquashedGaussianMLP:

@@ -121,6 +121,7 @@ class DeviceReplayBuffer:
         self.monitor = (monitor if monitor is not None else env.make_monitor()) if handle_timeout_termination else None
         self.seen = None            # (the carry is zeros: the first call reads it from the env's rows)
         self.index = None           # int64 indices of the last sample(..., want_index=True)
+        self.last_samples = None    # what the last sample(...) returned: the dense copies of the rows self.index names
         self._sample_bufs = {}
 
     # ---------------------------------------------------------------------------------------------- counts and state
@@ -224,7 +225,8 @@ class DeviceReplayBuffer:
                                        index_ptr=0 if idx is None else idx.data_ptr(), stream=self._stream())
         one = (lambda t: t[0]) if G == 1 else (lambda t: t)
         self.index = None if idx is None else one(idx)
-        return ReplaySamples(one(bufs["obs"]), one(bufs["act"]), one(bufs["nxt"]), one(bufs["done"]), one(bufs["rew"]))
+        self.last_samples = ReplaySamples(one(bufs["obs"]), one(bufs["act"]), one(bufs["nxt"]), one(bufs["done"]), one(bufs["rew"]))
+        return self.last_samples
 
     # ---------------------------------------------------------------------------------------------- checkpoint
     def state_dict(self) -> dict:

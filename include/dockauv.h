@@ -1121,11 +1121,12 @@ int dockauv_replay_state(dockauv_replay rb, float** storage, float** carry, long
  * (train() with MODEL = SAC, SAC_HYPER_PARAMS_*) -- the squashed-Gaussian actor (sac.policies.Actor, use_sde = False), Q critics on
  * [obs | action] (ContinuousCritic) and the TD target of SAC.train -- on the tile body of the MLP actor.  Additive: calls that do
  * not use these objects queue exactly what they queued before.  Of the gradient half the library has the networks' share, every
- * matrix product (dockauv_sac_actor_forward_rows, dockauv_sac_actor_backward, dockauv_q_backward, at the end of this file).  What
- * remains outside it: the loss head (the elementwise algebra of the actor, critic and ent_coef losses), ent_coef itself, the
- * optimiser for these roles and the Polyak update; torch on small [B][n_u] tensors and on raw parameter tensors plus
- * dockauv_policy_load / dockauv_sac_actor_load serves until they are.  All pointers below are device pointers unless a descriptor says otherwise; every call
- * is asynchronous on the stream and synchronises nothing.
+ * matrix product (dockauv_sac_actor_forward_rows, dockauv_sac_actor_backward, dockauv_q_backward), and what lies between them:
+ * the loss head (the elementwise algebra of the actor, critic and ent_coef losses: dockauv_sac_sample, dockauv_sac_critic_head,
+ * dockauv_sac_actor_head) and ent_coef itself (dockauv_sac_ent_coef_step), all at the end of this file, so that one SAC gradient
+ * computation needs no torch arithmetic.  What remains outside it: the optimiser for these roles and the Polyak update; torch on
+ * raw parameter tensors plus dockauv_policy_load / dockauv_sac_actor_load serves until they are.  All pointers below are device
+ * pointers unless a descriptor says otherwise; every call is asynchronous on the stream and synchronises nothing.
  *
  * Widths stay <= DOCKAUV_POLICY_MAX_WIDTH (128), one or two hidden layers, tanh or ReLU hidden units.  SB3's SAC default
  * net_arch = [256, 256] does NOT fit: 256 x 256 float32 weights alone exceed the 160 KiB of LDS a group keeps the network in.
@@ -1237,9 +1238,9 @@ int dockauv_sac_target(dockauv_handle h, dockauv_policy actor, dockauv_policy q1
                        const dockauv_sac_target_io* io, void* hip_stream);
 
 /*
- * SAC, the networks' share of the gradient half: every matrix product of SAC.train's three backward passes.  What stays with the
- * learner is elementwise algebra on [B][n_u] tensors (the clamp's mask, exp, tanh and the log-probability of the actor's sample;
- * the three losses) and, until later calls exist, the optimiser and the Polyak update.  All pointers are device pointers, float32
+ * SAC, the networks' share of the gradient half: every matrix product of SAC.train's three backward passes.  The elementwise
+ * algebra on [B][n_u] tensors between them (the clamp's mask, exp, tanh and the log-probability of the actor's sample; the three
+ * losses) is the loss head below; what stays with the learner, until later calls exist, is the optimiser and the Polyak update.  All pointers are device pointers, float32
  * (row_index: int64); every call is asynchronous on the stream and synchronises nothing; every refusal is DOCKAUV_E_INVALID
  * with the field named, before any device call.  Each call takes its own role only and refuses the three others by name;
  * dockauv_policy_forward_rows and dockauv_policy_backward go on refusing both SAC roles.
@@ -1267,7 +1268,7 @@ int dockauv_sac_actor_forward_rows(dockauv_handle h, dockauv_policy actor, const
  * same rows laid out densely in that order), the library's partial sums (allocated at the first backward of the actor, freed by
  * dockauv_policy_destroy; later calls allocate nothing), two launches -- with grad_out [n_rows][2 n_u] = dL/d(out), out as
  * dockauv_sac_actor_forward_rows defines it: columns 0 .. n_u - 1 act on mu, n_u .. 2 n_u - 1 on the raw log-std head.  The clamp's
- * mask (no gradient where the raw value lies outside [-20, 2]) belongs to the head and so to the caller, which has the raw values.
+ * mask (no gradient where the raw value lies outside [-20, 2]) belongs to the head (dockauv_sac_actor_head applies it), which has the raw values.
  * Written, torch.nn.Linear layout, overwritten: dW1 db1 [dW2 db2] of latent_pi, dW_mu db_mu, dW_ls db_ls; a head whose columns of
  * grad_out are all zero gets exact zeros.  The observation rows come through rows / row_stride / row_index as above.  LDS: the
  * kernel of dockauv_policy_backward with 16 rows of output weights and upstream gradients where that has 8: a 36-128-128 actor
@@ -1317,6 +1318,121 @@ int dockauv_q_backward(dockauv_handle h, dockauv_policy critic, const dockauv_q_
  * parameter gradients (dockauv_policy_backward, dockauv_sac_actor_backward, dockauv_q_backward with grads) allocates it.  Read-only
  * bookkeeping, no device call. */
 int dockauv_policy_backward_workspace(dockauv_policy p, float** partial, long long* n_floats);
+
+/*
+ * SAC, the loss head: everything of SAC.train between the forward calls above and the backward calls above, and the learned
+ * entropy coefficient.  Four calls, one launch each, no workspace, nothing allocated.  All pointers are device pointers, float32;
+ * every call is asynchronous on the stream and synchronises nothing; every refusal is DOCKAUV_E_INVALID with the field named,
+ * before any device call.  Reproducible: no floating-point atomics; the bits depend on the inputs, a row's position in the
+ * minibatch, B and n_u only; two calls give the same bits.  The library is built with -ffp-contract=on: only the fmaf written here
+ * are fused.
+ *
+ * Notation.  B = n_rows, n_u = dockauv_n_u.  heads [B][2 n_u] is what dockauv_sac_actor_forward_rows writes, mu | raw log-std;
+ * mu_j = heads[i][j], raw_j = heads[i][n_u + j].  z_j is the rows-form normal of the actor, Philox counter (row_offset + i,
+ * t mod 2^32, j, 5), key = the actor's seed: slot 5 is the stream dockauv_sac_target draws from, so the learner gives the draw of
+ * the actor loss a t (or a row_offset) different from that of the target's draw of the same gradient step (the Python
+ * composition sac_gradients: the target at 2 t, the actor loss at 2 t + 1).  Per action, the actor's expressions above, unchanged:
+ *   ls = fminf(fmaxf(raw_j, -20.0f), 2.0f);  std = expf(ls);  x = fmaf(std, z_j, mu_j);  a_j = tanh(x)
+ *   g_j = fmaf(-0.5f * z_j, z_j, -(ls + 0.918938533f))
+ *   e = expf(-2.0f * fabsf(x));  d = 1.0f + e;  s_j = 4.0f * e / (d * d);  c_j = logf(s_j + 1e-6f)
+ *   logp = (G_lo - C_lo) + (G_hi - C_hi)          (sums from 0.0f in the order of j, j = 0..3 and 4..7)
+ * Sums over the rows: ONE group of 1 024 lanes a call; lane t adds the rows t, t + 1 024, .. in float64, the lanes of a wave are
+ * added by a fixed tree, the sixteen waves in order.  A mean is such a float64 sum of float32 per-row terms divided by B and
+ * rounded to float32 once.  SAC's minibatches are a few hundred to a few thousand rows, where one launch of one group costs less
+ * than a second launch that adds partial sums.
+ *
+ * dockauv_sac_sample: a [B][n_u] and logp [B] of the expressions above, elementwise over heads.  Held bit for bit: for the same
+ * actor, observation rows, t and row_offset, a and logp are the a2 and logp2 dockauv_sac_target writes for those rows.  Refused:
+ * NULL arguments, a wrong struct_size, n_rows < 1, an actor that is not a squashed-Gaussian actor, an actor of another handle.
+ */
+typedef struct dockauv_sac_sample_io {
+    uint32_t struct_size;          /* sizeof(dockauv_sac_sample_io): ABI check */
+    int32_t reserved;
+    const float* heads;            /* [n_rows][2 n_u] */
+    long long n_rows;              /* >= 1 */
+    uint64_t t, row_offset;        /* the normals' counter: (row_offset + i, t mod 2^32, j, 5), key = the actor's seed */
+    float* a;                      /* [n_rows][n_u] */
+    float* logp;                   /* [n_rows] */
+} dockauv_sac_sample_io;
+int dockauv_sac_sample(dockauv_handle h, dockauv_policy actor, const dockauv_sac_sample_io* io, void* hip_stream);
+
+/*
+ * dockauv_sac_critic_head: SB3 1.5's critic_loss = 0.5 * sum_k mse_loss(q_k, y) and its gradient on both critics' outputs.
+ * q1, q2 [B]: dockauv_q_forward on the replayed actions; y [B]: dockauv_sac_target.  Per row
+ *   d1 = q1_i - y_i;  d2 = q2_i - y_i;  grad_q1[i] = d1 / (float)B;  grad_q2[i] = d2 / (float)B
+ * which dockauv_q_backward takes as grad_q.  stats [6]: critic_loss = 0.5f * (mse1 + mse2), mse1, mse2 (the means of d1 * d1 and
+ * d2 * d2, each product in float32), mean q1, mean q2, mean y.  q1_critic must be a Q critic of the handle (it fixes the device;
+ * nothing of it is read).  grad_q1, grad_q2 and stats are overwritten and must not overlap q1, q2, y or one another.
+ */
+typedef struct dockauv_sac_critic_head_io {
+    uint32_t struct_size;          /* sizeof(dockauv_sac_critic_head_io): ABI check */
+    int32_t reserved;
+    const float *q1, *q2, *y;      /* [n_rows] each */
+    long long n_rows;              /* >= 1 */
+    float *grad_q1, *grad_q2;      /* [n_rows] each */
+    float* stats;                  /* [6] */
+} dockauv_sac_critic_head_io;
+int dockauv_sac_critic_head(dockauv_handle h, dockauv_policy q1_critic, const dockauv_sac_critic_head_io* io, void* hip_stream);
+
+/*
+ * dockauv_sac_actor_head: SB3's actor_loss = mean(alpha logp - min(Q1, Q2)(obs, a)) and its gradient on heads, the clamp's mask
+ * applied: grad_out [B][2 n_u] is what dockauv_sac_actor_backward takes.  heads, t, row_offset: the draw of dockauv_sac_sample,
+ * which is formed again here (logp has the bits of that call).  q1_pi, q2_pi [B]: dockauv_q_forward at a.  dq1, dq2 [B][n_u]:
+ * dockauv_q_backward with grads == NULL and grad_q a buffer of 1.0f, so pure dq/da.  alpha = log_ent_coef ? expf(*log_ent_coef) :
+ * ent_coef, as in dockauv_sac_target_io.  Per row and action, in this float32 order:
+ *   w_j   = (2.0f * a_j) * (s_j / (s_j + 1e-6f))                 d logp / d x_j
+ *   sel_j = (q1_pi_i <= q2_pi_i) ? dq1[i][j] : dq2[i][j]         the minimum's gradient; a tie goes to critic 1
+ *   gx    = fmaf(alpha, w_j, -(sel_j * s_j)) / (float)B          d loss / d x_j   (d a / d x = s_j)
+ *   grad_out[i][j]       = gx
+ *   inside               = raw_j >= -20.0f && raw_j <= 2.0f      torch.clamp's backward: both edges included
+ *   grad_out[i][n_u + j] = inside ? fmaf(gx, std * z_j, -(alpha / (float)B)) : 0.0f
+ *   loss_i = fmaf(alpha, logp_i, -fminf(q1_pi_i, q2_pi_i))
+ * Under reparameterisation the Gaussian term's gradient on mu is 0 and on ls is -1: that is the -alpha / B.  stats [4]: actor_loss
+ * (the mean of loss_i), mean logp, mean min q, alpha.  Refused as dockauv_sac_sample, and: a NaN ent_coef when log_ent_coef is
+ * NULL; grad_out or stats overlapping an input or one another.
+ */
+typedef struct dockauv_sac_actor_head_io {
+    uint32_t struct_size;          /* sizeof(dockauv_sac_actor_head_io): ABI check */
+    float ent_coef;                /* alpha when log_ent_coef is NULL */
+    const float* heads;            /* [n_rows][2 n_u] */
+    const float *q1_pi, *q2_pi;    /* [n_rows] each */
+    const float *dq1, *dq2;        /* [n_rows][n_u] each */
+    const float* log_ent_coef;     /* nullable device scalar */
+    long long n_rows;              /* >= 1 */
+    uint64_t t, row_offset;        /* as dockauv_sac_sample_io */
+    float* grad_out;               /* [n_rows][2 n_u] */
+    float* stats;                  /* [4] */
+} dockauv_sac_actor_head_io;
+int dockauv_sac_actor_head(dockauv_handle h, dockauv_policy actor, const dockauv_sac_actor_head_io* io, void* hip_stream);
+
+/*
+ * dockauv_sac_ent_coef_step: the learned temperature, with no object behind it -- SB3's ent_coef_loss = -(log_ent_coef * (logp +
+ * target_entropy).detach()).mean() and one step of torch.optim.Adam on the scalar.  state: the caller's device float [3] =
+ * log_ent_coef, m, v; the caller sets (logf(init), 0, 0), SB3's "auto" is init = 1.  step: the caller's count, >= 1.  logp [B]:
+ * dockauv_sac_sample's.  target_entropy: SB3's "auto" is -n_u.
+ *   mean = (float)((float64 sum of (double)(logp_i + target_entropy)) / B)          (the add in float32)
+ *   g = -mean
+ *   m = fmaf(c1, g - m, m);  v = fmaf(c2 * g, g, b2 * v);  denom = fmaf(sqrtf(v), rsq, eps);  p = p - step_size * (m / denom)
+ * with c1, c2, b2, step_size, rsq the host's, computed in double from step and rounded once exactly as dockauv_optim_step
+ * documents, and eps = (float)eps; no clipping.  before (nullable device float) receives log_ent_coef as it was before the step:
+ * SB3 uses the alpha from before the step in the target and in the actor loss, so `before` is the scalar to hand to
+ * dockauv_sac_target and dockauv_sac_actor_head as log_ent_coef when the step was queued first.  stats (nullable [4]):
+ * ent_coef_loss = -(p_before * mean), expf(p_before), mean, the new p.  Refused: beta1 or beta2 outside [0, 1), eps <= 0, lr < 0 or
+ * not finite, step < 1, n_rows < 1, NULL state or logp, before or stats overlapping state.  The step's scalars travel in the kernel
+ * arguments: as for the optimiser, do not capture the call in a stream capture.
+ */
+typedef struct dockauv_sac_ent_coef_io {
+    uint32_t struct_size;          /* sizeof(dockauv_sac_ent_coef_io): ABI check */
+    float target_entropy;
+    float* state;                  /* [3]: log_ent_coef, m, v; updated in place */
+    const float* logp;             /* [n_rows] */
+    long long n_rows;              /* >= 1 */
+    long long step;                /* >= 1 */
+    double lr, beta1, beta2, eps;
+    float* before;                 /* nullable: one float */
+    float* stats;                  /* nullable [4] */
+} dockauv_sac_ent_coef_io;
+int dockauv_sac_ent_coef_step(dockauv_handle h, const dockauv_sac_ent_coef_io* io, void* hip_stream);
 
 #ifdef __cplusplus
 }
