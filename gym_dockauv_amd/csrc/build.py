@@ -8,10 +8,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(os.path.dirname(HERE), "lib")
 OUT = os.path.join(LIB_DIR, os.environ.get("DOCKAUV_LIB_NAME", "libdockauv.so"))
 SOURCES = ["dockauv_kernels_f32.hip", "dockauv_kernels_f64.hip", "dockauv_kernels_seq.hip", "dockauv_capi.hip", "dockauv_capi_policy.hip",
+           "dockauv_capi_collect.hip", "dockauv_capi_optim.hip", "dockauv_capi_sac.hip",
            "dockauv_p2p.hip", "dockauv_policy.hip", "dockauv_collect.hip", "dockauv_backward.hip", "dockauv_head.hip", "dockauv_optim.hip", "dockauv_monitor.hip",
            "dockauv_update.hip", "dockauv_rewnorm.hip", "dockauv_eval.hip", "dockauv_capi_eval.hip",
            "dockauv_replay.hip", "dockauv_capi_replay.hip", "dockauv_sac.hip", "dockauv_sac_head.hip"]
-DEPS = SOURCES + ["dockauv_step.hip.inc", "dockauv_device.h", "dockauv_capi.h", "dockauv_ride.h", "dockauv_replay.h", "dockauv_policy_tile.h", os.path.join("..", "..", "include", "dockauv.h")]
+DEPS = SOURCES + ["dockauv_step.hip.inc", "dockauv_device.h", "dockauv_capi.h", "dockauv_capi_policy.h", "dockauv_ride.h", "dockauv_replay.h", "dockauv_policy_tile.h", os.path.join("..", "..", "include", "dockauv.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-slp-vectorize: the SLP vectoriser packs independent f32 ops into v_pk_* pairs; on this kernel that costs ~370
 # v_mov to build the aligned register pairs and pushes the step kernel from 113 to ~200 VGPRs (4 -> 2 waves/SIMD)

@@ -1,8 +1,10 @@
-// dockauv_capi.h -- what the translation units of the C ABI share (dockauv_capi.hip, dockauv_capi_policy.hip,
-// dockauv_capi_eval.hip, dockauv_capi_replay.hip, dockauv_p2p.hip): the env handle, error reporting, the step launch.  Internal to libdockauv.so.
+// dockauv_capi.h -- what the translation units of the C ABI share (dockauv_capi.hip, dockauv_capi_policy.hip, dockauv_capi_collect.hip,
+// dockauv_capi_optim.hip, dockauv_capi_sac.hip, dockauv_capi_eval.hip, dockauv_capi_replay.hip, dockauv_p2p.hip): the env handle, error
+// reporting, the step launch, and the pieces every entry point checks alike.  Internal to libdockauv.so.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -70,5 +72,56 @@ int sync_last(dockauv_handle h);      // wait for the stream of the handle's las
 int launch(dockauv_handle h, const dockauv_step_io* io, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // dockauv_p2p.hip; returns a DOCKAUV_* code, message in g_create_error
 int launch_gather(const dockauv_p2p_plan* pl, const void* src, uint32_t stamp, uint32_t wait_stamp, hipStream_t stream);
+
+// ---- what the entry points check alike.  An entry point calls these top to bottom: the order of the calls is the order of refusal.
+
+// a block's struct_size against the library's; `name`: the struct's
+template <class T>
+int check_size(dockauv_handle h, const T* b, const char* name) {
+    if (b->struct_size != sizeof(T)) return fail(h, DOCKAUV_E_INVALID, "%s.struct_size: got %u, library has %zu", name, b->struct_size, sizeof(T));
+    return 0;
+}
+
+// an io or desc block of `fn`: not NULL (`arg`: what the message calls it -- "io", "cio", "the dockauv_rewnorm_io"), then its size
+template <class T>
+int check_block(dockauv_handle h, const T* b, const char* fn, const char* arg, const char* name) {
+    if (!b) return fail(h, DOCKAUV_E_INVALID, "%s: %s is NULL", fn, arg);
+    return check_size(h, b, name);
+}
+
+// the pointers of block `name` that must not be NULL, refused in the list's order
+struct Required {
+    const char* field;
+    const void* p;
+};
+inline int require(dockauv_handle h, const char* name, std::initializer_list<Required> fields) {
+    for (const Required& r : fields)
+        if (!r.p) return fail(h, DOCKAUV_E_INVALID, "%s.%s is NULL", name, r.field);
+    return 0;
+}
+
+// the end of a launch: rc is the launcher's hipError_t (0: queued on `stream`, which becomes the handle's last)
+inline int launch_failed(dockauv_handle h, const char* what, int rc) {
+    return fail(h, DOCKAUV_E_HIP, "%s launch failed: %s", what, hipGetErrorString((hipError_t)rc));
+}
+inline int launched(dockauv_handle h, const char* what, int rc, void* stream) {
+    if (rc != 0) return launch_failed(h, what, rc);
+    h->last_stream = (hipStream_t)stream;
+    return 0;
+}
+
+// what reads the packed float32 rows does not take a float64 handle
+inline int refuse_f64_rows(dockauv_handle h, const char* fn) {
+    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "%s: the packed rows are float32; the handle's precision is DOCKAUV_F64", fn);
+    return 0;
+}
+
+// what follows episodes through the rows needs envs that restart
+inline int refuse_reset_none(dockauv_handle h, const char* fn) {
+    if (h->cfg.reset_mode == DOCKAUV_RESET_NONE)
+        return fail(h, DOCKAUV_E_INVALID, "%s: the handle's reset_mode is DOCKAUV_RESET_NONE: an episode does not restart at the row "
+                    "after a done", fn);
+    return 0;
+}
 
 }  // namespace dockauv

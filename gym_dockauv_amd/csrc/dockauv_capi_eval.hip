@@ -27,9 +27,7 @@ int eval_begin(dockauv_eval e, const int32_t* targets, int uniform_target, hipSt
     HIP_TRY(h, hipMemcpyAsync(e->carry_len, h->B.t_steps, N * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
     const int rc = launch_eval_begin(targets, uniform_target, e->count, e->target, e->ep_return, e->ep_length, e->ep_outcome,
                                      h->cfg.n_envs, e->n_slots, stream);
-    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "evaluation begin launch failed: %s", hipGetErrorString((hipError_t)rc));
-    h->last_stream = stream;
-    return 0;
+    return launched(h, "evaluation begin", rc, stream);
 }
 
 }  // namespace
@@ -45,10 +43,8 @@ int dockauv_eval_create(dockauv_handle h, int max_episodes_per_env, dockauv_eval
     if ((long long)max_episodes_per_env * (long long)h->cfg.n_envs >= (1LL << 31))
         return fail(h, DOCKAUV_E_INVALID, "dockauv_eval_create: max_episodes_per_env %d x n_envs %d: the slot arrays would reach 2^31 elements",
                     max_episodes_per_env, h->cfg.n_envs);
-    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "dockauv_eval_create: the packed rows are float32; the handle's precision is DOCKAUV_F64");
-    if (h->cfg.reset_mode == DOCKAUV_RESET_NONE)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_eval_create: the handle's reset_mode is DOCKAUV_RESET_NONE: an episode does not "
-                    "restart at the row after a done");
+    if (int rc = refuse_f64_rows(h, "dockauv_eval_create")) return rc;
+    if (int rc = refuse_reset_none(h, "dockauv_eval_create")) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     dockauv_eval e = new dockauv_eval_s();
     e->h = h;
@@ -100,18 +96,13 @@ int dockauv_eval_begin(dockauv_eval e, const int32_t* targets, int uniform_targe
 }
 
 int dockauv_eval_scan(dockauv_handle h, dockauv_eval e, const dockauv_eval_io* io, void* hip_stream) {
-    if (!io) return fail(h, DOCKAUV_E_INVALID, "dockauv_eval_scan: io is NULL");
-    if (io->struct_size != sizeof(dockauv_eval_io))
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_eval_io.struct_size: got %u, library has %zu", io->struct_size, sizeof(dockauv_eval_io));
+    if (int rc = check_block(h, io, "dockauv_eval_scan", "io", "dockauv_eval_io")) return rc;
     if (io->n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_eval_io.n_steps: %d must be >= 1", io->n_steps);
-    if (!io->rows_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_eval_io.rows_out is NULL");
-    if (!io->stats) return fail(h, DOCKAUV_E_INVALID, "dockauv_eval_io.stats is NULL");
+    if (int rc = require(h, "dockauv_eval_io", {{"rows_out", io->rows_out}, {"stats", io->stats}})) return rc;
     if (!h) return fail(nullptr, DOCKAUV_E_INVALID, "dockauv_eval_scan: null handle");
     if (!e) return fail(h, DOCKAUV_E_INVALID, "dockauv_eval_scan: null evaluator");
-    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "dockauv_eval_scan: the packed rows are float32; the handle's precision is DOCKAUV_F64");
-    if (h->cfg.reset_mode == DOCKAUV_RESET_NONE)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_eval_scan: the handle's reset_mode is DOCKAUV_RESET_NONE: an episode does not "
-                    "restart at the row after a done");
+    if (int rc = refuse_f64_rows(h, "dockauv_eval_scan")) return rc;
+    if (int rc = refuse_reset_none(h, "dockauv_eval_scan")) return rc;
     if (e->h != h) return fail(h, DOCKAUV_E_INVALID, "dockauv_eval_scan: the evaluator was created for another handle");
     HIP_TRY(h, hipSetDevice(h->device));
     EvalArgs a{};
@@ -132,10 +123,7 @@ int dockauv_eval_scan(dockauv_handle h, dockauv_eval e, const dockauv_eval_io* i
     a.row_stride = h->n_obs + 2;
     a.max_timesteps = h->cfg.max_timesteps;
     a.n_slots = e->n_slots;
-    const int rc = launch_eval_scan(a, hip_stream);
-    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "evaluation launch failed: %s", hipGetErrorString((hipError_t)rc));
-    h->last_stream = (hipStream_t)hip_stream;
-    return 0;
+    return launched(h, "evaluation", launch_eval_scan(a, hip_stream), hip_stream);
 }
 
 int dockauv_eval_state(dockauv_eval e, int32_t** count, int32_t** target, float** ep_return, int32_t** ep_length, uint8_t** ep_outcome,

@@ -37,10 +37,8 @@ int dockauv_replay_create(dockauv_handle h, long long buffer_size, uint64_t seed
     if (!out) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_create: out is NULL");
     *out = nullptr;
     if (buffer_size < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_create: buffer_size %lld must be >= 1", buffer_size);
-    if (h->f64) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_create: the packed rows are float32; the handle's precision is DOCKAUV_F64");
-    if (h->cfg.reset_mode == DOCKAUV_RESET_NONE)
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_create: the handle's reset_mode is DOCKAUV_RESET_NONE: an episode does not "
-                    "restart at the row after a done");
+    if (int rc = refuse_f64_rows(h, "dockauv_replay_create")) return rc;
+    if (int rc = refuse_reset_none(h, "dockauv_replay_create")) return rc;
     const long long N = h->cfg.n_envs;
     const long long cap = buffer_size / N > 1 ? buffer_size / N : 1;   // SB3: max(buffer_size // n_envs, 1)
     if (cap >= (1LL << 31))
@@ -83,26 +81,19 @@ int dockauv_replay_sync(dockauv_handle h, dockauv_replay rb, const float* rows, 
     if (const int rc = check_pair(h, rb, "dockauv_replay_sync")) return rc;
     if (!rows) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_sync: rows is NULL");
     HIP_TRY(h, hipSetDevice(h->device));
-    const int rc = launch_replay_sync(rows, rb->carry[rb->cur], h->cfg.n_envs, h->n_obs, hip_stream);
-    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "replay sync launch failed: %s", hipGetErrorString((hipError_t)rc));
-    h->last_stream = (hipStream_t)hip_stream;
-    return 0;
+    return launched(h, "replay sync", launch_replay_sync(rows, rb->carry[rb->cur], h->cfg.n_envs, h->n_obs, hip_stream), hip_stream);
 }
 
 int dockauv_replay_push(dockauv_handle h, dockauv_replay rb, const dockauv_replay_push_io* io, void* hip_stream) {
     if (const int rc = check_pair(h, rb, "dockauv_replay_push")) return rc;
-    if (!io) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_push: io is NULL");
-    if (io->struct_size != sizeof(dockauv_replay_push_io))
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_push_io.struct_size: got %u, library has %zu", io->struct_size,
-                    sizeof(dockauv_replay_push_io));
+    if (int rc = check_block(h, io, "dockauv_replay_push", "io", "dockauv_replay_push_io")) return rc;
     if (io->n_steps < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_push_io.n_steps: %d must be >= 1", io->n_steps);
     if ((long long)io->n_steps > rb->capacity_steps)
         return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_push_io.n_steps: %d exceeds capacity_steps %lld", io->n_steps, rb->capacity_steps);
     if ((long long)io->n_steps * (long long)h->cfg.n_envs >= (1LL << 31))
         return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_push_io.n_steps: %d x n_envs %d reaches 2^31 records in one push", io->n_steps,
                     h->cfg.n_envs);
-    if (!io->rows_out) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_push_io.rows_out is NULL");
-    if (!io->actions) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_push_io.actions is NULL");
+    if (int rc = require(h, "dockauv_replay_push_io", {{"rows_out", io->rows_out}, {"actions", io->actions}})) return rc;
     if (!io->terminal_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_push_io.terminal_obs is NULL (next_obs where done)");
     HIP_TRY(h, hipSetDevice(h->device));
     ReplayPushArgs a{};
@@ -122,7 +113,7 @@ int dockauv_replay_push(dockauv_handle h, dockauv_replay rb, const dockauv_repla
     a.pos = rb->pos;
     a.capacity_steps = rb->capacity_steps;
     const int rc = launch_replay_push(a, hip_stream);
-    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "replay push launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (rc != 0) return launch_failed(h, "replay push", rc);
     rb->cur ^= 1;
     rb->pos = (rb->pos + io->n_steps) % rb->capacity_steps;
     rb->size = rb->size + io->n_steps < rb->capacity_steps ? rb->size + io->n_steps : rb->capacity_steps;
@@ -132,20 +123,15 @@ int dockauv_replay_push(dockauv_handle h, dockauv_replay rb, const dockauv_repla
 
 int dockauv_replay_sample(dockauv_handle h, dockauv_replay rb, const dockauv_replay_sample_io* io, void* hip_stream) {
     if (const int rc = check_pair(h, rb, "dockauv_replay_sample")) return rc;
-    if (!io) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_sample: io is NULL");
-    if (io->struct_size != sizeof(dockauv_replay_sample_io))
-        return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_sample_io.struct_size: got %u, library has %zu", io->struct_size,
-                    sizeof(dockauv_replay_sample_io));
+    if (int rc = check_block(h, io, "dockauv_replay_sample", "io", "dockauv_replay_sample_io")) return rc;
     if (io->batch_size < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_sample_io.batch_size: %lld must be >= 1", io->batch_size);
     if (io->n_batches < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_sample_io.n_batches: %d must be >= 1", io->n_batches);
     if (io->batch_size >= (1LL << 31) || io->batch_size * (long long)io->n_batches >= (1LL << 31))
         return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_sample_io.batch_size: %lld x n_batches %d reaches 2^31 transitions in one call",
                     io->batch_size, io->n_batches);
-    if (!io->obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_sample_io.obs is NULL");
-    if (!io->actions) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_sample_io.actions is NULL");
-    if (!io->next_obs) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_sample_io.next_obs is NULL");
-    if (!io->rewards) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_sample_io.rewards is NULL");
-    if (!io->dones) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_sample_io.dones is NULL");
+    if (int rc = require(h, "dockauv_replay_sample_io", {{"obs", io->obs}, {"actions", io->actions}, {"next_obs", io->next_obs},
+                                                         {"rewards", io->rewards}, {"dones", io->dones}}))
+        return rc;
     if (rb->size < 1) return fail(h, DOCKAUV_E_INVALID, "dockauv_replay_sample: size is 0: nothing has been pushed");
     HIP_TRY(h, hipSetDevice(h->device));
     ReplaySampleArgs a{};
@@ -166,7 +152,7 @@ int dockauv_replay_sample(dockauv_handle h, dockauv_replay rb, const dockauv_rep
     a.seed = rb->seed;
     a.draws = rb->draws;
     const int rc = launch_replay_sample(a, hip_stream);
-    if (rc != 0) return fail(h, DOCKAUV_E_HIP, "replay sample launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (rc != 0) return launch_failed(h, "replay sample", rc);
     rb->draws += (uint64_t)io->n_batches;
     h->last_stream = (hipStream_t)hip_stream;
     return 0;
