@@ -315,6 +315,7 @@ SYMBOLS = [
     ("dockauv_n_obs", C.c_int, [C.c_void_p]),
     ("dockauv_threads_per_group", C.c_int, [C.c_void_p]),
     ("dockauv_step_uses_current", C.c_int, [C.c_void_p]),
+    ("dockauv_step_uses_capsules", C.c_int, [C.c_void_p]),
     ("dockauv_n_rays", C.c_int, [C.c_void_p]),
     ("dockauv_n_u", C.c_int, [C.c_void_p]),
     ("dockauv_field_width", C.c_int, [C.c_void_p, C.c_int]),

@@ -379,7 +379,7 @@ StepRequest step_request(dockauv_handle h, const dockauv_step_io& io, bool ride)
     const bool extras = io.noise || io.reward_terms || io.conditions || io.nav || io.ray_dist || io.state_dot || h->trace_dev || h->cfg.device_noise;
     return StepRequest{h->f64, h->sym, h->vk, h->has_rays, h->threads, h->cfg.n_envs, ceil_log2(h->n_rays), h->cfg.reset_mode,
                        h->cfg.reward_set, extras, io.terminal_obs != nullptr, io.pack_reward_done == 2 ? 2 : (io.pack_reward_done ? 1 : 0), ride,
-                       h->no_current};
+                       h->no_current, h->cfg.max_capsules, h->cfg.max_spheres};
 }
 
 }  // namespace
@@ -504,6 +504,12 @@ int dockauv_step_uses_current(dockauv_handle h) {
     dockauv_step_io plain{};
     plain.pack_reward_done = 1;
     return select_step(step_request(h, plain, false)).NOCUR ? 0 : 1;
+}
+int dockauv_step_uses_capsules(dockauv_handle h) {
+    if (!h) return DOCKAUV_E_INVALID;
+    dockauv_step_io plain{};
+    plain.pack_reward_done = 1;
+    return select_step(step_request(h, plain, false)).NOCAP ? 0 : 1;
 }
 int dockauv_n_rays(dockauv_handle h) { return h ? h->n_rays : DOCKAUV_E_INVALID; }
 int dockauv_n_u(dockauv_handle h) { return h ? h->n_u_max : DOCKAUV_E_INVALID; }

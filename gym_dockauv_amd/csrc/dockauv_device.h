@@ -323,6 +323,7 @@ struct StepRequest {
     int pack;             // StepIO::pack
     bool ride;            // copy groups ride in this launch (RideLaunch::plan)
     bool no_current;      // the handle's "no water current" property holds (no_current_after_write, below)
+    int max_capsules, max_spheres;   // obstacle slots per env (dockauv_config): who has a sphere-only kernel (nocap_shape)
 };
 
 // the template arguments of the kernel that serves it (RAYS = has_rays, EPG = 64)
@@ -332,6 +333,7 @@ struct StepVariant {
     bool ride;            // step_ride_kernel<..., NT> instead of step_kernel<..., NT, LOG, TERM, WB>
     bool unsupported;     // no such kernel: hipErrorNotSupported (select_sequence: the caller launches the steps one by one)
     bool NOCUR;           // the lean twin without the water current (step_nocur_kernel / _ride_ / _seq_; nocur_shape)
+    bool NOCAP;           // on top of NOCUR: the sphere-only twin without capsule code (step_nocap_kernel / _ride_ / _seq_; nocap_shape)
 };
 
 // "This handle has no water current": V_c = V_min = V_max = 0 in every env for as long as the property holds, so the lean
@@ -388,13 +390,20 @@ inline bool nocur_shape(const StepRequest& r, int NT) {
     return r.vk == VK_LAUV && r.has_rays && NT == 512;
 }
 
+// The group shape that has a sphere-only (NOCAP) twin on top of its lean one: the BlueROV2's ray kernel of 256 threads for a
+// handle with no capsule slot and at least one sphere slot (BASELINE config 3) -- the step carries no capsule code.  The slot
+// counts are handle constants: what takes the twin away is the loss of no_current, with which the whole twin goes.
+inline bool nocap_shape(const StepRequest& r, int NT) {
+    return nocur_shape(r, NT) && r.vk == VK_JOY && r.has_rays && r.max_capsules == 0 && r.max_spheres >= 1;   // (nocur_shape: NT == 256)
+}
+
 inline StepVariant select_step(const StepRequest& r) {
     const bool fast = !r.f64 && r.sym;   // the float32 kernels of the structural fast path
     // product kernels that also deliver terminal observations (TERM): float32, structural fast path, packed rows, the two
     // default group shapes -- what a device-resident learner runs (TorchDocking3d.step(want_terminal_obs=True))
     const bool term_ok = fast && r.vk != VK_DENSEB;
     const bool term_product = term_ok && r.terminal_obs && r.pack && !r.ride;
-    StepVariant v{256, false, false, false, false, false, false};
+    StepVariant v{256, false, false, false, false, false, false, false};
     if (needs_full_kernel(r) || (r.terminal_obs && !term_product)) {
         v.LOG = true;
         v.unsupported = r.ride;   // (the riding gather is a throughput feature)
@@ -404,6 +413,7 @@ inline StepVariant select_step(const StepRequest& r) {
         v.TERM = true;
         if (r.has_rays && r.threads >= 512) v.NT = 512;
         v.NOCUR = r.no_current && nocur_shape(r, v.NT);
+        v.NOCAP = v.NOCUR && nocap_shape(r, v.NT);
         return v;
     }
     // write-through stores while the launch is one round of resident groups, write-back beyond (store_global_): the
@@ -416,6 +426,7 @@ inline StepVariant select_step(const StepRequest& r) {
     v.ride = r.ride && fast && !v.WB;
     v.unsupported = r.ride && !v.ride;
     v.NOCUR = r.no_current && !v.WB && nocur_shape(r, v.NT);
+    v.NOCAP = v.NOCUR && nocap_shape(r, v.NT);
     return v;
 }
 
@@ -427,13 +438,14 @@ inline StepVariant select_step(const StepRequest& r) {
 // (profiles/r4/ab_same_box.txt): write-back stores config 2 3.61 -> 3.39 us per step, config 4 8.72 -> 8.52, but config 3
 // 7.05 -> 7.39: the four-wave ray kernels stay written through.
 inline StepVariant select_sequence(const StepRequest& r) {
-    StepVariant v{group_threads(r.has_rays, r.threads), false, false, false, false, false, false};
+    StepVariant v{group_threads(r.has_rays, r.threads), false, false, false, false, false, false, false};
     v.unsupported = r.f64 || !r.sym || r.vk == VK_DENSEB || needs_full_kernel(r) || r.terminal_obs || r.pack == 0;
     // (the mixed kernel -- two integrating waves writing interleaved lanes of the same lines -- did NOT reproduce the single
     // launches with write-back stores between resident steps, tests/test_gpu_reset.py: written through like config 3's)
     v.WB = !r.has_rays || v.NT == 512 || (v.NT == 256 && many_rounds(r.n_envs) && r.vk != VK_MIXED);
     // (the lean twins: the sequence kernel of each nocur_shape with the stores it has at the BASELINE batch size)
     v.NOCUR = r.no_current && !v.unsupported && nocur_shape(r, v.NT) && !(r.has_rays && v.NT == 256 && v.WB);
+    v.NOCAP = v.NOCUR && nocap_shape(r, v.NT);
     return v;
 }
 

@@ -802,7 +802,8 @@ __device__ __forceinline__ bool sphere_may_be_hit_(T ocx, T d2, T dist, T rad, T
 // Writes pose (6), goal (4), current rows (8) and the capsule slots of the env (caps_blk = capsule rows at this
 // group's first env, ul = lane offset).
 // the 12 (8 for SimpleDocking3d) uniforms of episode `episode` of env `env`
-template <typename T, typename EP>
+// NORING: the caller does not read ring_u (a kernel without capsule code, NOCAP); SphereDocking3d then reads draws 0..6 only
+template <typename T, bool NORING = false, typename EP>
 __device__ __forceinline__ void episode_uniforms_(const EP& E, int env, int episode, T U[12]) {
     const int scn = E.scenario;
     const unsigned long long seed = E.seed;
@@ -811,7 +812,7 @@ __device__ __forceinline__ void episode_uniforms_(const EP& E, int env, int epis
         uint32_t c[4] = {(uint32_t)env, (uint32_t)episode, (uint32_t)blk, 0u};
         // SimpleDocking3d draws 7 uniforms: the third counter block is never looked at (32-bit integer multiplies
         // are quarter rate; a block is ~40 of them)
-        if (blk < 2 || scn != 0) philox4x32_10_(c, (uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32));
+        if (blk < 2 || (scn != 0 && !(NORING && scn == 7))) philox4x32_10_(c, (uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32));
 #pragma unroll
         for (int j = 0; j < 4; ++j) U[blk * 4 + j] = T(c[j] >> 8) * T(1.0 / 16777216.0);
     }
@@ -820,6 +821,8 @@ __device__ __forceinline__ void episode_uniforms_(const EP& E, int env, int epis
 // generate_episode_ computes pose / goal / current of the next episode and the one draw the capsule rows depend on
 // (ring_u: angle of the four-pillar ring); it has no side effects, so that a wave can run it ahead of time.
 // store_capsules_ writes the capsule rows of an env once its episode really ends.
+// (episode_uniforms_<T, NORING> relies on this: scenario 7 -- SphereDocking3d -- reads U[0..6] and nothing of U[8..11] but ring_u.
+// A change that makes scenario 7 read a later draw has to take that scenario out of NORING's skip.)
 template <typename T, typename EP>
 __device__ __forceinline__ void generate_episode_(const EP& E, const T U[12], T pose[6], T goal[4], T cur[8], T& ring_u) {
     const int scn = E.scenario;
@@ -1191,10 +1194,20 @@ constexpr bool tail_params_() {
 // loaded or stored, V_c is not filtered, V_c and nu_c do not travel through lds_hx (rows 12 and 16-18 stay unused), observations
 // 13-15 are written as the +0 they always were, and an episode reset leaves the current rows, which hold what it would write,
 // alone.  The right-hand sides keep their three nu + nu_c additions with nu_c a literal zero: x + 0 is not x for x = -0.
+// NOCAP (on top of NOCUR; the BlueROV2's ray kernel of 256 threads, nocap_shape in dockauv_device.h): the handle has no capsule slot,
+// and the ray stage and the reset carry no capsule code -- no capsule masks (cm_l, wc, cmask are literal zeros, nocap a literal true:
+// row 14 of lds_pose is neither zeroed nor read, row 0 is not read by the ray stage), no capsule loop in the passes, no capsule rows
+// in a reset and no draw of the pillar ring's angle.  Wave 1's zero-trip capsule prefetch and the slot count it leaves in row 0 for
+// the record completion stay: with `ncap` a literal zero there the plain and the riding kernel took 112 / 111 VGPRs against their
+// twins' 107 (a guard rail, DESIGN.md section 3); with the row read 107 / 107 and 2 / 2 SGPR spills against 6 / 7.
+// Measured and left out (profiles/sphere_only/parts.txt): the sphere prefetch spread over waves 1 and 2 with every row requested at
+// once -- the pose barrier never waited for the prefetch, and 32 more row loads per group at the launch's cold start held up the
+// integrating wave's own rows -- and a group-wide skip of spheres out of range in the record completion.
 template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool LOG = false, bool TERM = false, bool WB = false, int KIND = 0,
-          bool NOCUR = false>
+          bool NOCUR = false, bool NOCAP = false>
 __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix = threadIdx.x, const unsigned bix = blockIdx.x) {
     static_assert(!NOCUR || (sizeof(T) == 4 && SYM && !LOG && VK != VK_MIXED && NT / EPG >= 4), "the lean form: see nocur_shape");
+    static_assert(!NOCAP || (NOCUR && RAYS && VK == VK_JOY && NT / EPG == 4), "the sphere-only form: see nocap_shape");
     DOCKAUV_SPAN(0);   // (diagnostic build: the group's very first instructions)
     extern __shared__ __align__(16) unsigned char smem_raw[];
     typedef const __attribute__((address_space(4))) ParamBlock<T, 2> CParams;
@@ -1523,7 +1536,7 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
             for (int k = first; k < n_red_z; k += step) orow[k] = 0.0f;
             for (int k = first; k < W_ * 2; k += step) lds_oa[k * EPG + ule] = T(0);
             if (first == 0 && !SOLO) {
-                lds_pose[14 * EPG + ule] = T(0);   // may-be-hit masks (bit patterns: all zero)
+                if (!NOCAP) lds_pose[14 * EPG + ule] = T(0);   // may-be-hit masks (bit patterns: all zero)
                 lds_pose[15 * EPG + ule] = T(0);
                 if (SHARE_NAV && ule < 2) lds_nav[4 * EPG + ule] = T(0);   // "navigation errors published" flags
             }
@@ -1588,6 +1601,7 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
                 nsph = open ? s_i + 1 : nsph;
             }
             if (SOLO) nsph_r = nsph; else lds_pose[1 * EPG + pe] = T(nsph);
+            if (W == 4 && !MIXED2) DOCKAUV_STAMP_WAVES(28);   // (diagnostic build) slot 30: the sphere rows are in LDS
         }
     }
 
@@ -1596,7 +1610,7 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
         // this step will use it, so it is parked in LDS (read back by the same lane) rather than held in 19 registers
         // through the ray stage.
         T Ub[12], pose_s[6], goal_s[4], cur_s[8], ring_s;
-        episode_uniforms_<T>(E, env0 + (int)ule, episode_in + 1, Ub);
+        episode_uniforms_<T, NOCAP>(E, env0 + (int)ule, episode_in + 1, Ub);
         generate_episode_<T>(E, Ub, pose_s, goal_s, cur_s, ring_s);
 #pragma unroll
         for (int k = 0; k < 6; ++k) lds_spec[k * EPG + ule] = pose_s[k];
@@ -1605,7 +1619,7 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
 #pragma unroll
         for (int k = 0; k < 8; ++k)
             if (!NOCUR) lds_spec[(10 + k) * EPG + ule] = cur_s[k];   // (NOCUR: the resetter writes no current row)
-        lds_spec[18 * EPG + ule] = ring_s;
+        if (!NOCAP) lds_spec[18 * EPG + ule] = ring_s;   // (NOCAP: no capsule rows, nobody reads the ring's angle)
     }
 
     if (MIXED2) owner = loader && (vid_l == wv);
@@ -2268,13 +2282,13 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
                     for (int k = 0; k < 4; ++k) goal_b[k] = lds_spec[(6 + k) * EPG + ule];
 #pragma unroll
                     for (int k = 0; k < 8; ++k) curv[k] = NOCUR ? T(0) : lds_spec[(10 + k) * EPG + ule];
-                    ring_s = lds_spec[18 * EPG + ule];
+                    ring_s = NOCAP ? T(0) : lds_spec[18 * EPG + ule];
                 } else {
                     T Ub[12];
                     episode_uniforms_<T>(E, env0 + (int)ule, ep_next, Ub);
                     generate_episode_<T>(E, Ub, sb, goal_b, curv, ring_s);
                 }
-                store_capsules_<T>(E, g_caps, S, ule, ring_s);
+                if (!NOCAP) store_capsules_<T>(E, g_caps, S, ule, ring_s);   // (NOCAP: the handle has no capsule slot)
             }
 #pragma unroll
             for (int k = 6; k < 12; ++k) sb[k] = T(0);
@@ -2505,9 +2519,10 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
             const bool env_ok = env0 + lane < A.n_envs;
             // lane = env view of the group: may-be-hit masks and "has no capsule" (then the sphere group is group 0 of
             // update_radar_collision, docking3d.py:431-439)
-            const unsigned cm_l = !env_ok ? 0u : (SOLO ? cmask_r : *reinterpret_cast<const unsigned int*>(lds_pose + 14 * EPG + lane));
+            // (NOCAP: no capsule mask, and every env "has no capsule" -- rows 14 and 0 are not read)
+            const unsigned cm_l = (NOCAP || !env_ok) ? 0u : (SOLO ? cmask_r : *reinterpret_cast<const unsigned int*>(lds_pose + 14 * EPG + lane));
             const unsigned sm_l = !env_ok ? 0u : (SOLO ? smask_r : *reinterpret_cast<const unsigned int*>(lds_pose + 15 * EPG + lane));
-            const int nocap_l = ((SOLO ? ncap_r : (int)lds_pose[0 * EPG + lane]) == 0) ? 1 : 0;
+            const int nocap_l = NOCAP ? 1 : (((SOLO ? ncap_r : (int)lds_pose[0 * EPG + lane]) == 0) ? 1 : 0);
             const bool act = (cm_l | sm_l) != 0u;
             const unsigned long long ball = __ballot(act);
             const int n_act = __builtin_amdgcn_readfirstlane(__popcll(ball));
@@ -2566,9 +2581,9 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
                         }
                         e = e0;
                         live = ray_ok;
-                        wc = (unsigned)__builtin_amdgcn_readlane((int)cm_l, e0);
+                        wc = NOCAP ? 0u : (unsigned)__builtin_amdgcn_readlane((int)cm_l, e0);
                         ws = (unsigned)__builtin_amdgcn_readlane((int)sm_l, e0);
-                        nocap = __builtin_amdgcn_readlane(nocap_l, e0) != 0;
+                        nocap = NOCAP || __builtin_amdgcn_readlane(nocap_l, e0) != 0;
                         cmask = wc;
                         smask = ws;
                     } else if constexpr (PL == 4) {
@@ -2581,21 +2596,22 @@ __device__ __forceinline__ void step_body(const DevArgs& A, const unsigned tix =
                         live = ray_ok && slot;
                         // (all 64 lanes take part in the three exchanges: a lane's source lane may sit in a row whose
                         // own slot is empty)
-                        const unsigned cm_e = (unsigned)__shfl((int)cm_l, e, 64), sm_e = (unsigned)__shfl((int)sm_l, e, 64);
-                        nocap = __shfl(nocap_l, e, 64) != 0;
+                        const unsigned cm_e = NOCAP ? 0u : (unsigned)__shfl((int)cm_l, e, 64), sm_e = (unsigned)__shfl((int)sm_l, e, 64);
+                        nocap = NOCAP || __shfl(nocap_l, e, 64) != 0;
                         cmask = live ? cm_e : 0u;
                         smask = live ? sm_e : 0u;
-                        wc = (unsigned)__builtin_amdgcn_readlane((int)cmask, 0) | (unsigned)__builtin_amdgcn_readlane((int)cmask, 16) |
-                             (unsigned)__builtin_amdgcn_readlane((int)cmask, 32) | (unsigned)__builtin_amdgcn_readlane((int)cmask, 48);
+                        wc = NOCAP ? 0u
+                                   : ((unsigned)__builtin_amdgcn_readlane((int)cmask, 0) | (unsigned)__builtin_amdgcn_readlane((int)cmask, 16) |
+                                      (unsigned)__builtin_amdgcn_readlane((int)cmask, 32) | (unsigned)__builtin_amdgcn_readlane((int)cmask, 48));
                         ws = (unsigned)__builtin_amdgcn_readlane((int)smask, 0) | (unsigned)__builtin_amdgcn_readlane((int)smask, 16) |
                              (unsigned)__builtin_amdgcn_readlane((int)smask, 32) | (unsigned)__builtin_amdgcn_readlane((int)smask, 48);
                     } else {
                         const bool slot = p0 + sub < n_act;
                         e = act_list[slot ? p0 + sub : n_act - 1];
                         live = ray_ok && slot;
-                        cmask = live ? *reinterpret_cast<const unsigned int*>(lds_pose + 14 * EPG + e) : 0u;
+                        cmask = (live && !NOCAP) ? *reinterpret_cast<const unsigned int*>(lds_pose + 14 * EPG + e) : 0u;
                         smask = live ? *reinterpret_cast<const unsigned int*>(lds_pose + 15 * EPG + e) : 0u;
-                        nocap = (int)lds_pose[0 * EPG + e] == 0;
+                        nocap = NOCAP || (int)lds_pose[0 * EPG + e] == 0;
                         wc = 0;
                         ws = 0;
                         if (epp <= 8) {   // a few envs per wave: the first lane of each carries its masks
@@ -2937,6 +2953,12 @@ __global__ __launch_bounds__(NT, (min_waves_<T, NT>())) void step_nocur_kernel(c
     step_body<T, VK, SYM, RAYS, EPG, NT, false, TERM, false, 0, true>(A);
 }
 
+// The sphere-only twins of the lean ray kernel (NOCAP on top of NOCUR, see step_body): plain and TERM.
+template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool TERM = false>
+__global__ __launch_bounds__(NT, (min_waves_<T, NT>())) void step_nocap_kernel(const DevArgs A) {
+    step_body<T, VK, SYM, RAYS, EPG, NT, false, TERM, false, 0, true, true>(A);
+}
+
 // The step kernel with copy groups behind the step groups (dockauv_ride.h): the previous step's rows travel to the
 // peers while this step is integrated.
 template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT>
@@ -2959,6 +2981,17 @@ __global__ __launch_bounds__(NT, (min_waves_<T, NT>())) void step_ride_nocur_ker
         return;
     }
     step_body<T, VK, SYM, RAYS, EPG, NT, false, false, false, 1, true>(A);
+}
+// (its sphere-only twin)
+template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT>
+__global__ __launch_bounds__(NT, (min_waves_<T, NT>())) void step_ride_nocap_kernel(const DevArgs A, const RideArgs R) {
+    const unsigned groups = (unsigned)((A.n_envs + EPG - 1) / EPG);
+    if (blockIdx.x >= groups) {
+        extern __shared__ __align__(16) unsigned char smem_raw[];
+        ride_body<NT>(R, blockIdx.x - groups, gridDim.x - groups, reinterpret_cast<uint32_t*>(smem_raw));
+        return;
+    }
+    step_body<T, VK, SYM, RAYS, EPG, NT, false, false, false, 1, true, true>(A);
 }
 
 // The RESIDENT step sequence (round 4; dockauv_step_sequence's fast path for open-loop action sequences: the scripted /
@@ -3039,7 +3072,37 @@ __global__ __launch_bounds__(NT, (min_waves_<T, NT>())) void step_seq_nocur_kern
     }
 }
 
-template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool WB = false, bool NOCUR = false>
+// (and the sphere-only twin of that: NOCAP on top of NOCUR -- a copy for the reason given at step_seq_nocur_kernel)
+template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool WB>
+__global__ __launch_bounds__(NT, (min_waves_<T, NT>())) void step_seq_nocap_kernel(const DevArgs, const SeqArgs) {
+    struct KernArgs { DevArgs A; SeqArgs Q; };   // (the kernarg segment: both arguments by value, 8-byte aligned)
+    static_assert(alignof(DevArgs) == 8 && alignof(SeqArgs) == 8 && sizeof(DevArgs) % 8 == 0, "kernarg layout");
+    typedef const __attribute__((address_space(4))) KernArgs CKA;
+    CKA* ka = (CKA*)__builtin_amdgcn_kernarg_segment_ptr();
+    unsigned tix = threadIdx.x, bix = blockIdx.x;
+    const int n = ka->Q.n;
+    for (int k = 0; k < n; ++k) {
+        asm volatile("" : "+s"(ka));
+        asm volatile("" : "+v"(tix));
+        asm volatile("" : "+s"(bix));
+        union { DevArgs a; unsigned long long w[sizeof(DevArgs) / 8]; } Ak;
+        typedef const __attribute__((address_space(4))) unsigned long long CW8;
+        CW8* const src = (CW8*)ka;
+#pragma unroll
+        for (unsigned i = 0; i < sizeof(DevArgs) / 8; ++i) Ak.w[i] = src[i];
+        Ak.a.io.actions = ka->Q.actions[k];
+        Ak.a.io.obs = ka->Q.obs[k];
+        step_body<T, VK, SYM, RAYS, EPG, NT, false, false, WB, 2, true, true>(Ak.a, tix, bix);
+        if (k + 1 < n) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            if (NT > 64) __builtin_amdgcn_s_barrier();
+            asm volatile("buffer_inv sc0" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        }
+    }
+}
+
+template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool WB = false, bool NOCUR = false, bool NOCAP = false>
 static int launch_seq_one(const KernelArgs<T, 2>& a, const SeqArgs& seq, void* stream) {
     const EnvP<T>& E = a.P.E;
     const int groups = (E.n_envs + EPG - 1) / EPG;
@@ -3050,7 +3113,10 @@ static int launch_seq_one(const KernelArgs<T, 2>& a, const SeqArgs& seq, void* s
     d.io = a.io;
     d.n_envs = E.n_envs;
     void (*kernel)(const DevArgs, const SeqArgs);
-    if constexpr (NOCUR) kernel = &step_seq_nocur_kernel<T, VK, SYM, RAYS, EPG, NT, WB>; else kernel = &step_seq_kernel<T, VK, SYM, RAYS, EPG, NT, WB>;
+    static_assert(!NOCAP || NOCUR, "the sphere-only twins stand on the lean ones");
+    if constexpr (NOCAP) kernel = &step_seq_nocap_kernel<T, VK, SYM, RAYS, EPG, NT, WB>;
+    else if constexpr (NOCUR) kernel = &step_seq_nocur_kernel<T, VK, SYM, RAYS, EPG, NT, WB>;
+    else kernel = &step_seq_kernel<T, VK, SYM, RAYS, EPG, NT, WB>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
@@ -3069,6 +3135,7 @@ static int launch_seq_vk(const KernelArgs<T, 2>& a, const StepRequest& r, const 
     if (v.NOCUR) {   // (the lean twins: nocur_shape)
         if constexpr (VK == VK_JOY) {
             if (is(false, 256, true)) return launch_seq_one<T, VK, true, false, 64, 256, true, true>(a, seq, stream);
+            if (v.NOCAP && is(true, 256, false)) return launch_seq_one<T, VK, true, true, 64, 256, false, true, true>(a, seq, stream);
             if (is(true, 256, false)) return launch_seq_one<T, VK, true, true, 64, 256, false, true>(a, seq, stream);
         }
         if constexpr (VK == VK_LAUV) {
@@ -3088,11 +3155,16 @@ static int launch_seq_vk(const KernelArgs<T, 2>& a, const StepRequest& r, const 
 
 // ------------------------------------------------------------------------------------------ launchers
 // NOCUR: the lean twin of a plain or TERM product kernel (step_nocur_kernel / step_ride_nocur_kernel)
-template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool LOG = false, bool TERM = false, bool WB = false, bool NOCUR = false>
+// NOCAP: the sphere-only twin of that (step_nocap_kernel / step_ride_nocap_kernel)
+template <typename T, int VK, bool SYM, bool RAYS, int EPG, int NT, bool LOG = false, bool TERM = false, bool WB = false, bool NOCUR = false,
+          bool NOCAP = false>
 static int launch_one(const KernelArgs<T, 2>& a, void* stream, void* ev0, void* ev1) {
     static_assert(!NOCUR || (!LOG && !WB), "the lean twins: plain and TERM product kernels");
+    static_assert(!NOCAP || NOCUR, "the sphere-only twins stand on the lean ones");
     void (*kernel)(const DevArgs);
-    if constexpr (NOCUR) kernel = &step_nocur_kernel<T, VK, SYM, RAYS, EPG, NT, TERM>; else kernel = &step_kernel<T, VK, SYM, RAYS, EPG, NT, LOG, TERM, WB>;
+    if constexpr (NOCAP) kernel = &step_nocap_kernel<T, VK, SYM, RAYS, EPG, NT, TERM>;
+    else if constexpr (NOCUR) kernel = &step_nocur_kernel<T, VK, SYM, RAYS, EPG, NT, TERM>;
+    else kernel = &step_kernel<T, VK, SYM, RAYS, EPG, NT, LOG, TERM, WB>;
     const EnvP<T>& E = a.P.E;
     const int groups = (E.n_envs + EPG - 1) / EPG;
     const size_t lds = lds_bytes<T>(EPG, NT, E.max_cap, E.max_sph, E.n_obs, RAYS, E.ray_pad_log2);
@@ -3114,7 +3186,9 @@ static int launch_one(const KernelArgs<T, 2>& a, void* stream, void* ev0, void* 
         // separate gather kernel otherwise
         if constexpr (sizeof(T) == 4 && SYM) {
             void (*ride_kernel)(const DevArgs, const RideArgs);
-            if constexpr (NOCUR) ride_kernel = &step_ride_nocur_kernel<T, VK, SYM, RAYS, EPG, NT>; else ride_kernel = &step_ride_kernel<T, VK, SYM, RAYS, EPG, NT>;
+            if constexpr (NOCAP) ride_kernel = &step_ride_nocap_kernel<T, VK, SYM, RAYS, EPG, NT>;
+            else if constexpr (NOCUR) ride_kernel = &step_ride_nocur_kernel<T, VK, SYM, RAYS, EPG, NT>;
+            else ride_kernel = &step_ride_kernel<T, VK, SYM, RAYS, EPG, NT>;
             if (lds > 64 * 1024) {
                 hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ride_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 if (e != hipSuccess) return (int)e;
@@ -3150,6 +3224,11 @@ static int launch_vk(const KernelArgs<T, 2>& a, const StepRequest& r, void* stre
     constexpr bool TERM_OK = sizeof(T) == 4 && SYM && VK != VK_DENSEB;
     if (v.NOCUR) {   // (the lean twins: nocur_shape; launch_one takes the ride branch of a plain one)
         if constexpr (sizeof(T) == 4 && SYM && VK == VK_JOY) {
+            if (v.NOCAP) {   // (the sphere-only twins: nocap_shape)
+                if (is(true, 256)) return launch_one<T, VK, SYM, true, 64, 256, false, false, false, true, true>(a, stream, ev0, ev1);
+                if (is(true, 256, false, true)) return launch_one<T, VK, SYM, true, 64, 256, false, true, false, true, true>(a, stream, ev0, ev1);
+                return (int)hipErrorNotSupported;
+            }
             if (is(false, 256)) return launch_one<T, VK, SYM, false, 64, 256, false, false, false, true>(a, stream, ev0, ev1);
             if (is(true, 256)) return launch_one<T, VK, SYM, true, 64, 256, false, false, false, true>(a, stream, ev0, ev1);
             if (is(false, 256, false, true)) return launch_one<T, VK, SYM, false, 64, 256, false, true, false, true>(a, stream, ev0, ev1);

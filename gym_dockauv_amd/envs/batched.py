@@ -617,6 +617,12 @@ class BatchedDocking3d:
         a scenario without current and no non-zero current row written since the handle was created)."""
         return bool(self._lib.dockauv_step_uses_current(self._handle))
 
+    @property
+    def step_uses_capsules(self) -> bool:
+        """False while the next plain step runs the sphere-only kernel (dockauv_step_uses_capsules: the lean kernel of a BlueROV2
+        handle with a ray fan, no capsule slot and at least one sphere slot)."""
+        return bool(self._lib.dockauv_step_uses_capsules(self._handle))
+
     def set_sequence_resident(self, on: bool) -> None:
         """Switch the resident fast path of run_step_sequence (on by default) for this handle."""
         rc = self._lib.dockauv_set_option(self._handle, _capi.OPT_SEQUENCE_RESIDENT, 1 if on else 0)

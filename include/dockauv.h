@@ -207,6 +207,10 @@ int dockauv_threads_per_group(dockauv_handle h);
  * DOCKAUV_F_CURRENT / DOCKAUV_F_POOL_CURRENT rows other than exact zeros since dockauv_create; the first such write switches the
  * handle to the general kernels for good.  Same results either way, bit for bit.  No reference counterpart: a tuning read-out. */
 int dockauv_step_uses_current(dockauv_handle h);
+/* 1: the next plain step runs a step kernel that carries the capsule code; 0: the sphere-only one -- the lean kernel above for a
+ * BlueROV2 handle with a ray fan, 256 threads per group, no capsule slot and at least one sphere slot.  It goes with the lean
+ * kernel: the first non-zero current row switches the handle to the general kernels.  Same results either way, bit for bit. */
+int dockauv_step_uses_capsules(dockauv_handle h);
 int dockauv_n_rays(dockauv_handle h);
 int dockauv_n_u(dockauv_handle h);
 

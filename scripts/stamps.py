@@ -78,7 +78,11 @@ for i, nm in ((10, "ray stage entered / hand-over received"), (22, "active list 
     v = med(i)
     if not np.isnan(v):
         print(f"    {nm:<42s} at {v:8.0f}")
-arr = [med(24 + w) for w in range(8)]
+if np.isnan(med(28)) and not np.isnan(med(30)):   # (groups of four waves: the prefetching waves stamp slot 28 + wave once their sphere rows are in LDS)
+    print("  sphere prefetch done (rows in LDS): " + "  ".join(f"wave {w}@{med(28 + w):.0f}" for w in (1, 2) if not np.isnan(med(28 + w)))
+          + f";  wave 0 publishes the pose@{med(14):.0f}")
+NW = env.threads_in_use // 64   # (slots 24 + wave of the waves that exist; four-wave groups use 29 / 30 for the prefetch stamp)
+arr = [med(24 + w) if w < NW else np.nan for w in range(8)]
 if not all(np.isnan(a) for a in arr):
     print("  arrival of (physical) waves 0.. at the barrier behind the ray stage: " + "  ".join("-" if np.isnan(a) else f"{a:.0f}" for a in arr))
 tt = total[:, :, 0]
@@ -89,7 +93,7 @@ worst = np.nanargmax(tt, axis=1)
 sel = rel[np.arange(rel.shape[0]), worst]          # [launch, stamp]
 print("  slowest sampled group of each launch, medians: " + "  ".join(f"{nm.split()[0]}@{np.nanmedian(sel[:, i]):.0f}" for i, nm in
       ((2, "landed"), (3, "rk"), (14, "publish"), (15, "records"), (4, "raydone"), (5, "navobs"), (8, "wb"), (9, "end")) if not np.all(np.isnan(sel[:, i]))))
-arr_w = [np.nanmedian(sel[:, 24 + w]) for w in range(8)]
+arr_w = [np.nanmedian(sel[:, 24 + w]) if w < NW else np.nan for w in range(8)]
 if not all(np.isnan(a_) for a_ in arr_w):
     print("  slowest sampled group of each launch: arrival of (physical) waves 0.. at the barrier behind the ray stage: "
           + "  ".join("-" if np.isnan(a_) else f"{a_:.0f}" for a_ in arr_w)
