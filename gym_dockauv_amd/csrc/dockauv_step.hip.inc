@@ -683,8 +683,11 @@ __device__ __forceinline__ T ray_capsule_(const CapRec<T>& c, T bx, T by, T bz) 
         const T cap = (h2 > T(0)) ? (-b2 - sqrt_(abs_(h2))) : T(0);
         res = shaft ? t : cap;
         // y NaN (ray parallel to the axis, a == 0): the reference tests the cap sphere with oc = 0 and gets -r
-        // (shape.py:377); any negative number gives the same clamped distance
-        res = isnan_(y) ? T(-1) : res;
+        // (shape.py:377); any negative number gives the same clamped distance.  The reference's a = |ba|^2 - (ba.rd)^2
+        // cancels to exactly 0 for every ray within ~1e-8 rad of the axis (sin^2 < 2^-53), not only for bard == 1: |q|^2
+        // here keeps 1e-32 for the central ray (1, 1.1e-16, 1.1e-16) of the shipped fans along an x-aligned axis and used
+        // to answer the cap hit where the reference answers a miss (tests/golden/g4_rays.npz: edge cases 3 and 4)
+        res = (isnan_(y) || a < T(1.1102230246251565e-16)) ? T(-1) : res;
     }
     // an exact zero -> -inf  (shape.py:386-388)
     return (hit && res != T(0)) ? res : -inf_<T>();
